@@ -5,20 +5,29 @@ One "step" = one rsl_rl learning iteration of the drop-in runner on synthetic Go
 terrain: 24 env steps (policy act + fused HIP env step + storage + the per-step episode
 bookkeeping train.py's runner does, on_policy_runner.py:160-170) + GAE + the PPO/ROA update
 (5 epochs x 4 minibatches) — i.e. Perf/total_fps of on_policy_runner.py:219.
-value = num_envs x 24 x world_size x K / (max over ranks of the timed K iterations), the MEDIAN
-of 3 windows of K iterations each (`windows` lists all three, with the GPU shader clock read
-after each); `value_no_episode_tracking` is one window of the same loop without the bookkeeping.
-The windows avoid the runner's DAgger iterations (it % 20 == 0, on_policy_runner.py:147) when
-W + K <= 18.
+value = num_envs x 24 x world_size x K / (max over ranks of the timed K iterations).
 
-Also reported: `roofline` of the env-step kernel (algorithmic bytes per launch over its
-HIP-event-timed duration vs 8 TB/s HBM; the kernel is not HBM-bound: `roofline_valu` gives
+A plain run does only what that figure needs: set-up (two untimed iterations: the DAgger
+iteration 0 and the first PPO iteration, which compile, allocate and capture the graphs), then
+one window of W warm-up + K timed iterations starting right after a DAgger iteration
+(it % 20 == 0, on_policy_runner.py:147), so none is inside when W + K <= 18; `ms_per_step` is
+the wall time of one of the K timed iterations. `--dump-outputs DIR` then writes what the last
+timed iteration left its caller (observations, robot state, the rollout's actions / rewards /
+values and, where the step has a learner, the returns and the updated network parameters) as
+DIR/<name>.npy (float32; at most 64 MB in all: a larger array is cut to a fixed, seeded sample
+of its elements). The inputs (seed 1) are the same from run to run.
+
+`--full` adds everything else: value becomes the MEDIAN of 3 such windows (`windows` lists all
+three, with the GPU shader clock read after each; `window_spread`), after one window of the same
+loop without the episode bookkeeping (`value_no_episode_tracking`); `env_kernel` and `roofline`
+of the env-step kernel (algorithmic bytes per launch over its HIP-event-timed duration vs
+8 TB/s HBM; the kernel is not HBM-bound: `roofline_valu` gives
 its VALU issue utilisation and wait fraction from the committed PMC profile), `roofline_learner`, and
 `cpu_baseline`: the same framework on the host (--sim_device=cpu --rl_device=cpu: liblgx.so's
 host backend, OpenMP over envs, + the torch-CPU learner) at the same shape (one iteration),
 rank 0 at N=1 only.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--num_envs 4096]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--num_envs 4096] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -268,6 +277,40 @@ def cpu_baseline(num_envs=4096, iters=3, steps_per_env=24):
             "learn_s": round(perf.get("learn_time", 0.0), 3)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, runner, env, learner=True):
+    """What the last timed iteration left its caller, as <out_dir>/<name>.npy (float32): the
+    env's observation buffers and robot state, the last rollout's rows in the storage, and
+    (learner=True: the iteration ran GAE and the update) the returns and the network parameters
+    after the last update. The arrays share DUMP_LIMIT_BYTES equally; one above its share is
+    cut to a fixed (seed 0), sorted sample of its flattened elements."""
+    import numpy as np
+    st = runner.alg.storage
+
+    def flat(module):
+        return torch.cat([v.detach().reshape(-1).float() for _, v in sorted(module.state_dict().items())])
+
+    arrays = {"obs": env.get_observations(), "privileged_obs": env.get_privileged_observations(),
+              "critic_obs": env.get_critic_observations(), "root_states": env.root_states,
+              "dof_pos": env.dof_pos, "dof_vel": env.dof_vel,
+              "rollout_actions": st.actions, "rollout_rewards": st.rewards, "rollout_values": st.values}
+    if learner:
+        arrays.update({"rollout_returns": st.returns, "actor_critic_params": flat(runner.alg.actor_critic),
+                       "estimator_params": flat(runner.alg.estimator)})
+    arrays = {k: v for k, v in arrays.items() if torch.is_tensor(v)}
+    os.makedirs(out_dir, exist_ok=True)
+    # the share, and with it the sampled indices of a large array, depends on how many arrays
+    # there are: add or drop one and dumps of the two bench.py versions no longer line up
+    share = DUMP_LIMIT_BYTES // len(arrays) // 4  # elements per array
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def rollout_only(args, runner, env, dev, world, rank, barrier):
     """C3: ANYmal-C rough trimesh + height scan, the env step plus the actor /
     critic / encoder forward in privileged-latent mode, 24 steps per iteration as the runner's
@@ -295,21 +338,27 @@ def rollout_only(args, runner, env, dev, world, rank, barrier):
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
-    # env kernel alone (HIP events on the launch stream)
-    stream = torch.cuda.current_stream(dev)
-    g = torch.Generator(device=dev).manual_seed(1234)
-    n_k = args.kernel_iters
-    acts = torch.randn(n_k, env.num_envs, env.num_actions, device=dev, generator=g)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_k)]
-    for i in range(n_k):
-        env.actions_in.copy_(acts[i])
-        env.common_step_counter += 1
-        evs[i][0].record(stream)
-        env._native.step(env.seed, env.common_step_counter, stream.cuda_stream)
-        evs[i][1].record(stream)
-    torch.cuda.synchronize(dev)
-    kern_ms = sorted(a.elapsed_time(b) for a, b in evs)
-    kern_avg = sum(kern_ms) / len(kern_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, env, learner=False)  # no GAE, no update here
+    extra = {}
+    if args.full:
+        # env kernel alone (HIP events on the launch stream)
+        stream = torch.cuda.current_stream(dev)
+        g = torch.Generator(device=dev).manual_seed(1234)
+        n_k = args.kernel_iters
+        acts = torch.randn(n_k, env.num_envs, env.num_actions, device=dev, generator=g)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_k)]
+        for i in range(n_k):
+            env.actions_in.copy_(acts[i])
+            env.common_step_counter += 1
+            evs[i][0].record(stream)
+            env._native.step(env.seed, env.common_step_counter, stream.cuda_stream)
+            evs[i][1].record(stream)
+        torch.cuda.synchronize(dev)
+        kern_ms = sorted(a.elapsed_time(b) for a, b in evs)
+        kern_avg = sum(kern_ms) / len(kern_ms)
+        extra["env_kernel"] = {"avg_us": round(kern_avg * 1e3, 2), "min_us": round(kern_ms[0] * 1e3, 2),
+                               "env_steps_per_s": round(env.num_envs / (kern_avg * 1e-3), 1)}
     if rank == 0:
         total = args.num_envs * steps * world * args.steps
         print(json.dumps({
@@ -322,8 +371,7 @@ def rollout_only(args, runner, env, dev, world, rank, barrier):
             "config": {"workload": f"{args.task} rollout: {steps} x (act in privileged-latent mode + env step)",
                        "num_envs_per_gpu": args.num_envs, "num_steps_per_env": steps,
                        "global_envs": args.num_envs * world, "parallelism": f"env-sharded dp{world}"},
-            "env_kernel": {"avg_us": round(kern_avg * 1e3, 2), "min_us": round(kern_ms[0] * 1e3, 2),
-                           "env_steps_per_s": round(env.num_envs / (kern_avg * 1e-3), 1)}}))
+            **extra}))
     if world > 1:
         dist.destroy_process_group()
 
@@ -334,8 +382,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--num_envs", type=int, default=4096)
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--kernel_iters", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also: 3 windows (median) after a window without episode tracking, env-kernel timing, "
+                         "rooflines, cpu_baseline")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--kernel_iters", type=int, default=50, help="with --full: env-kernel launches timed alone")
     ap.add_argument("--task", default="go2", help="go2 (the BASELINE metric) | go2_parkour (C4) | anymal_c_rough "
                                                   "(C3: rollout only)")
     args = ap.parse_args()
@@ -403,20 +456,70 @@ def main():
 
     if args.task.startswith("anymal"):
         return rollout_only(args, runner, env, dev, world, rank, barrier)
-    elapsed_nt, perf_nt = timed(False)  # iterations 0..W-1 warm-up (0 is a DAgger iteration), then W..W+K-1
-    # the headline, as train.py runs it: 3 windows, each W warm-up + K timed iterations starting
-    # right after a DAgger iteration (it % 20 == 0, on_policy_runner.py:147), so none is inside
+    if args.full:
+        elapsed_nt, perf_nt = timed(False)  # iterations 0..W-1 warm-up (0 is a DAgger iteration), then W..W+K-1
+    else:
+        # set-up: the DAgger iteration 0 and the first PPO iteration (first use of every kernel,
+        # the eager update, the capture of the rollout and update graphs)
+        runner.track_episodes = True
+        runner.learn(num_learning_iterations=2, init_at_random_ep_len=True)
+    # the headline, as train.py runs it: W warm-up + K timed iterations starting right after a
+    # DAgger iteration (it % 20 == 0, on_policy_runner.py:147), so none is inside; 3 such
+    # windows with --full
     steps_per_iter = train_cfg.runner.num_steps_per_env
     total_env_steps = args.num_envs * steps_per_iter * world * args.steps
     windows = []
-    for w in range(3):
+    for w in range(3 if args.full else 1):
         runner.current_learning_iteration = 20 * (w + 1) + 1
         el_w, perf_w = timed(True)
         windows.append((el_w, perf_w, sclk_mhz()))
-    order = sorted(range(3), key=lambda i: windows[i][0])
-    elapsed, perf, _clk = windows[order[1]]
+    order = sorted(range(len(windows)), key=lambda i: windows[i][0])
+    elapsed, perf, _clk = windows[order[len(windows) // 2]]
     value = total_env_steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runner, env)
 
+    if rank == 0:
+        data = ("synthetic (Go2 flat terrain, random-init ActorCritic/estimator, seed 1)" if args.task == "go2" else
+                f"synthetic ({args.task}: generated terrain, random-init ActorCritic/estimator, seed 1)")
+        out = {
+            "metric": METRIC if args.task == "go2" else f"env-steps/sec, {args.task} {args.num_envs} envs per GPU", "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "data": data,
+            "config": {"workload": f"{args.task}, rsl_rl PPO/ROA iteration (24 env steps + 5x4 minibatch update)",
+                       "num_envs_per_gpu": args.num_envs, "num_steps_per_env": steps_per_iter,
+                       "global_envs": args.num_envs * world, "parallelism": f"env-sharded dp{world}"},
+            "windows": [{"value": round(total_env_steps / el, 1), "ms_per_step": round(el / args.steps * 1e3, 3),
+                         "sclk_mhz": clk} for el, _p, clk in windows],
+            # which code paths the timed iterations ran (no silent fallback: ppo.py / s8_*.py raise
+            # on a missing library; these say which of the built paths were selected)
+            "paths": {"learner": "s8" if runner.alg._s8 is not None else "autograd",
+                      "act": "fused" if runner.alg._s8act is not None else "grouped",
+                      "graph_mode": runner.alg.graph_mode,
+                      "dagger": runner.alg.dagger_path, "dagger_graph_mode": runner.alg.dagger_graph_mode,
+                      "rollout_graphs": sorted(str(k) for k in runner._graphs)},
+            # the native libraries that ran (mapped by this process) and any LGX_* variables set
+            "binaries": loaded_binaries(),
+            "env_overrides": {k: v for k, v in sorted(os.environ.items()) if k.startswith("LGX_")},
+            "collection_s": round(perf.get("collection_time", 0.0), 4),
+            "learn_s": round(perf.get("learn_time", 0.0), 4),
+        }
+    if args.full:
+        extra = full_extras(args, env, dev, world, rank)
+        if rank == 0:
+            out["value_no_episode_tracking"] = round(total_env_steps / elapsed_nt, 1)
+            out["window_spread"] = round((max(w[0] for w in windows) - min(w[0] for w in windows)) / elapsed, 4)
+            out.update(extra)
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_extras(args, env, dev, world, rank):
+    """--full: the env-step kernel alone (every rank steps its env; rank 0 reports `env_kernel`
+    and `roofline`), `roofline_valu`, `roofline_learner` and `cpu_baseline`."""
     # ---- env-step kernel alone (HIP events on the launch stream) -> roofline
     g = torch.Generator(device=dev).manual_seed(1234)
     acts = torch.clamp(torch.randn(args.kernel_iters, env.num_envs, env.num_actions, device=dev, generator=g), -3.14, 3.14)
@@ -440,57 +543,31 @@ def main():
     achieved = launch_bytes / (kern_avg_ms * 1e-3) / 1e9
     traffic, traffic_src = committed_traffic(args.num_envs) if args.task == "go2" else (None, None)
 
-    if rank == 0:
-        terrain = env.cfg.terrain.mesh_type in ("heightfield", "trimesh")
-        # two envs per wavefront (EPW 2) by default on the plane with an even env count (lgx_env.hip launch_step)
-        actnet = bool(getattr(env.cfg.control, "use_actuator_network", False))
-        epw = 2 if (env.num_envs % 2 == 0 and not actnet and not terrain) else 1
-        kname = f"lgx::env_step_kernel<true, {'true' if terrain else 'false'}, {'true' if actnet else 'false'}, {epw}>"
-        data = ("synthetic (Go2 flat terrain, random-init ActorCritic/estimator, seed 1)" if args.task == "go2" else
-                f"synthetic ({args.task}: generated terrain, random-init ActorCritic/estimator, seed 1)")
-        out = {
-            "metric": METRIC if args.task == "go2" else f"env-steps/sec, {args.task} {args.num_envs} envs per GPU", "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": data,
-            "config": {"workload": f"{args.task}, rsl_rl PPO/ROA iteration (24 env steps + 5x4 minibatch update)",
-                       "num_envs_per_gpu": args.num_envs, "num_steps_per_env": steps_per_iter,
-                       "global_envs": args.num_envs * world, "parallelism": f"env-sharded dp{world}"},
-            "value_no_episode_tracking": round(total_env_steps / elapsed_nt, 1),
-            "windows": [{"value": round(total_env_steps / el, 1), "ms_per_step": round(el / args.steps * 1e3, 3),
-                         "sclk_mhz": clk} for el, _p, clk in windows],
-            "window_spread": round((max(w[0] for w in windows) - min(w[0] for w in windows)) / elapsed, 4),
-            # which code paths the timed iterations ran (no silent fallback: ppo.py / s8_*.py raise
-            # on a missing library; these say which of the built paths were selected)
-            "paths": {"learner": "s8" if runner.alg._s8 is not None else "autograd",
-                      "act": "fused" if runner.alg._s8act is not None else "grouped",
-                      "graph_mode": runner.alg.graph_mode,
-                      "dagger": runner.alg.dagger_path, "dagger_graph_mode": runner.alg.dagger_graph_mode,
-                      "rollout_graphs": sorted(str(k) for k in runner._graphs)},
-            # the native libraries that ran (mapped by this process) and any LGX_* variables set
-            "binaries": loaded_binaries(),
-            "env_overrides": {k: v for k, v in sorted(os.environ.items()) if k.startswith("LGX_")},
-            "collection_s": round(perf.get("collection_time", 0.0), 4),
-            "learn_s": round(perf.get("learn_time", 0.0), 4),
-            "env_kernel": {"avg_us": round(kern_avg_ms * 1e3, 2), "min_us": round(kern_ms[0] * 1e3, 2),
-                           "env_steps_per_s": round(env.num_envs / (kern_avg_ms * 1e-3), 1)},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "bytes_per_env_step": bpe, "bytes_per_launch": launch_bytes,
-                         "traffic": None if traffic is None else round(traffic), "traffic_source": traffic_src,
-                         "note": "the kernel's algorithmic bytes vs HBM peak, as north_star asks; it is bound by "
-                                 "per-env latency (LDS round trips, dependent lane exchanges), not HBM (roofline_valu, "
-                                 "DESIGN.md 4.1)"},
-        }
-        if args.task == "go2" and args.num_envs == 4096:
-            out["roofline_valu"] = committed_valu(args.num_envs)
-        if args.task == "go2":
-            out["roofline_learner"] = learner_gemm_roofline(dev)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
-        print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+    if rank != 0:
+        return None
+    terrain = env.cfg.terrain.mesh_type in ("heightfield", "trimesh")
+    # two envs per wavefront (EPW 2) by default on the plane with an even env count (lgx_env.hip launch_step)
+    actnet = bool(getattr(env.cfg.control, "use_actuator_network", False))
+    epw = 2 if (env.num_envs % 2 == 0 and not actnet and not terrain) else 1
+    kname = f"lgx::env_step_kernel<true, {'true' if terrain else 'false'}, {'true' if actnet else 'false'}, {epw}>"
+    out = {
+        "env_kernel": {"avg_us": round(kern_avg_ms * 1e3, 2), "min_us": round(kern_ms[0] * 1e3, 2),
+                       "env_steps_per_s": round(env.num_envs / (kern_avg_ms * 1e-3), 1)},
+        "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 1),
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "bytes_per_env_step": bpe, "bytes_per_launch": launch_bytes,
+                     "traffic": None if traffic is None else round(traffic), "traffic_source": traffic_src,
+                     "note": "the kernel's algorithmic bytes vs HBM peak, as north_star asks; it is bound by "
+                             "per-env latency (LDS round trips, dependent lane exchanges), not HBM (roofline_valu, "
+                             "DESIGN.md 4.1)"},
+    }
+    if args.task == "go2" and args.num_envs == 4096:
+        out["roofline_valu"] = committed_valu(args.num_envs)
+    if args.task == "go2":
+        out["roofline_learner"] = learner_gemm_roofline(dev)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline()
+    return out
 
 
 if __name__ == "__main__":

@@ -37,7 +37,7 @@ def test_bench_two_ranks_gloo_line():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--no_cpu_baseline", "--kernel_iters", "5"]
+           "--steps", "2", "--warmup", "1", "--full", "--no_cpu_baseline", "--kernel_iters", "5"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -45,6 +45,7 @@ def test_bench_two_ranks_gloo_line():
     d = json.loads(lines[0])
     print({k: d[k] for k in ("value", "ms_per_step", "n_gpus")}, d["paths"])
     assert d["n_gpus"] == 2 and d["config"]["global_envs"] == 8192
+    assert len(d["windows"]) == 3 and d["env_kernel"]["avg_us"] > 0 and "cpu_baseline" not in d
     assert d["value"] > 0 and d["value"] == d["value"] and d["value"] != float("inf")
     assert d["paths"]["graph_mode"] == "phased"
     assert d["paths"]["dagger"] == "fused" and d["paths"]["dagger_graph_mode"] == "phased"

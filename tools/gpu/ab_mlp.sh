@@ -14,7 +14,7 @@ if [ -z "$NOTEST" ]; then
 fi
 for r in 1 2; do
   for v in product "$@"; do
-    env $(env_of $v) LGX_MLP_LIB=$(lib_of $v) timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no_cpu_baseline > $O/b_${v//[:=]/_}_$r.log 2>&1 || { tail -5 $O/b_${v//[:=]/_}_$r.log; exit 1; }
+    env $(env_of $v) LGX_MLP_LIB=$(lib_of $v) timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no_cpu_baseline > $O/b_${v//[:=]/_}_$r.log 2>&1 || { tail -5 $O/b_${v//[:=]/_}_$r.log; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/b_${v//[:=]/_}_$r.log').read().strip().splitlines()[-1]); print('$v', round(d['value']), d['ms_per_step'], d['collection_s'], d['learn_s'])"
   done
 done

@@ -3,7 +3,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; T=$1; shift
 O=$R/gpurun_out/prof_$T; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-env "$@" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o run -- python3 $R/bench.py --no_cpu_baseline --steps 4 --warmup 1 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+env "$@" timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o run -- python3 $R/bench.py --full --no_cpu_baseline --steps 4 --warmup 1 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 f=$(find $O -name "*kernel_stats.csv" | head -1); cp $f $O/kernel_stats.csv
 python3 - $O/kernel_stats.csv <<'PY'
 import csv,sys

@@ -13,9 +13,9 @@ bash tools/gpu/prof_kernels.sh r05 > $O/prof_head.txt 2>&1 || { tail -5 $O/prof_
 cp gpurun_out/prof_r05/kernel_stats.csv $O/bench_kernel_stats.csv && tail -1 gpurun_out/prof_r05/bench.json > $O/bench_profiled_line.json
 head -24 $O/prof_head.txt
 cd $R
-timeout -k 10 600 python bench.py --task go2_parkour --num_envs 8192 --no_cpu_baseline > $O/bench_c4.log 2>&1 || exit $?
+timeout -k 10 600 python bench.py --full --task go2_parkour --num_envs 8192 --no_cpu_baseline > $O/bench_c4.log 2>&1 || exit $?
 tail -1 $O/bench_c4.log > $O/bench_c4_line.json
-timeout -k 10 600 python bench.py --task anymal_c_rough --no_cpu_baseline > $O/bench_c3.log 2>&1 || exit $?
+timeout -k 10 600 python bench.py --full --task anymal_c_rough --no_cpu_baseline > $O/bench_c3.log 2>&1 || exit $?
 tail -1 $O/bench_c3.log > $O/bench_c3_line.json
 for f in bench_c4_line bench_c3_line bench_profiled_line; do python -c "import json; b=json.load(open('$O/$f.json')); print('$f', b['value'], b.get('ms_per_step'), b.get('env_kernel'))"; done
 timeout -k 10 300 python tools/dagger_timing.py > $O/dagger_timing.txt 2>&1 || exit $?

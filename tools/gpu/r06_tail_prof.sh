@@ -3,7 +3,7 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${TAG:-r06_tailp}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
-  LGX_TAIL_S8=$v timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p$v -o run -- python3 $R/bench.py --no_cpu_baseline --steps 3 --warmup 1 > $O/b$v.json 2> $O/b$v.err || { tail -5 $O/b$v.err; exit 1; }
+  LGX_TAIL_S8=$v timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/p$v -o run -- python3 $R/bench.py --full --no_cpu_baseline --steps 3 --warmup 1 > $O/b$v.json 2> $O/b$v.err || { tail -5 $O/b$v.err; exit 1; }
   f=$(find $O/p$v -name "*kernel_stats.csv" | head -1)
   python3 - $f $v <<'PY'
 import csv,sys

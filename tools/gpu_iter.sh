@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 timeout -k 10 400 python -u -m pytest -x -q --timeout 120 --timeout-method thread ${TESTS:-tests/test_gpu_mlp.py tests/test_gpu_learner.py} > $O/t1.log 2>&1
 rc=$?; echo pytest rc=$rc; tail -3 $O/t1.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no_cpu_baseline > $O/bench.log 2>&1
+timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no_cpu_baseline > $O/bench.log 2>&1
 rc=$?; echo bench rc=$rc; tail -1 $O/bench.log; [ $rc -eq 0 ] || exit $rc
 [ -n "$NOPROF" ] && exit 0
 rm -rf $O/prof_iter2; mkdir -p $O/prof_iter2
