@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 6
+#define LGX_ABI_VERSION 7
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -45,6 +45,8 @@ extern "C" {
 #define LGX_MAX_CONTACTS 16       /* active contact points solved per substep */
 #define LGX_MAX_PENALISED 24
 #define LGX_MAX_TERMINATION 8
+#define LGX_EVAL_METRICS 8        /* per-env record columns (lgx_eval_buffers.acc) */
+#define LGX_EVAL_CELL_COLS 12     /* per-cell output columns (lgx_eval_buffers.cells) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -362,6 +364,49 @@ int lgx_command_curriculum(lgx_env* env, uint64_t seed, uint64_t step_counter, c
  * default: 2 on the plane, 1 on heightfield / trimesh terrain (faster there) and with the actuator
  * net (a dev build, -DLGX_DEV_KNOBS, also reads LGX_ENVS_PER_WAVE=1). */
 int lgx_set_envs_per_wave(lgx_env* env, int32_t envs_per_wave);
+
+/* ABI 7. Policy evaluation: a per-env record of each env's FIRST episode since lgx_eval_begin,
+ * then reduced per terrain cell. Every env is weighted once, so short (falling) episodes are
+ * not over-counted as they are in extras['episode']. The reference has no counterpart.
+ * Buffers are the caller's, in the env's memory space (device, or host for device < 0). */
+typedef struct lgx_eval_buffers {
+  float* acc;        /* [N, 8] per-env record, columns below */
+  uint8_t* status;   /* [N] 0 running, 1 timed out, 2 fell (reset without time-out), 3 blew up */
+  double* cells;     /* [cell_rows*cell_cols, 12], written by lgx_eval_reduce */
+  uint32_t* overflow;/* [1] written by lgx_eval_reduce: envs whose terrain level / type lies outside
+                        the cell grid (0: cells are valid; else cells were left untouched) */
+  int32_t cell_rows, cell_cols; /* terrain levels x terrain types; 1 x 1 when none are bound */
+} lgx_eval_buffers;
+int64_t lgx_sizeof_eval_buffers(void);
+/* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph.
+ * They need commands, base_lin_vel, base_ang_vel, torques, dof_state, contact_forces, reset and
+ * time_out bound; blew_up, terrain_levels and terrain_types are optional.
+ * lgx_eval_begin: zero acc, status and overflow. */
+int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
+/* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
+ * status[e] == 0:
+ *   reset[e]: status[e] = 3 if blew_up is bound and set, else 1 if time_out[e], else 2; no sample
+ *             (the step has already reset dof_state and resampled commands of that env).
+ *   else one sample, dt = params.dt, v = base_lin_vel[e], w = base_ang_vel[e], c = commands[e]
+ *             (commands after the step with the step's velocities: the pairing of the reference's
+ *             tracking rewards):
+ *     acc[0] += 1                                  samples (episode steps)
+ *     acc[1] += (c0-v0)^2 + (c1-v1)^2              linear velocity tracking error
+ *     acc[2] += (c2-w2)^2                          yaw rate tracking error
+ *     acc[3] += v0*dt                              signed forward progress
+ *     acc[4] += sqrt(v0^2+v1^2)*dt                 path length
+ *     acc[5] += dt * sum_j |torques[e,j] * dof_state[e,j,1]|   mechanical energy
+ *     acc[6] += sum_j torques[e,j]^2
+ *     acc[7]  = max(acc[7], max_f |contact_forces[e, feet_idx[f], :]|)   peak foot force
+ * Envs with status != 0 are not touched: a finished env's later episodes change nothing. */
+int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
+/* cells[terrain_levels[e] * cell_cols + terrain_types[e]] (cell 0 for an unbound one) =
+ * {n_envs, n_timeout, n_fall, n_blowup, fp64 sums of acc[0..7] over the cell's finished envs
+ * (status != 0)}. Deterministic: fixed env order per lane and a fixed combination tree, no
+ * floating-point atomics; two calls on the same records give bit-identical cells. A level or type
+ * outside the grid is never used as an index: such envs are counted in *overflow, and cells are
+ * then left unwritten (the host backend fails the call instead). */
+int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
 const char* lgx_last_error(const lgx_env* env);
 void lgx_destroy(lgx_env* env);
 

@@ -5,7 +5,7 @@ sizeof against the values the native library (and the oracle) report.
 """
 import ctypes as C
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -17,6 +17,8 @@ MAX_CANDIDATES = 64
 MAX_CONTACTS = 16
 MAX_PENALISED = 24
 MAX_TERMINATION = 8
+EVAL_METRICS = 8     # per-env record columns (lgx_eval_buffers.acc)
+EVAL_CELL_COLS = 12  # per-cell output columns (lgx_eval_buffers.cells)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -136,9 +138,14 @@ class Buffers(C.Structure):
 BUFFER_FIELDS = [f[0] for f in Buffers._fields_]
 
 
+class EvalBuffers(C.Structure):
+    """lgx_eval_buffers (ABI 7): the policy evaluation's records and cells."""
+    _fields_ = [("acc", P), ("status", P), ("cells", P), ("overflow", P), ("cell_rows", i32), ("cell_cols", i32)]
+
+
 def check_layout(lib, prefix):
     """Compare ctypes sizes with the native library's sizeof() exports."""
-    for name, cls in (("model", Model), ("params", TaskParams), ("buffers", Buffers)):
+    for name, cls in (("model", Model), ("params", TaskParams), ("buffers", Buffers), ("eval_buffers", EvalBuffers)):
         fn = getattr(lib, f"{prefix}{name}", None)
         if fn is None:
             continue

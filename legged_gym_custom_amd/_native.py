@@ -35,6 +35,8 @@ def lib():
     L.lgx_episode_extras.argtypes = [vp, vp, vp, vp, vp, vp]
     L.lgx_command_curriculum.argtypes = [vp, u64, u64, vp, vp, vp]
     L.lgx_set_envs_per_wave.argtypes = [vp, i32]
+    for fn in (L.lgx_eval_begin, L.lgx_eval_accumulate, L.lgx_eval_reduce):
+        fn.argtypes = [vp, vp, vp]
     L.lgx_last_error.argtypes = [vp]
     L.lgx_last_error.restype = C.c_char_p
     L.lgx_destroy.argtypes = [vp]
@@ -48,7 +50,8 @@ def lib():
 
 EXPORTED = ["lgx_abi_version", "lgx_sizeof_model", "lgx_sizeof_task_params", "lgx_sizeof_buffers", "lgx_create",
             "lgx_bind", "lgx_step", "lgx_step_dev", "lgx_post_physics", "lgx_physics", "lgx_reset_envs", "lgx_last_error",
-            "lgx_destroy", "lgx_episode_extras", "lgx_command_curriculum", "lgx_set_envs_per_wave"]
+            "lgx_destroy", "lgx_episode_extras", "lgx_command_curriculum", "lgx_set_envs_per_wave", "lgx_eval_begin",
+            "lgx_eval_accumulate", "lgx_eval_reduce"]
 
 
 class NativeEnv:
@@ -122,6 +125,38 @@ class NativeEnv:
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         self._check(self._L.lgx_episode_extras(self.handle, p(means), p(level_mean), p(time_outs), p(step_dev),
                                                C.c_void_p(stream)), "lgx_episode_extras")
+
+    def eval_buffers(self, acc, status, cells, overflow):
+        """lgx_eval_buffers over the given tensors: acc [N, 8] fp32, status [N] uint8, cells
+        [rows, cols, 12] float64, overflow [1] int32, all in the env's memory space."""
+        n = self.params.num_envs
+        want = {"acc": ((n, _abi.EVAL_METRICS), "float32"), "status": ((n,), "uint8"),
+                "cells": (None, "float64"), "overflow": ((1,), "int32")}
+        ev = _abi.EvalBuffers()
+        for name, t in (("acc", acc), ("status", status), ("cells", cells), ("overflow", overflow)):
+            shape, dtype = want[name]
+            if name == "cells" and (t.dim() != 3 or t.shape[2] != _abi.EVAL_CELL_COLS):
+                raise LgxError(f"eval buffer cells must be [rows, cols, {_abi.EVAL_CELL_COLS}]")
+            if (shape is not None and tuple(t.shape) != shape) or str(t.dtype) != "torch." + dtype \
+                    or not t.is_contiguous() or t.device.type != self._dev_type:
+                raise LgxError(f"eval buffer {name} must be a contiguous {dtype} tensor"
+                               f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
+            setattr(ev, name, t.data_ptr())
+        ev.cell_rows, ev.cell_cols = int(cells.shape[0]), int(cells.shape[1])
+        ev._keep = (acc, status, cells, overflow)
+        return ev
+
+    def eval_begin(self, ev, stream):
+        """lgx_eval_begin: zero the records (ev: eval_buffers(...))."""
+        self._check(self._L.lgx_eval_begin(self.handle, C.byref(ev), C.c_void_p(stream)), "lgx_eval_begin")
+
+    def eval_accumulate(self, ev, stream):
+        """lgx_eval_accumulate: one sample per running env from the step just run."""
+        self._check(self._L.lgx_eval_accumulate(self.handle, C.byref(ev), C.c_void_p(stream)), "lgx_eval_accumulate")
+
+    def eval_reduce(self, ev, stream):
+        """lgx_eval_reduce: records -> cells (and the out-of-grid count in ev.overflow)."""
+        self._check(self._L.lgx_eval_reduce(self.handle, C.byref(ev), C.c_void_p(stream)), "lgx_eval_reduce")
 
     def __del__(self):
         try:

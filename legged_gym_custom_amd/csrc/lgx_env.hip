@@ -2724,6 +2724,207 @@ int lgx_command_curriculum(lgx_env* env, uint64_t seed, uint64_t step_counter, c
   return 0;
 }
 
+// ------------------------------------------------------------------ policy evaluation (ABI 7)
+namespace lgx {
+struct EvalArgs {
+  const float* commands;
+  const float* lin_vel;
+  const float* ang_vel;
+  const float* torques;
+  const float* dof_state;
+  const float* contact;
+  const uint8_t* reset;
+  const uint8_t* time_out;
+  const uint8_t* blew_up;  // optional
+  float* acc;
+  uint8_t* status;
+  int N, D, NB, nfeet;
+  int feet[LGX_MAX_FEET];
+  float dt;
+};
+
+// lgx_eval_accumulate: four lanes per env (16 envs per wave). Lane q of an env reads a quarter of
+// the joints (consecutive lanes read consecutive addresses: 48 B of torques and 96 B of dof_state
+// per env, whole lines per wave) and foot q; two xor shuffles combine the quarters; lane q then
+// updates record columns 2q and 2q+1 (a wave writes 512 contiguous bytes). About 60 floats per
+// env: the kernel is launch-bound. No LDS, no atomics; finished envs are read-only.
+__global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 2, q = t & 3;
+  // no early return: the shuffles below need every lane of a group; tail lanes load nothing
+  const bool live = e < A.N;
+  const int st = live ? A.status[e] : 1;
+  const int rs = live ? A.reset[e] : 0;
+  const bool sample = st == 0 && !rs;
+  float en = 0.f, t2 = 0.f, fmax_ = 0.f;
+  if (sample) {
+    const int per = (A.D + 3) >> 2, j0 = q * per, j1 = min(A.D, j0 + per);
+    const float* tq = A.torques + (size_t)e * A.D;
+    const float* ds = A.dof_state + (size_t)e * A.D * 2;
+    for (int j = j0; j < j1; ++j) {
+      const float tau = tq[j], qd = ds[2 * j + 1];
+      en += fabsf(tau * qd);
+      t2 += tau * tau;
+    }
+    if (q < A.nfeet) {
+      const float* c = A.contact + ((size_t)e * A.NB + A.feet[q]) * 3;
+      fmax_ = sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    }
+  }
+  for (int o = 1; o <= 2; o <<= 1) {
+    en += __shfl_xor(en, o, 64);
+    t2 += __shfl_xor(t2, o, 64);
+    fmax_ = fmaxf(fmax_, __shfl_xor(fmax_, o, 64));
+  }
+  if (!live || st != 0) return;
+  if (rs) {
+    if (q == 0) A.status[e] = (A.blew_up && A.blew_up[e]) ? 3 : (A.time_out[e] ? 1 : 2);
+    return;
+  }
+  const float v0 = A.lin_vel[e * 3], v1 = A.lin_vel[e * 3 + 1], w2 = A.ang_vel[e * 3 + 2];
+  const float c0 = A.commands[e * 4], c1 = A.commands[e * 4 + 1], c2 = A.commands[e * 4 + 2];
+  float* a = A.acc + (size_t)e * LGX_EVAL_METRICS + 2 * q;
+  float x0 = a[0], x1 = a[1];
+  if (q == 0) {
+    x0 += 1.0f;
+    x1 += (c0 - v0) * (c0 - v0) + (c1 - v1) * (c1 - v1);
+  } else if (q == 1) {
+    x0 += (c2 - w2) * (c2 - w2);
+    x1 += v0 * A.dt;
+  } else if (q == 2) {
+    x0 += sqrtf(v0 * v0 + v1 * v1) * A.dt;
+    x1 += A.dt * en;
+  } else {
+    x0 += t2;
+    x1 = fmaxf(x1, fmax_);
+  }
+  a[0] = x0;
+  a[1] = x1;
+}
+
+// lgx_eval_reduce: one block of 256 threads per cell. Thread t scans envs t, t+256, ... in
+// increasing order (the loads coalesce) and keeps fp64 partial sums of its cell's finished envs;
+// the partials are combined by a fixed tree (shuffle-down inside each wave, then the four
+// wave results in wave order by thread 0), so the result depends only on the records. Every block
+// scans every env's level / type and so knows the number of out-of-grid envs: no block writes
+// its cell when there are any, and block 0 publishes the count.
+__global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restrict__ acc,
+                                                          const uint8_t* __restrict__ status,
+                                                          const int64_t* __restrict__ levels,
+                                                          const int64_t* __restrict__ types, int N, int rows,
+                                                          int cols, double* __restrict__ cells,
+                                                          uint32_t* __restrict__ overflow) {
+  constexpr int NC = LGX_EVAL_CELL_COLS;
+  __shared__ double part[4][NC];
+  __shared__ uint32_t bad_s[4];
+  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double s[NC];
+  for (int k = 0; k < NC; ++k) s[k] = 0.0;
+  uint32_t bad = 0;
+  for (int e = tid; e < N; e += 256) {
+    const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
+    if (lv < 0 || lv >= rows || ty < 0 || ty >= cols) { ++bad; continue; }
+    if ((int)(lv * cols + ty) != cell) continue;
+    const int st = status[e];
+    s[0] += 1.0;
+    if (st == 0) continue;
+    s[1] += st == 1 ? 1.0 : 0.0;  // time-out
+    s[2] += st == 2 ? 1.0 : 0.0;  // fall
+    s[3] += st == 3 ? 1.0 : 0.0;  // blow-up
+    const float* a = acc + (size_t)e * LGX_EVAL_METRICS;
+    for (int k = 0; k < LGX_EVAL_METRICS; ++k) s[4 + k] += (double)a[k];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int k = 0; k < NC; ++k) s[k] += __shfl_down(s[k], o, 64);
+    bad += __shfl_down(bad, o, 64);
+  }
+  if (lane == 0) {
+    for (int k = 0; k < NC; ++k) part[wv][k] = s[k];
+    bad_s[wv] = bad;
+  }
+  __syncthreads();
+  const uint32_t nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
+  if (tid == 0 && cell == 0 && overflow) *overflow = nbad;
+  if (nbad == 0 && tid < NC) cells[(size_t)cell * NC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
+}  // namespace lgx
+
+// shared checks of the three lgx_eval_* calls
+static int eval_check(lgx_env* env, const lgx_eval_buffers* ev, const char* what, bool reduce) {
+  if (!env) return -2;
+  const std::string w(what);
+  if (!env->bound) return fail(env, w + " before lgx_bind");
+  if (!ev) return fail(env, w + ": eval buffers are NULL");
+  const lgx_buffers& b = env->buffers;
+  static const char* names[] = {"commands", "base_lin_vel", "base_ang_vel", "torques", "dof_state",
+                                "contact_forces", "reset", "time_out"};
+  const void* ptrs[] = {b.commands, b.base_lin_vel, b.base_ang_vel, b.torques, b.dof_state,
+                        b.contact_forces, b.reset, b.time_out};
+  for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
+    if (!ptrs[i]) return fail(env, w + ": required buffer not bound: " + names[i]);
+  if (!ev->acc || !ev->status) return fail(env, w + ": acc and status are required");
+  if (ev->cell_rows < 1 || ev->cell_cols < 1 || (int64_t)ev->cell_rows * ev->cell_cols > (1 << 20))
+    return fail(env, w + ": cell_rows * cell_cols must be >= 1 (and at most 2^20)");
+  if (reduce && (!ev->cells || !ev->overflow)) return fail(env, w + ": cells and overflow are required");
+  for (int f = 0; f < env->params.num_feet; ++f)
+    if (env->params.feet_idx[f] < 0 || env->params.feet_idx[f] >= env->params.num_bodies)
+      return fail(env, w + ": feet_idx outside the bodies");
+  return 0;
+}
+
+int64_t lgx_sizeof_eval_buffers(void) { return (int64_t)sizeof(lgx_eval_buffers); }
+
+int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) {
+  if (int rc = eval_check(env, ev, "lgx_eval_begin", false)) return rc;
+  const size_t N = (size_t)env->params.num_envs;
+  if (env->host) {
+    lgxh::eval_begin(&env->params, ev);
+    return 0;
+  }
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_OK(hipMemsetAsync(ev->acc, 0, sizeof(float) * LGX_EVAL_METRICS * N, st));
+  HIP_OK(hipMemsetAsync(ev->status, 0, N, st));
+  if (ev->overflow) HIP_OK(hipMemsetAsync(ev->overflow, 0, sizeof(uint32_t), st));
+  return 0;
+}
+
+int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) {
+  if (int rc = eval_check(env, ev, "lgx_eval_accumulate", false)) return rc;
+  if (env->host) {
+    lgxh::eval_accumulate(&env->params, &env->buffers, ev);
+    return 0;
+  }
+  const lgx_buffers& b = env->buffers;
+  const lgx_task_params& p = env->params;
+  lgx::EvalArgs A;
+  A.commands = b.commands; A.lin_vel = b.base_lin_vel; A.ang_vel = b.base_ang_vel; A.torques = b.torques;
+  A.dof_state = b.dof_state; A.contact = b.contact_forces; A.reset = b.reset; A.time_out = b.time_out;
+  A.blew_up = b.blew_up; A.acc = ev->acc; A.status = ev->status;
+  A.N = p.num_envs; A.D = p.num_dof; A.NB = p.num_bodies; A.nfeet = p.num_feet; A.dt = p.dt;
+  for (int f = 0; f < LGX_MAX_FEET; ++f) A.feet[f] = f < p.num_feet ? p.feet_idx[f] : 0;
+  const int64_t threads = (int64_t)p.num_envs * 4;
+  hipLaunchKernelGGL(lgx::eval_accumulate_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, A);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) {
+  if (int rc = eval_check(env, ev, "lgx_eval_reduce", true)) return rc;
+  if (env->host) {
+    const int bad = lgxh::eval_reduce(&env->params, &env->buffers, ev);
+    if (bad) return fail(env, "lgx_eval_reduce: " + std::to_string(bad) + " envs have a terrain level / type outside the "
+                              "cell grid (cells not written)");
+    return 0;
+  }
+  const lgx_buffers& b = env->buffers;
+  hipLaunchKernelGGL(lgx::eval_reduce_kernel, dim3((unsigned)(ev->cell_rows * ev->cell_cols)), dim3(256), 0,
+                     (hipStream_t)hip_stream, ev->acc, ev->status, b.terrain_levels, b.terrain_types,
+                     env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cells, ev->overflow);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 #ifdef LGX_PHASE_CLOCK
 // dev builds only: per-env phase cycle counters ([num_envs][16] uint32, device memory)
 int lgx_debug_phase_buffer(uint32_t* dev_ptr) {

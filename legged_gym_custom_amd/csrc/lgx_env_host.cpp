@@ -1415,6 +1415,75 @@ void command_curriculum(const lgx_task_params* P, const lgx_buffers* B, uint64_t
   }
 }
 
+void eval_begin(const lgx_task_params* P, const lgx_eval_buffers* E) {
+  const size_t N = (size_t)P->num_envs;
+  memset(E->acc, 0, sizeof(float) * LGX_EVAL_METRICS * N);
+  memset(E->status, 0, N);
+  if (E->overflow) *E->overflow = 0;
+}
+
+// lgx_eval_accumulate (include/lgx.h): the kernel's arithmetic (lgx_env.hip
+// eval_accumulate_kernel), the joint sums in joint order
+void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E) {
+  const int N = P->num_envs, D = P->num_dof, NB = P->num_bodies;
+  const float dt = P->dt;
+#pragma omp parallel for schedule(static)
+  for (int e = 0; e < N; ++e) {
+    if (E->status[e] != 0) continue;
+    if (B->reset[e]) {
+      E->status[e] = (B->blew_up && B->blew_up[e]) ? 3 : (B->time_out[e] ? 1 : 2);
+      continue;
+    }
+    const float* v = B->base_lin_vel + (size_t)e * 3;
+    const float* w = B->base_ang_vel + (size_t)e * 3;
+    const float* c = B->commands + (size_t)e * 4;
+    const float* tq = B->torques + (size_t)e * D;
+    const float* ds = B->dof_state + (size_t)e * D * 2;
+    float en = 0.f, t2 = 0.f, fm = 0.f;
+    for (int j = 0; j < D; ++j) {
+      en += fabsf(tq[j] * ds[2 * j + 1]);
+      t2 += tq[j] * tq[j];
+    }
+    for (int f = 0; f < P->num_feet; ++f) {
+      const float* cf = B->contact_forces + ((size_t)e * NB + P->feet_idx[f]) * 3;
+      fm = std::max(fm, sqrtf(cf[0] * cf[0] + cf[1] * cf[1] + cf[2] * cf[2]));
+    }
+    float* a = E->acc + (size_t)e * LGX_EVAL_METRICS;
+    a[0] += 1.0f;
+    a[1] += (c[0] - v[0]) * (c[0] - v[0]) + (c[1] - v[1]) * (c[1] - v[1]);
+    a[2] += (c[2] - w[2]) * (c[2] - w[2]);
+    a[3] += v[0] * dt;
+    a[4] += sqrtf(v[0] * v[0] + v[1] * v[1]) * dt;
+    a[5] += dt * en;
+    a[6] += t2;
+    a[7] = std::max(a[7], fm);
+  }
+}
+
+int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E) {
+  const int N = P->num_envs, rows = E->cell_rows, cols = E->cell_cols;
+  auto cell_of = [&](int e) -> int64_t {
+    const int64_t lv = B->terrain_levels ? B->terrain_levels[e] : 0, ty = B->terrain_types ? B->terrain_types[e] : 0;
+    return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : lv * cols + ty;
+  };
+  int bad = 0;
+  for (int e = 0; e < N; ++e) bad += cell_of(e) < 0;
+  *E->overflow = (uint32_t)bad;
+  if (bad) return bad;
+  const size_t nc = (size_t)rows * cols * LGX_EVAL_CELL_COLS;
+  for (size_t i = 0; i < nc; ++i) E->cells[i] = 0.0;
+  for (int e = 0; e < N; ++e) {  // env order: deterministic
+    double* cl = E->cells + (size_t)cell_of(e) * LGX_EVAL_CELL_COLS;
+    const int st = E->status[e];
+    cl[0] += 1.0;
+    if (st == 0) continue;
+    if (st >= 1 && st <= 3) cl[st] += 1.0;
+    const float* a = E->acc + (size_t)e * LGX_EVAL_METRICS;
+    for (int k = 0; k < LGX_EVAL_METRICS; ++k) cl[4 + k] += (double)a[k];
+  }
+  return 0;
+}
+
 int threads() { return omp_get_max_threads(); }
 
 }  // namespace lgxh

@@ -129,6 +129,45 @@ class LeggedRobot(BaseTask):
             self._extras_time_outs.copy_(torch.where(self.reset_buf.any(), self.time_out_buf, self._extras_time_outs))
         self._publish_extras()
 
+    # ------------------------------------------------------------------ policy evaluation
+    def _eval_buffers(self):
+        """The evaluation's tensors (include/lgx.h lgx_eval_buffers), allocated once so a captured
+        loop replays on fixed addresses: eval_acc [N, 8] and eval_status [N] (each env's first
+        episode since eval_begin), the cells [terrain rows, terrain cols, 12] (1 x 1 without a
+        terrain grid) and the out-of-grid counter."""
+        if getattr(self, "_eval", None) is None:
+            grid = getattr(self, "terrain_levels", None) is not None
+            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
+            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
+            self.eval_acc = z(self.num_envs, _abi.EVAL_METRICS, dtype=torch.float32)
+            self.eval_status = z(self.num_envs, dtype=torch.uint8)
+            self._eval_cells = z(rows, cols, _abi.EVAL_CELL_COLS, dtype=torch.float64)
+            self._eval_overflow = z(1, dtype=torch.int32)
+            self._eval = self._native.eval_buffers(self.eval_acc, self.eval_status, self._eval_cells,
+                                                   self._eval_overflow)
+        return self._eval
+
+    def eval_begin(self):
+        """lgx_eval_begin: start recording every env's next (first) episode."""
+        self._native.eval_begin(self._eval_buffers(), self._stream())
+
+    def eval_accumulate(self):
+        """lgx_eval_accumulate for the step just run (call after every step(); stream-ordered,
+        no host sync, capturable)."""
+        self._native.eval_accumulate(self._eval_buffers(), self._stream())
+
+    def eval_cells(self):
+        """lgx_eval_reduce, then the cells [rows, cols, 12] float64 on the host: n_envs, n_timeout,
+        n_fall, n_blowup and the sums of the 8 record columns over each cell's finished envs.
+        Synchronises. An env whose terrain level / type lies outside the grid is an error."""
+        ev = self._eval_buffers()
+        self._native.eval_reduce(ev, self._stream())
+        bad = int(self._eval_overflow.item())
+        if bad:
+            raise _native.LgxError(f"lgx_eval_reduce: {bad} envs have a terrain level / type outside the "
+                                   f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
+        return self._eval_cells.cpu().clone()
+
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""
         return torch.cuda.current_stream(self.device).cuda_stream if self.sim_device_id >= 0 else 0

@@ -1,0 +1,179 @@
+"""PolicyEvaluator — batched policy evaluation on the device, with per-terrain metrics.
+
+What share of the robots survive a full episode on each terrain level x type, how well do they
+track the command and at what cost of transport: every env runs ONE episode (its first since
+the start; later episodes of an env that fell are ignored, so falls are not over-counted as
+they are in extras['episode']), the per-env records are kept by lgx_eval_accumulate after each
+env step and folded per terrain cell by lgx_eval_reduce (include/lgx.h, ABI 7). The reference
+has no counterpart (its play.py drives one robot and plots a few joint traces).
+
+Policies:
+  "student"  what a robot runs (deploy_base.py:244-250 with the exported modules):
+             actor([obs | adaptation_encoder(history) | scan_encoder(scan) | estimator(obs)]),
+             the mean action, no noise. The actor is fed the ESTIMATOR's output, not the env's
+             true estimated observation (which play.py feeds).
+  "teacher"  the same with the privileged encoder's latent.
+
+On the GPU, when S8Act covers the networks (Go2), the act is its one-launch kernel writing the
+mean straight into env.actions_in (the weights are packed once, at construction and by
+refresh_weights()), and the loop body {act, env.step, eval_accumulate} is captured once as a
+hipGraph and replayed. Otherwise (CPU, ANYmal) the torch modules run eagerly.
+
+Single process only: sharded evaluation (env shards over ranks) is out of scope.
+"""
+import math
+import time
+
+import torch
+
+from legged_gym_custom_amd import _abi
+
+REPORT_KEYS = ("episodes", "running", "survival_rate", "fall_rate", "blowups", "mean_episode_s", "rms_lin_vel_err",
+               "rms_yaw_err", "mean_forward_speed", "cost_of_transport", "mean_peak_foot_force")
+
+
+def cell_report(cell, dt, weight):
+    """The report entries of one cell row [12] (n_envs, n_timeout, n_fall, n_blowup, sums of the
+    8 record columns); weight = m * g of the cost of transport. Ratios without data are None."""
+    n, n_to, n_fall, n_blow = (int(round(float(v))) for v in cell[:4])
+    s = [float(v) for v in cell[4:]]
+    ep = n_to + n_fall + n_blow
+    div = lambda a, b: a / b if b > 0 else None  # noqa: E731
+    rms = lambda a: math.sqrt(a / s[0]) if s[0] > 0 else None  # noqa: E731
+    return {"episodes": ep, "running": n - ep, "survival_rate": div(n_to, ep), "fall_rate": div(n_fall, ep),
+            "blowups": n_blow, "mean_episode_s": div(s[0] * dt, ep), "rms_lin_vel_err": rms(s[1]),
+            "rms_yaw_err": rms(s[2]), "mean_forward_speed": div(s[3], s[0] * dt),
+            "cost_of_transport": div(s[5], weight * s[4]), "mean_peak_foot_force": div(s[7], ep)}
+
+
+class PolicyEvaluator:
+    def __init__(self, env, runner, policy="student"):
+        if policy not in ("student", "teacher"):
+            raise ValueError(f"policy must be 'student' or 'teacher' (got {policy!r})")
+        if getattr(env, "num_envs_total", env.num_envs) != env.num_envs:
+            raise RuntimeError("PolicyEvaluator is single-process: the env is sharded over ranks")
+        self.env, self.runner, self.alg = env, runner, runner.alg
+        self.policy = policy
+        self.adaptation_mode = policy == "student"
+        self.device = str(runner.device)
+        if torch.device(self.device) != torch.device(env.device):
+            raise RuntimeError(f"the evaluator runs the policy on the env's device ({env.device}), not {self.device}")
+        self.on_gpu = self.device.startswith("cuda")
+        self._graph = None
+        self._fused = None
+        self.last_cells = None
+        if self.on_gpu:
+            from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
+            if S8Act.supported(self.alg):
+                f = S8Act(self.alg, env.num_envs)
+                dst = env.actions_in
+                if dst.shape == f.mu.shape and dst.is_contiguous() and dst.dtype == torch.float32:
+                    # the kernel writes the mean into the env's action input: env.step copies nothing
+                    f.mu = dst
+                    f.args.mu, f.args.ld_mu = dst.data_ptr(), dst.stride(0)
+                self._fused = f
+                self.refresh_weights()
+        # m * g of the cost of transport: the model's nominal total mass (the per-env added base
+        # mass of the mass randomisation is ignored)
+        self.mass = float(sum(l["mass"] for l in env.model_dict["links"]))
+        self.gravity = abs(float(env.sim_params.gravity[2]))
+
+    def refresh_weights(self):
+        """Re-pack the fused act kernel's weights (after the runner loaded or trained them)."""
+        if self._fused is not None:
+            self._fused.refresh_weights()
+            self._graph = None
+
+    # ------------------------------------------------------------------ one iteration
+    def act(self):
+        """The policy's mean action on the env's current observations."""
+        env, ac = self.env, self.alg.actor_critic
+        obs, priv, scan = env.obs_buf, env.privileged_obs_buf, env.scan_obs_buf
+        if self._fused is not None:
+            mu, _ = self._fused.run(obs, priv, env.critic_obs_buf, scan, rows=None, head=None,
+                                    adaptation_mode=self.adaptation_mode)
+            return mu
+        return ac.act_inference(obs, priv, self.alg.estimator(obs), scan, adaptation_mode=self.adaptation_mode)
+
+    def step(self):
+        """One eager iteration: act, env.step, eval_accumulate."""
+        with torch.no_grad():
+            self.env.step(self.act())
+            self.env.eval_accumulate()
+
+    def begin(self):
+        """Reset every env and start recording. The env's step and reset-call counters (the keys
+        of its random streams) are rewound, so an evaluation depends only on the weights, the
+        seed and the config, and repeats exactly; do not interleave it with training on the same
+        env. reset() ends with the reference's zero-action step (base_task.py:131-135), which
+        yields the first observations; the episode lengths are then set to 0 (no random initial
+        lengths)."""
+        env = self.env
+        env.common_step_counter = 0
+        env._reset_calls = 0
+        with torch.no_grad():
+            env.reset()
+            env.episode_length_buf = torch.zeros_like(env.episode_length_buf)
+            env.eval_begin()
+
+    def _capture(self):
+        """The loop body as one hipGraph (the runner's _capture_rollout is the model): one eager
+        iteration warms every kernel, then the capture records without executing."""
+        env = self.env
+        self.step()
+        torch.cuda.synchronize(self.device)
+        csc = env.common_step_counter
+        g = torch.cuda.CUDAGraph()
+        with torch.inference_mode(False), torch.no_grad(), \
+                torch.cuda.graph(g, capture_error_mode=self.alg.capture_mode()):
+            env.step(self.act())
+            env.eval_accumulate()
+        env.common_step_counter = csc  # host mirror (capture advanced it, the device did not)
+        self._graph = g
+
+    # ------------------------------------------------------------------ run
+    def run(self, num_steps=None, graph=True):
+        """Evaluate: reset, num_steps x {act, step, accumulate}, reduce, one host read; returns the
+        report (JSON-serialisable): per-cell and total entries REPORT_KEYS, None where a cell has
+        no data (never NaN).
+
+        num_steps defaults to max_episode_length + 1: the step kernel's rule is time_out =
+        episode_length > max_episode_length (lgx_env.hip env_step_kernel, go2.py:186-204), the
+        length counting from 0, so by then every env has finished once and `running` is 0.
+        graph: replay the captured loop body where the env allows it (GPU, env.graph_capturable);
+        False forces the eager loop. Both give bit-identical cells."""
+        env = self.env
+        steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
+        use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
+        if use_graph and self._graph is None:
+            self._capture()
+        self.begin()
+        if self.on_gpu:
+            torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        if use_graph:
+            for _ in range(steps):
+                self._graph.replay()
+                env.advance_step_counter(1)
+        else:
+            for _ in range(steps):
+                self.step()
+        cells = env.eval_cells()  # reduce + the host read (synchronises)
+        wall = time.perf_counter() - t0
+        self.last_cells = cells  # [rows, cols, 12] float64, as lgx_eval_reduce wrote them
+        return self.report(cells, steps, wall, use_graph)
+
+    def report(self, cells, steps=None, wall=None, graph=None):
+        env = self.env
+        dt, w = float(env.dt), self.mass * self.gravity
+        rows, cols = int(cells.shape[0]), int(cells.shape[1])
+        assert cells.shape[2] == _abi.EVAL_CELL_COLS
+        total = cells.reshape(-1, _abi.EVAL_CELL_COLS).sum(0)
+        out = {"policy": self.policy, "num_envs": int(env.num_envs), "num_steps": steps, "dt": dt,
+               "nominal_mass": self.mass, "graph": graph, "terrain_levels": rows, "terrain_types": cols,
+               "total": cell_report(total, dt, w),
+               "cells": [[cell_report(cells[r, c], dt, w) for c in range(cols)] for r in range(rows)]}
+        if wall is not None and steps:
+            out["wall_s"] = wall
+            out["env_steps_per_s"] = steps * env.num_envs / wall if wall > 0 else None
+        return out

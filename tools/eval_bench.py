@@ -1,0 +1,86 @@
+"""Policy evaluation throughput (dev tool): PolicyEvaluator on a task with randomly initialised
+networks (the timing does not depend on the weights), graph replay and the eager loop alternated.
+
+  python tools/eval_bench.py [--task go2] [--num_envs 4096] [--steps N] [--repeats 3] [--out FILE]
+  rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/eval_bench.py --profile
+  python tools/eval_bench.py --stats DIR/..._kernel_stats.csv --merge FILE   # kernel times into FILE
+
+Times are host clocks around runs that end in the evaluator's host read (a device synchronise);
+--profile runs one short eager evaluation only (kernel times come from the trace, not from here)."""
+import argparse
+import csv
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+KERNELS = {"eval_accumulate_kernel": "eval_accumulate_us", "eval_reduce_kernel": "eval_reduce_us",
+           "env_step_kernel": "env_step_us", "act_kernel(lgx_s8_act_args": "act_us"}
+
+
+def merge_stats(stats_csv, out):
+    """Average kernel times (us) of the evaluation's kernels from a rocprofv3 --stats CSV."""
+    doc = json.load(open(out)) if os.path.exists(out) else {}
+    k = doc.setdefault("kernel_trace", {"source": "rocprofv3 --kernel-trace --stats, eager evaluation"})
+    for row in csv.DictReader(open(stats_csv)):
+        for pat, key in KERNELS.items():
+            if pat in row["Name"]:
+                k[key] = round(float(row["AverageNs"]) / 1e3, 2)
+                k[key.replace("_us", "_calls")] = int(row["Calls"])
+    json.dump(doc, open(out, "w"), indent=1)
+    print(json.dumps(k))
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--task", default="go2")
+    p.add_argument("--num_envs", type=int, default=4096)
+    p.add_argument("--steps", type=int, default=None)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--device", default="cuda:0", help="cpu: a rehearsal of the tool, not a measurement")
+    p.add_argument("--profile", action="store_true")
+    p.add_argument("--stats")
+    p.add_argument("--merge")
+    p.add_argument("--out")
+    a = p.parse_args()
+    if a.stats:
+        return merge_stats(a.stats, a.merge)
+    import torch
+    from legged_gym_custom_amd.envs import task_registry, task_registry_configs
+    from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator
+    from legged_gym_custom_amd.utils.helpers import get_args
+    assert a.device == "cpu" or torch.cuda.is_available(), "eval_bench needs an MI355X"
+    cfg, tcfg = task_registry_configs(a.task)
+    cfg.seed = tcfg.seed = 1
+    cfg.terrain.curriculum = cfg.commands.curriculum = False
+    args = get_args([f"--task={a.task}", "--headless", f"--num_envs={a.num_envs}", "--seed=1",
+                     f"--sim_device={a.device}", f"--rl_device={a.device}"])
+    env, _ = task_registry.make_env(a.task, args, env_cfg=cfg)
+    runner, _ = task_registry.make_alg_runner(env, args=args, train_cfg=tcfg, log_root=None)
+    ev = PolicyEvaluator(env, runner)
+    if a.profile:
+        r = ev.run(a.steps or 200, graph=False)
+        print(json.dumps({"profiled_steps": r["num_steps"], "total": r["total"]}))
+        return
+    ev.run(20)  # warm both paths (the capture included)
+    ev.run(20, graph=False)
+    rates = {"graph": [], "eager": []}
+    for _ in range(a.repeats):
+        for mode in ("graph", "eager"):
+            r = ev.run(a.steps, graph=mode == "graph")
+            assert a.device == "cpu" or r["graph"] == (mode == "graph")
+            rates[mode].append(r["env_steps_per_s"])
+    doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
+           "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
+                               for m, v in rates.items()},
+           "total": r["total"]}
+    print(json.dumps(doc))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(doc, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
