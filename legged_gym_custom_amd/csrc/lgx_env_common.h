@@ -1,0 +1,526 @@
+// lgx_env_common.h — the env step's scalar code, stated once for both backends of
+// include/lgx.h: the gfx950 kernels (lgx_env.hip) and the host backend (lgx_env_host.cpp).
+// Plain C++17 with no lane index in it: the 3-vector math, the Philox counter RNG, the step's
+// constants and uniform slots, the terrain triangle geometry, the post-physics helpers, command
+// resampling, the reward terms, the scalar head of reset_idx and the command curriculum.
+// Not here, on purpose: the physics and every lane-parallel phase (the kernel spreads an env
+// over a wave's lanes, the host loops), and the oracle under oracle/, which stays an
+// independent statement and never includes this file.
+// Both backends build with -ffp-contract=off, so one body gives each backend the bits its own copy
+// gave; the one exception is marked below ("inside the physics").
+#pragma once
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/lgx.h"
+
+#ifdef __HIPCC__
+#define LGX_HD __host__ __device__ __forceinline__
+#define LGX_UNROLL _Pragma("unroll")
+#else
+#define LGX_HD static inline
+#define LGX_UNROLL
+#endif
+
+// ---------------------------------------------------------------- Philox4x32-10
+// Same definition as oracle/philox.py and oracle/lgx_oracle.c (counter layout:
+// c0 = global env id, c1/c3 = step lo/hi, c2 = block | stream << 16; key = seed).
+LGX_HD uint32_t mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+LGX_HD void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                          uint32_t out[4]) {
+  LGX_UNROLL
+  for (int r = 0; r < 10; ++r) {
+    uint32_t hi0 = mulhi32(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    uint32_t hi1 = mulhi32(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    uint32_t n0 = hi1 ^ c1 ^ k0;
+    uint32_t n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+LGX_HD float u01(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
+
+// ---------------------------------------------------------------- fp32 vector math
+struct f3 {
+  float x, y, z;
+};
+LGX_HD f3 mk(float x, float y, float z) { return f3{x, y, z}; }
+LGX_HD f3 ld3(const float* p) { return f3{p[0], p[1], p[2]}; }
+LGX_HD void st3(float* p, f3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+LGX_HD f3 operator+(f3 a, f3 b) { return f3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+LGX_HD f3 operator-(f3 a, f3 b) { return f3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+LGX_HD f3 operator*(f3 a, float s) { return f3{a.x * s, a.y * s, a.z * s}; }
+LGX_HD float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+LGX_HD f3 cross(f3 a, f3 b) { return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+// row-major 3x3
+LGX_HD f3 mv(const float* R, f3 v) {
+  return f3{R[0] * v.x + R[1] * v.y + R[2] * v.z, R[3] * v.x + R[4] * v.y + R[5] * v.z,
+            R[6] * v.x + R[7] * v.y + R[8] * v.z};
+}
+LGX_HD void mm(const float* A, const float* B, float* O) {
+  float T[9];
+  LGX_UNROLL
+  for (int i = 0; i < 3; ++i)
+    LGX_UNROLL
+    for (int j = 0; j < 3; ++j) T[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
+  LGX_UNROLL
+  for (int i = 0; i < 9; ++i) O[i] = T[i];
+}
+// symmetric inertia (xx yy zz xy xz yz) times vector
+LGX_HD f3 symv(const float* I, f3 v) {
+  return f3{I[0] * v.x + I[3] * v.y + I[4] * v.z, I[3] * v.x + I[1] * v.y + I[5] * v.z,
+            I[4] * v.x + I[5] * v.y + I[2] * v.z};
+}
+LGX_HD void quat_to_R(const float* q, float* R) {
+  float x = q[0], y = q[1], z = q[2], w = q[3];
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+}
+
+// ---------------------------------------------------------------- inside the physics
+// The one difference between the backends in this header: the kernel's physics contracts
+// a * b + c into fma (lgx_env.hip, "physics helpers"), the host backend never does, so the
+// bodies of this section are contracted under hipcc only. The backends' physics is
+// pinned to each other at 2e-3 (tests/test_host_parity.py), not bit for bit.
+#ifdef __HIPCC__
+#pragma clang fp contract(fast)
+#endif
+
+// symmetric 3x3 (xx yy zz xy xz yz) inverse
+LGX_HD void sym3_inv(const float* D, float* O) {
+  float a = D[0], b = D[1], c = D[2], d = D[3], e = D[4], f = D[5];
+  float A = b * c - f * f, Bm = -(d * c - e * f), Cm = d * f - b * e;
+  float det = a * A + d * Bm + e * Cm;
+  float inv = 1.0f / det;
+  O[0] = A * inv;
+  O[1] = (a * c - e * e) * inv;
+  O[2] = (a * b - d * d) * inv;
+  O[3] = Bm * inv;
+  O[4] = Cm * inv;
+  O[5] = -(a * f - d * e) * inv;
+}
+LGX_HD float sym3(const float* S, int i, int j) {
+  if (i == j) return S[i];
+  int k = i + j;  // (0,1)->3 (0,2)->4 (1,2)->5
+  return S[k == 1 ? 3 : (k == 2 ? 4 : 5)];
+}
+// packed symmetric 6x6 index (lower, row-major)
+LGX_HD int pk(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+
+// The reference's trimesh (terrain_utils.py:382-465) is never materialised: vertex (i, j) sits
+// at ((i + dx) hs, (j + dy) hs, h vs) - border, where h (int16) and the slope-threshold shift
+// (dx, dy in {-1, 0, 1}) are packed in one 32-bit word per vertex (lgx_buffers.terrain_mesh).
+// Here relative to the query's cell (ci, cj).
+LGX_HD f3 mesh_vertex(const uint32_t* mesh, int cols, int i, int j, int ci, int cj, float hs, float vs) {
+  const uint32_t w = mesh[(size_t)i * cols + j];
+  const float h = (float)(int16_t)(w & 0xffffu);
+  const int dx = (int)((w >> 16) & 3u) - 1, dy = (int)((w >> 18) & 3u) - 1;
+  return mk((float)(i - ci + dx) * hs, (float)(j - cj + dy) * hs, h * vs);
+}
+
+// closest point of triangle abc to p (Ericson, Real-Time Collision Detection 5.1.5),
+// with guards for the zero-area triangles a wall shift can produce
+LGX_HD f3 closest_on_triangle(f3 p, f3 a, f3 b, f3 c) {
+  const f3 ab = b - a, ac = c - a, ap = p - a;
+  const float d1 = dot(ab, ap), d2 = dot(ac, ap);
+  if (d1 <= 0.f && d2 <= 0.f) return a;
+  const f3 bp = p - b;
+  const float d3 = dot(ab, bp), d4 = dot(ac, bp);
+  if (d3 >= 0.f && d4 <= d3) return b;
+  const float vc = d1 * d4 - d3 * d2;
+  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) return a + ab * (d1 / fmaxf(d1 - d3, 1e-30f));
+  const f3 cp = p - c;
+  const float d5 = dot(ab, cp), d6 = dot(ac, cp);
+  if (d6 >= 0.f && d5 <= d6) return c;
+  const float vb = d5 * d2 - d1 * d6;
+  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) return a + ac * (d2 / fmaxf(d2 - d6, 1e-30f));
+  const float va = d3 * d6 - d5 * d4;
+  if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f)
+    return b + (c - b) * ((d4 - d3) / fmaxf((d4 - d3) + (d5 - d6), 1e-30f));
+  const float inv = 1.0f / fmaxf(va + vb + vc, 1e-30f);
+  return a + ab * (vb * inv) + ac * (vc * inv);
+}
+
+// surface height of triangle abc above (p.x, p.y) if its xy projection contains it
+LGX_HD bool height_in_triangle(f3 p, f3 a, f3 b, f3 c, float& z) {
+  const float e1x = b.x - a.x, e1y = b.y - a.y, e2x = c.x - a.x, e2y = c.y - a.y;
+  const float det = e1x * e2y - e1y * e2x;
+  if (fabsf(det) < 1e-10f) return false;  // vertical wall: no projection
+  const float px = p.x - a.x, py = p.y - a.y;
+  const float u = (px * e2y - py * e2x) / det, v = (e1x * py - e1y * px) / det;
+  const float eps = -1e-6f;
+  if (u < eps || v < eps || u + v > 1.0f - eps) return false;
+  z = a.z + u * (b.z - a.z) + v * (c.z - a.z);
+  return true;
+}
+
+#ifdef __HIPCC__
+#pragma clang fp contract(off)
+#endif
+
+// ---------------------------------------------------------------- the step's constants, post-physics
+// (isaacgym torch_utils / legged_gym math in fp32, no contraction: the reference evaluates
+// these as separate eager torch ops)
+namespace lgx {
+
+constexpr int NL = 13;  // dynamic links: base + 4 chains x 3 (checked by lgx_create)
+constexpr int NJ = 12;
+constexpr int NU = 18;
+constexpr int MAXC = LGX_MAX_CONTACTS;
+constexpr int MAXR = NJ + 3 * MAXC;
+// Philox blocks per env per step: 9 fixed blocks (commands, push/terrain, dof, root, reset
+// commands) + one per 4 observation-noise draws (oracle/philox.py num_blocks): Go2 22,
+// ANYmal (235 proprio) 68
+constexpr int NBLK_MAX = 9 + (LGX_MAX_PROPRIO + 3) / 4;
+constexpr int NSLOT = NBLK_MAX * 4;
+LGX_HD int rng_blocks(const lgx_task_params* Pm) { return 9 + (Pm->num_proprio + 3) / 4; }
+constexpr int MAXHIST = 1216;
+
+enum Slot { S_CMD = 0, S_PUSH = 4, S_TERR = 6, S_DOF = 8, S_ROOT_XY = 20, S_ROOT_VEL = 24, S_RCMD = 32, S_NOISE = 36 };
+
+struct Scratch {  // per-env post-physics scalars (go2.py:357-367, 279-328)
+  float blv[3], bav[3], pg[3];
+  float roll, pitch, yaw;
+  float ph[4];  // fl fr bl br
+  int contact[4];
+  float feet_z[4];
+  float jump;
+};
+
+// sums over joints / height points shared by the reward terms (each backend's joint_sums)
+enum JSum { J_ACTION_RATE, J_DELTA_TORQUES, J_DOF_ACC, J_DOF_ERROR, J_DOF_POS_LIMITS, J_DOF_VEL, J_DOF_VEL_LIMITS,
+            J_STAND_ABS, J_TORQUE_LIMITS, J_TORQUES, J_HIP_POS, J_THIGH_POS, J_CALF_POS, J_HEIGHT, J_N };
+
+LGX_HD void quat_rotate_inverse(const float* q, const float* v, float* out) {
+  float w = q[3];
+  float sc = 2.0f * (w * w) - 1.0f;
+  float cx = q[1] * v[2] - q[2] * v[1];
+  float cy = q[2] * v[0] - q[0] * v[2];
+  float cz = q[0] * v[1] - q[1] * v[0];
+  float d = q[0] * v[0] + q[1] * v[1] + q[2] * v[2];
+  out[0] = v[0] * sc - cx * w * 2.0f + q[0] * d * 2.0f;
+  out[1] = v[1] * sc - cy * w * 2.0f + q[1] * d * 2.0f;
+  out[2] = v[2] * sc - cz * w * 2.0f + q[2] * d * 2.0f;
+}
+LGX_HD void quat_apply(const float* q, const float* b, float* out) {
+  float t0 = (q[1] * b[2] - q[2] * b[1]) * 2.0f;
+  float t1 = (q[2] * b[0] - q[0] * b[2]) * 2.0f;
+  float t2 = (q[0] * b[1] - q[1] * b[0]) * 2.0f;
+  out[0] = b[0] + q[3] * t0 + (q[1] * t2 - q[2] * t1);
+  out[1] = b[1] + q[3] * t1 + (q[2] * t0 - q[0] * t2);
+  out[2] = b[2] + q[3] * t2 + (q[0] * t1 - q[1] * t0);
+}
+LGX_HD float trem(float a, float b) {  // torch.remainder
+  float m = fmodf(a, b);
+  if (m != 0.0f && ((m < 0.0f) != (b < 0.0f))) m += b;
+  return m;
+}
+LGX_HD float wrap_to_pi(float a) {
+  const float two_pi = 6.283185307179586f, pi = 3.141592653589793f;
+  float m = trem(a, two_pi);
+  m -= two_pi * (float)(m > pi);
+  return m;
+}
+LGX_HD float clipf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+LGX_HD float sq(float x) { return x * x; }
+LGX_HD float nrm3(float a, float b, float c) { return sqrtf(a * a + b * b + c * c); }
+LGX_HD float nrm2(float a, float b) { return sqrtf(a * a + b * b); }
+LGX_HD float rand_range(float lo, float hi, float u) {
+  float span = (float)((double)hi - (double)lo);
+  return span * u + lo;
+}
+// torch_rand_float(lo, hi) with the reference's Python-float (double) bounds: (hi - lo) and lo
+// enter the fp32 tensor ops as fp32 scalars
+LGX_HD float rand_range_d(double lo, double hi, float u) { return (float)(hi - lo) * u + (float)lo; }
+
+// One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
+LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
+  uint32_t o[4];
+  philox4x32_10(gid, (uint32_t)step, (uint32_t)(slot >> 2), (uint32_t)(step >> 32), (uint32_t)seed,
+                (uint32_t)(seed >> 32), o);
+  return u01(o[slot & 3]);
+}
+
+// Go2Robot._resample_commands go2.py:413-464 / LeggedRobot legged_robot.py:406-437
+// R: the mutable command ranges (lgx_buffers.command_ranges, double [8]) or NULL (params' ranges)
+LGX_HD void resample_commands(const lgx_task_params* Pm, const double* R, float* cmd, const float* U, int slot0,
+                              const float* quat) {
+  if (Pm->has_user_command) {
+    for (int i = 0; i < 4; ++i) cmd[i] = Pm->user_command[i];
+    return;
+  }
+  if (R) {
+    cmd[0] = rand_range_d(R[0], R[1], U[slot0 + 0]);
+    cmd[1] = rand_range_d(R[2], R[3], U[slot0 + 1]);
+    if (Pm->heading_command)
+      cmd[3] = rand_range_d(R[6], R[7], U[slot0 + 2]);
+    else
+      cmd[2] = rand_range_d(R[4], R[5], U[slot0 + 2]);
+  } else {
+    cmd[0] = rand_range(Pm->cmd_lin_vel_x[0], Pm->cmd_lin_vel_x[1], U[slot0 + 0]);
+    cmd[1] = rand_range(Pm->cmd_lin_vel_y[0], Pm->cmd_lin_vel_y[1], U[slot0 + 1]);
+    if (Pm->heading_command)
+      cmd[3] = rand_range(Pm->cmd_heading[0], Pm->cmd_heading[1], U[slot0 + 2]);
+    else
+      cmd[2] = rand_range(Pm->cmd_ang_vel_yaw[0], Pm->cmd_ang_vel_yaw[1], U[slot0 + 2]);
+  }
+  float keep = (float)(nrm2(cmd[0], cmd[1]) > 0.2f);
+  cmd[0] = cmd[0] * keep;
+  cmd[1] = cmd[1] * keep;
+  if (Pm->zero_command && U[slot0 + 3] < Pm->zero_command_prob) {
+    if (Pm->task_kind == LGX_TASK_GO2) {
+      cmd[0] = cmd[0] * 0.0f; cmd[1] = cmd[1] * 0.0f; cmd[2] = cmd[2] * 0.0f;
+      if (Pm->heading_command) {
+        const float fwd[3] = {1.f, 0.f, 0.f};
+        float f[3];
+        quat_apply(quat, fwd, f);
+        cmd[3] = atan2f(f[1], f[0]);
+      }
+    } else {
+      for (int i = 0; i < 4; ++i) cmd[i] = cmd[i] * 0.0f;
+    }
+  }
+}
+
+// The scalar head of reset_idx for env e (go2.py:207-263 / legged_robot.py:157-213) on the
+// env's staged state S (root, cmd, ep): terrain-level curriculum, root state, command resample.
+// U: the env's uniforms. terrain_curriculum: whether the caller lets the curriculum run.
+template <class S>
+LGX_HD void reset_env_head(const lgx_task_params* Pm, const lgx_buffers& B, S& s, const float* U, int e,
+                           bool terrain_curriculum) {
+  float* root = s.root;
+  float* cmd = s.cmd;
+  // terrain curriculum legged_robot.py:543-574
+  if (Pm->curriculum && terrain_curriculum && B.terrain_levels) {
+    float dx = root[0] - B.env_origins[e * 3 + 0], dy = root[1] - B.env_origins[e * 3 + 1];
+    float dist = nrm2(dx, dy);
+    int up = dist > Pm->terrain_length * Pm->promote_threshold;
+    float expct = nrm2(cmd[0], cmd[1]) * Pm->max_episode_length_s;
+    int down = dist < expct * Pm->demote_threshold;
+    int64_t lvl = B.terrain_levels[e] + up - down;
+    if (lvl >= Pm->max_terrain_level) {
+      lvl = (int64_t)(U[S_TERR] * (float)Pm->max_terrain_level);
+      if (lvl >= Pm->max_terrain_level) lvl = Pm->max_terrain_level - 1;
+    } else if (lvl < 0) {
+      lvl = 0;
+    }
+    B.terrain_levels[e] = lvl;
+    const float* o = B.terrain_origins + ((size_t)lvl * Pm->num_terrain_cols + B.terrain_types[e]) * 3;
+    for (int i = 0; i < 3; ++i) B.env_origins[e * 3 + i] = o[i];
+  }
+  // _reset_root_states legged_robot.py:509-532
+  for (int i = 0; i < 13; ++i) root[i] = Pm->base_init_state[i];
+  for (int i = 0; i < 3; ++i) root[i] = root[i] + B.env_origins[e * 3 + i];
+  if (Pm->custom_origins) {
+    root[0] = root[0] + rand_range(-1.0f, 1.0f, U[S_ROOT_XY + 0]);
+    root[1] = root[1] + rand_range(-1.0f, 1.0f, U[S_ROOT_XY + 1]);
+  }
+  for (int i = 0; i < 6; ++i) root[7 + i] = rand_range(-0.5f, 0.5f, U[S_ROOT_VEL + i]);
+  resample_commands(Pm, B.command_ranges, cmd, U, S_RCMD, root + 3);
+  s.ep = 0;
+}
+
+// One reward term (the `_reward_<name>` methods; ids in include/lgx.h) on a backend's env
+// state S: x (Scratch), root, cmd, th, cf, lc, lch, fat, jsum.
+// Side effects (kept from the reference): feet_air_time (go2.py:827-830) and the in-place
+// wrap of commands[:, 3] (go2.py:744) are written back to the state.
+template <class S>
+LGX_HD float reward_term(const lgx_task_params* Pm, S& s, int id) {
+  const Scratch& x = s.x;
+  const float* root = s.root;
+  float* cmd = s.cmd;
+  const float* lch = s.lch;
+  float* fat = s.fat;
+  const int* lc = s.lc;
+  float r = 0.0f;
+  switch (id) {
+    case LGX_REW_ACTION_RATE: return s.jsum[J_ACTION_RATE];
+    case LGX_REW_ANG_VEL_XY: return sq(x.bav[0]) + sq(x.bav[1]);
+    case LGX_REW_BASE_HEIGHT:
+      return sq(s.jsum[J_HEIGHT] / (float)Pm->num_height_points - Pm->base_height_target);
+    case LGX_REW_CALF_COLLISION:
+      for (int i = 0; i < 4; ++i) { const float* c = s.cf[Pm->calf_idx[i]]; r += (float)(nrm3(c[0], c[1], c[2]) > 0.1f); }
+      return r;
+    case LGX_REW_CALF_POS: return s.jsum[J_CALF_POS];
+    case LGX_REW_CALF_SYMMETRY: {
+      const int* c = Pm->calf_joint_idx;
+      return fabsf(s.th[c[0]] - s.th[c[1]]) + fabsf(s.th[c[2]] - s.th[c[3]]);
+    }
+    case LGX_REW_COLLISION:
+      for (int i = 0; i < Pm->n_penalised; ++i) {
+        const float* c = s.cf[Pm->penalised_idx[i]];
+        r += (float)(nrm3(c[0], c[1], c[2]) > 0.1f);
+      }
+      return r;
+    case LGX_REW_DELTA_TORQUES: return s.jsum[J_DELTA_TORQUES];
+    case LGX_REW_DOF_ACC: return s.jsum[J_DOF_ACC];
+    case LGX_REW_DOF_ERROR: return s.jsum[J_DOF_ERROR];
+    case LGX_REW_DOF_POS_LIMITS: return s.jsum[J_DOF_POS_LIMITS];
+    case LGX_REW_DOF_VEL: return s.jsum[J_DOF_VEL];
+    case LGX_REW_DOF_VEL_LIMITS: return s.jsum[J_DOF_VEL_LIMITS];
+    case LGX_REW_FEET_AIR_TIME: {
+      float rew = 0.0f;
+      for (int f = 0; f < Pm->num_feet; ++f) {
+        int cfl = (s.cf[Pm->feet_idx[f]][2] > 1.0f) || lc[f];
+        float first = (float)((fat[f] > 0.0f) && cfl);
+        fat[f] = fat[f] + Pm->dt;
+        rew += (fat[f] - 0.5f) * first;
+      }
+      rew = rew * (float)(nrm2(cmd[0], cmd[1]) > 0.1f);
+      for (int f = 0; f < Pm->num_feet; ++f) {
+        int cfl = (s.cf[Pm->feet_idx[f]][2] > 1.0f) || lc[f];
+        fat[f] = fat[f] * (float)(!cfl);
+      }
+      return rew;
+    }
+    case LGX_REW_FEET_CONTACT_FORCES:
+      for (int f = 0; f < Pm->num_feet; ++f) {
+        const float* c = s.cf[Pm->feet_idx[f]];
+        float v = nrm3(c[0], c[1], c[2]) - Pm->max_contact_force;
+        r += v > 0.0f ? v : 0.0f;
+      }
+      return r;
+    case LGX_REW_HEADING_ALIGNMENT: {
+      const float fwd[3] = {1.f, 0.f, 0.f};
+      float f[3];
+      quat_apply(root + 3, fwd, f);
+      float heading = atan2f(f[1], f[0]);
+      float desired = 0.0f;
+      if (Pm->heading_command) {
+        cmd[3] = wrap_to_pi(cmd[3]);  // wrap_to_pi mutates commands[:, 3] (Q7)
+        desired = cmd[3];
+      }
+      float err = wrap_to_pi(desired - heading);
+      return sq(err) * (float)(nrm3(cmd[0], cmd[1], cmd[2]) >= 0.2f);
+    }
+    case LGX_REW_HIP_POS: return s.jsum[J_HIP_POS];
+    case LGX_REW_JUMP_ZONE_FORWARD_VEL: {
+      float fr = root[7] > 0.0f ? root[7] : 0.0f;
+      return fr * (float)(x.jump > 0.0f) * (float)(nrm3(cmd[0], cmd[1], cmd[2]) >= 0.2f);
+    }
+    case LGX_REW_JUMP_ZONE_UPWARD_VEL: {
+      float up = root[9] > 0.0f ? root[9] : 0.0f;
+      return up * (float)(x.jump > 0.0f) * (float)(nrm3(cmd[0], cmd[1], cmd[2]) >= 0.2f);
+    }
+    case LGX_REW_LIN_VEL_Z: return sq(x.blv[2]);
+    case LGX_REW_MIN_HEIGHT: {
+      float ze = clipf(Pm->base_height_target - root[2], 0.0f, Pm->base_height_target);
+      return ze * (float)(x.jump > 0.0f);
+    }
+    case LGX_REW_ORIENTATION: return sq(x.pg[0]) + sq(x.pg[1]);
+    case LGX_REW_PHASE_CONTACT_MATCH: {
+      float thr = 2.0f * Pm->percent_time_on_ground - 1.0f;
+      float rew = 0.0f;
+      for (int f = 0; f < 4; ++f) {
+        int stance = sinf(6.283185307179586f * x.ph[f]) <= thr;
+        rew += (x.contact[f] == stance) ? 0.25f : -0.25f;
+      }
+      return rew;
+    }
+    case LGX_REW_PHASE_FOOT_LIFTING: {
+      float thr = 2.0f * Pm->percent_time_on_ground - 1.0f;
+      float rew = 0.0f;
+      for (int f = 0; f < 4; ++f) {
+        int stance = sinf(6.283185307179586f * x.ph[f]) <= thr;
+        float h = clipf(x.feet_z[f] - lch[f], 0.0f, Pm->max_foot_height);
+        float nh = h / Pm->max_foot_height;
+        rew += stance ? -nh : nh;
+      }
+      return rew / 2.0f;
+    }
+    case LGX_REW_REVERSE_PENALTY: return -(root[7] < 0.0f ? root[7] : 0.0f);
+    case LGX_REW_STAND_STILL: return s.jsum[J_STAND_ABS] * (float)(nrm2(cmd[0], cmd[1]) < 0.1f);
+    case LGX_REW_STUMBLE_CALVES: {
+      int any = 0;
+      for (int i = 0; i < 4; ++i) { const float* c = s.cf[Pm->calf_idx[i]]; any |= nrm2(c[0], c[1]) > 5.0f * fabsf(c[2]); }
+      return (float)any;
+    }
+    case LGX_REW_STUMBLE_FEET: {
+      int any = 0;
+      for (int f = 0; f < Pm->num_feet; ++f) { const float* c = s.cf[Pm->feet_idx[f]]; any |= nrm2(c[0], c[1]) > 5.0f * fabsf(c[2]); }
+      return (float)any;
+    }
+    case LGX_REW_THIGH_POS: return s.jsum[J_THIGH_POS];
+    case LGX_REW_THIGH_SYMMETRY: {
+      const int* c = Pm->thigh_joint_idx;
+      return fabsf(s.th[c[0]] - s.th[c[1]]) + fabsf(s.th[c[2]] - s.th[c[3]]);
+    }
+    case LGX_REW_TORQUE_LIMITS: return s.jsum[J_TORQUE_LIMITS];
+    case LGX_REW_TORQUES: return s.jsum[J_TORQUES];
+    case LGX_REW_TRACKING_ANG_VEL: return expf(-sq(cmd[2] - x.bav[2]) / Pm->tracking_sigma);
+    case LGX_REW_TRACKING_LIN_VEL: return expf(-(sq(cmd[0] - x.blv[0]) + sq(cmd[1] - x.blv[1])) / Pm->tracking_sigma);
+    case LGX_REW_TRACKING_PITCH: {
+      float deg = x.pitch * 57.29577951308232f;
+      return expf(-sq(deg - Pm->pitch_deg_target) / Pm->tracking_sigma);
+    }
+    case LGX_REW_TRACKING_ROLL: {
+      float deg = x.roll * 57.29577951308232f;
+      return expf(-sq(deg - Pm->roll_deg_target) / Pm->tracking_sigma);
+    }
+    case LGX_REW_ZERO_CMD_DOF_ERROR:
+      return s.jsum[J_DOF_ERROR] * (float)(nrm3(cmd[0], cmd[1], cmd[2]) < 0.2f);
+    default: return 0.0f;
+  }
+}
+
+// update_command_curriculum (go2.py:80-107 / legged_robot.py:580-591), the range update.
+// S, Cn: sum and count of the pre-reset tracking_lin_vel episode sums (curriculum_vals) over
+// the envs reset in this step. Widens command_ranges (and command_range_log) when their mean
+// passes the threshold; returns whether the range changed.
+LGX_HD bool curriculum_update_ranges(const lgx_task_params* Pm, const lgx_buffers& B, double S, double Cn) {
+  int ch = 0;
+  // torch.mean (fp32) / max_episode_length, compared in fp32 (no reset: reset_idx returns early)
+  const float mean = Cn > 0.0 ? ((float)S / (float)Cn) / (float)Pm->max_episode_length : 0.f;
+  if (Cn > 0.0 && mean > Pm->curriculum_threshold) {
+    double* R = B.command_ranges;
+    const double lo = R[0], hi = R[1], d = Pm->curriculum_delta;
+    const double lo_max = Pm->curriculum_lo_free ? lo - d : Pm->curriculum_lo_max;
+    const double nlo = fmin(fmax(lo - d, Pm->curriculum_lo_min), lo_max);  // np.clip
+    const double nhi = fmin(fmax(hi + d, 0.0), Pm->curriculum_hi_max);
+    ch = (nlo != lo) || (nhi != hi);
+    R[0] = nlo;
+    R[1] = nhi;
+    float* L = B.command_range_log;
+    if (L) {
+      if (Pm->command_curriculum == 1) { L[0] = (float)nhi; L[1] = (float)nlo; L[2] = (float)R[3]; L[3] = (float)R[5]; }
+      else { L[0] = (float)nhi; L[1] = (float)R[3]; L[2] = (float)R[5]; }
+    }
+  }
+  return ch != 0;
+}
+
+// After a range change, env e (reset in this step): its commands are resampled again from the
+// same uniforms with the new range (reset_idx resamples after the curriculum, go2.py:222-230)
+// and the command entries of its observation rows are rewritten (a reset env's history is zero
+// in obs and all copies of the current observation in obs_history, go2.py:570-574).
+LGX_HD void curriculum_rewrite_env(const lgx_task_params* Pm, const lgx_buffers& B, uint64_t seed, uint64_t step,
+                                   int e) {
+  const bool go2 = Pm->task_kind == LGX_TASK_GO2;
+  const int Pp = Pm->num_proprio, H = Pm->history_len, c0 = go2 ? 5 : 9;
+  const float co = Pm->clip_obs;
+  const uint32_t gid = (uint32_t)(Pm->env_id_offset + e);
+  float U[4];  // the reset's command draws (slots S_RCMD..+3)
+  for (int k = 0; k < 4; ++k) U[k] = step_uniform(seed, gid, step, S_RCMD + k);
+  float cmd[4];
+  for (int k = 0; k < 4; ++k) cmd[k] = B.commands[e * 4 + k];
+  const float* quat = B.root_states + (size_t)e * 13 + 3;
+  resample_commands(Pm, B.command_ranges, cmd, U, 0, quat);
+  for (int k = 0; k < 4; ++k) B.commands[e * 4 + k] = cmd[k];
+  float* obs = B.obs + (size_t)e * Pm->num_obs;
+  float* cr = (go2 && B.critic) ? B.critic + (size_t)e * Pm->num_critic : nullptr;
+  float* hist = B.obs_history + (size_t)e * H * Pp;
+  for (int j = 0; j < 3; ++j) {
+    const int i = c0 + j;
+    float v = cmd[j] * Pm->commands_scale[j];
+    if (Pm->add_noise) v = v + (2.0f * step_uniform(seed, gid, step, S_NOISE + i) - 1.0f) * Pm->noise_vec[i];
+    const float vc = clipf(v, -co, co);
+    obs[H * Pp + i] = vc;
+    if (cr) cr[H * Pp + i] = vc;
+    for (int t = 0; t < H; ++t) hist[t * Pp + i] = v;  // reset env: every history row = current obs
+  }
+}
+
+}  // namespace lgx

@@ -10,7 +10,9 @@
 //   * the constraint solve always uses the dense A = J M⁻¹ Jᵀ (the kernel switches to a
 //     velocity-space sweep above 24 rows to bound LDS; both are the same Gauss-Seidel).
 // Post-physics follows legged_robot.py / go2.py statement order with no fp contraction
-// (built with -ffp-contract=off), like the kernel's golden-pinned tail.
+// (built with -ffp-contract=off), like the kernel's golden-pinned tail. The scalar code with
+// no lane index in it is the kernel's own, from lgx_env_common.h; what stays here is the physics
+// and the phases the kernel runs lane-parallel.
 #include <math.h>
 #include <cmath>
 #include <omp.h>
@@ -20,76 +22,12 @@
 #include <algorithm>
 #include <vector>
 
+#include "lgx_env_common.h"
 #include "lgx_host.h"
 
 namespace lgxh {
 
-constexpr int NL = 13, NJ = 12, NU = 18;
-constexpr int MAXC = LGX_MAX_CONTACTS;
-constexpr int MAXR = NJ + 3 * MAXC;
-constexpr int NBLK_MAX = 9 + (LGX_MAX_PROPRIO + 3) / 4;
-constexpr int MAXHIST = 1216;
-enum Slot { S_CMD = 0, S_PUSH = 4, S_TERR = 6, S_DOF = 8, S_ROOT_XY = 20, S_ROOT_VEL = 24, S_RCMD = 32, S_NOISE = 36 };
-
-// ------------------------------------------------------------------ small math
-struct v3 {
-  float x, y, z;
-};
-static inline v3 V(float x, float y, float z) { return v3{x, y, z}; }
-static inline v3 L3(const float* p) { return v3{p[0], p[1], p[2]}; }
-static inline void S3(float* p, v3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
-static inline v3 operator+(v3 a, v3 b) { return v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-static inline v3 operator-(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-static inline v3 operator*(v3 a, float s) { return v3{a.x * s, a.y * s, a.z * s}; }
-static inline float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-static inline v3 cross(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-static inline v3 rot(const float* R, v3 v) {  // row-major 3x3 times v
-  return v3{R[0] * v.x + R[1] * v.y + R[2] * v.z, R[3] * v.x + R[4] * v.y + R[5] * v.z,
-            R[6] * v.x + R[7] * v.y + R[8] * v.z};
-}
-static inline void matmul3(const float* A, const float* B, float* O) {
-  float T[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) T[i * 3 + j] = A[i * 3] * B[j] + A[i * 3 + 1] * B[3 + j] + A[i * 3 + 2] * B[6 + j];
-  memcpy(O, T, sizeof(T));
-}
-static inline v3 symmul(const float* I, v3 v) {  // symmetric (xx yy zz xy xz yz) times v
-  return v3{I[0] * v.x + I[3] * v.y + I[4] * v.z, I[3] * v.x + I[1] * v.y + I[5] * v.z,
-            I[4] * v.x + I[5] * v.y + I[2] * v.z};
-}
-static inline void quat_R(const float* q, float* R) {
-  const float x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
-  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
-  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
-}
-static inline void sym3_inverse(const float* D, float* O) {
-  const float a = D[0], b = D[1], c = D[2], d = D[3], e = D[4], f = D[5];
-  const float A = b * c - f * f, Bm = -(d * c - e * f), Cm = d * f - b * e;
-  const float inv = 1.0f / (a * A + d * Bm + e * Cm);
-  O[0] = A * inv; O[1] = (a * c - e * e) * inv; O[2] = (a * b - d * d) * inv;
-  O[3] = Bm * inv; O[4] = Cm * inv; O[5] = -(a * f - d * e) * inv;
-}
-static inline float sym3_at(const float* S, int i, int j) {
-  if (i == j) return S[i];
-  const int k = i + j;
-  return S[k == 1 ? 3 : (k == 2 ? 4 : 5)];
-}
-static inline int pk6(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
-
-// Philox4x32-10 (oracle/philox.py layout: c0 = global env id, c1/c3 = step lo/hi,
-// c2 = block | stream << 16, key = seed)
-static inline void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                          uint32_t out[4]) {
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-static inline float unit(uint32_t x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
+using namespace lgx;  // the shared scalar code (lgx_env_common.h)
 
 // ------------------------------------------------------------------ per-env state
 struct Link {
@@ -114,8 +52,8 @@ struct Env {
   float cf[LGX_MAX_BODIES][3], rbz[LGX_MAX_BODIES];
   // post-physics
   float root[13], cmd[4], U[4 * NBLK_MAX];
-  float blv[3], bav[3], pg[3], roll, pitch, yaw, ph[4], feet_z[4], jump;
-  int contact[4], lc[4];
+  Scratch x;
+  int lc[4];
   float lch[4], fat[4];
   float cur[LGX_MAX_PROPRIO], hist[MAXHIST], heights[LGX_MAX_HEIGHT_POINTS];
   float jsum[16], rterm[64];
@@ -132,50 +70,50 @@ static void kinematics(Env& s, const lgx_model* M, const lgx_task_params* P) {
   float Al[NL][3], Ao[NL][3];
   {
     Link& b = s.lk[0];
-    quat_R(s.qb, b.R);
-    S3(b.P, L3(s.pb)); S3(b.ax, V(0, 0, 0)); S3(b.W, L3(s.wb)); S3(b.V, L3(s.vo));
-    S3(Al[0], V(0, 0, 0)); S3(Ao[0], V(0, 0, 0));
+    quat_to_R(s.qb, b.R);
+    st3(b.P, ld3(s.pb)); st3(b.ax, mk(0, 0, 0)); st3(b.W, ld3(s.wb)); st3(b.V, ld3(s.vo));
+    st3(Al[0], mk(0, 0, 0)); st3(Ao[0], mk(0, 0, 0));
   }
   for (int j = 0; j < NJ; ++j) {
     const int k = j + 1, par = (j % 3 == 0) ? 0 : j;
     const Link& p = s.lk[par];
     Link& c = s.lk[k];
-    const v3 orig = L3(M->joint_origin[k]), al = L3(M->joint_axis[k]);
+    const f3 orig = ld3(M->joint_origin[k]), al = ld3(M->joint_axis[k]);
     const float* Rj = M->joint_rot[k];
     const float th = s.th[j], ct = cosf(th), st = sinf(th), t1 = 1.f - ct;
     const float Ra[9] = {t1 * al.x * al.x + ct, t1 * al.x * al.y - st * al.z, t1 * al.x * al.z + st * al.y,
                          t1 * al.x * al.y + st * al.z, t1 * al.y * al.y + ct, t1 * al.y * al.z - st * al.x,
                          t1 * al.x * al.z - st * al.y, t1 * al.y * al.z + st * al.x, t1 * al.z * al.z + ct};
     float Rl[9];
-    matmul3(Rj, Ra, Rl);
-    const v3 o = rot(p.R, orig), ax = rot(p.R, rot(Rj, al));
-    matmul3(p.R, Rl, c.R);
-    const v3 Wp = L3(p.W), wa = ax * s.thd[j];
-    S3(c.P, L3(p.P) + o);
-    S3(c.ax, ax);
-    S3(c.W, Wp + wa);
+    mm(Rj, Ra, Rl);
+    const f3 o = mv(p.R, orig), ax = mv(p.R, mv(Rj, al));
+    mm(p.R, Rl, c.R);
+    const f3 Wp = ld3(p.W), wa = ax * s.thd[j];
+    st3(c.P, ld3(p.P) + o);
+    st3(c.ax, ax);
+    st3(c.W, Wp + wa);
     if constexpr (BIAS) {
-      S3(Al[k], L3(Al[par]) + cross(Wp, wa));
-      S3(Ao[k], L3(Ao[par]) + cross(L3(Al[par]), o) + cross(Wp, cross(Wp, o)));
+      st3(Al[k], ld3(Al[par]) + cross(Wp, wa));
+      st3(Ao[k], ld3(Ao[par]) + cross(ld3(Al[par]), o) + cross(Wp, cross(Wp, o)));
     } else {
-      S3(c.V, L3(p.V) + cross(Wp, o));
+      st3(c.V, ld3(p.V) + cross(Wp, o));
     }
   }
-  const v3 g = L3(P->gravity), p0 = L3(s.pb);
+  const f3 g = ld3(P->gravity), p0 = ld3(s.pb);
   if constexpr (BIAS) memset(s.tot, 0, sizeof(s.tot));
   for (int k = 0; k < NL; ++k) {
     Link& c = s.lk[k];
     const float cb = k == 0 ? 1.f : 0.f;
     const float* cl = M->link_com[k];
-    const v3 C = L3(c.P) + rot(c.R, V(cl[0] + cb * s.cadd[0], cl[1] + cb * s.cadd[1], cl[2] + cb * s.cadd[2]));
-    S3(c.C, C);
+    const f3 C = ld3(c.P) + mv(c.R, mk(cl[0] + cb * s.cadd[0], cl[1] + cb * s.cadd[1], cl[2] + cb * s.cadd[2]));
+    st3(c.C, C);
     if constexpr (BIAS) {
       const float m = M->link_mass[k] + cb * s.madd;
       const float* In = M->link_inertia[k];
       const float Il[9] = {In[0], In[3], In[4], In[3], In[1], In[5], In[4], In[5], In[2]};
       const float* R = c.R;
       float T[9];
-      matmul3(R, Il, T);
+      mm(R, Il, T);
       float* Iw = c.I;
       Iw[0] = T[0] * R[0] + T[1] * R[1] + T[2] * R[2];
       Iw[1] = T[3] * R[3] + T[4] * R[4] + T[5] * R[5];
@@ -184,14 +122,14 @@ static void kinematics(Env& s, const lgx_model* M, const lgx_task_params* P) {
       Iw[4] = T[0] * R[6] + T[1] * R[7] + T[2] * R[8];
       Iw[5] = T[3] * R[6] + T[4] * R[7] + T[5] * R[8];
       c.m = m;
-      const v3 W = L3(c.W), al = L3(Al[k]), rl = C - L3(c.P);
-      const v3 acc = L3(Ao[k]) + cross(al, rl) + cross(W, cross(W, rl));
-      const v3 F = (acc - g) * m, N = symmul(Iw, al) + cross(W, symmul(Iw, W));
-      S3(c.F, F);
-      S3(c.N, N);
-      const v3 r = C - p0;
+      const f3 W = ld3(c.W), al = ld3(Al[k]), rl = C - ld3(c.P);
+      const f3 acc = ld3(Ao[k]) + cross(al, rl) + cross(W, cross(W, rl));
+      const f3 F = (acc - g) * m, N = symv(Iw, al) + cross(W, symv(Iw, W));
+      st3(c.F, F);
+      st3(c.N, N);
+      const f3 r = C - p0;
       const float rr = dot(r, r);
-      const v3 Nt = cross(r, F) + N;
+      const f3 Nt = cross(r, F) + N;
       const float rd[16] = {m, m * r.x, m * r.y, m * r.z,
                             Iw[0] + m * (rr - r.x * r.x), Iw[1] + m * (rr - r.y * r.y), Iw[2] + m * (rr - r.z * r.z),
                             Iw[3] - m * r.x * r.y, Iw[4] - m * r.x * r.z, Iw[5] - m * r.y * r.z,
@@ -204,21 +142,21 @@ static void kinematics(Env& s, const lgx_model* M, const lgx_task_params* P) {
 // Mass matrix M = [A B; Bᵀ D] (D block diagonal over the legs) and bias h, factored:
 // X = B D⁻¹, S = A − X Bᵀ (base Schur complement), S⁻¹ — lgx_env.hip `dynamics`.
 static void dynamics(Env& s) {
-  const v3 p0 = L3(s.lk[0].P);
+  const f3 p0 = ld3(s.lk[0].P);
   for (int j = 0; j < NJ; ++j) {
     const int l = j / 3, a = j % 3;
     const Link& lj = s.lk[1 + j];
-    const v3 ax = L3(lj.ax), pj = L3(lj.P);
-    v3 acc = V(0, 0, 0), hl = V(0, 0, 0), bang = V(0, 0, 0);
+    const f3 ax = ld3(lj.ax), pj = ld3(lj.P);
+    f3 acc = mk(0, 0, 0), hl = mk(0, 0, 0), bang = mk(0, 0, 0);
     for (int i = a; i < 3; ++i) {
       const Link& c = s.lk[1 + 3 * l + i];
-      const v3 C = L3(c.C), d = C - pj;
-      acc = acc + cross(d, L3(c.F)) + L3(c.N);
+      const f3 C = ld3(c.C), d = C - pj;
+      acc = acc + cross(d, ld3(c.F)) + ld3(c.N);
       hl = hl + d * c.m;
-      bang = bang + cross(C - p0, cross(ax, d)) * c.m + symmul(c.I, ax);
+      bang = bang + cross(C - p0, cross(ax, d)) * c.m + symv(c.I, ax);
     }
     s.hj[j] = dot(ax, acc);
-    const v3 blin = cross(ax, hl);
+    const f3 blin = cross(ax, hl);
     float* Bj = s.Bc[j];
     Bj[0] = blin.x; Bj[1] = blin.y; Bj[2] = blin.z; Bj[3] = bang.x; Bj[4] = bang.y; Bj[5] = bang.z;
   }
@@ -227,20 +165,20 @@ static void dynamics(Env& s) {
       const int j1 = e < 3 ? e : (e == 5 ? 1 : 0), j2 = e < 3 ? e : (e == 3 ? 1 : 2);
       const Link& k1 = s.lk[1 + 3 * l + j1];
       const Link& k2 = s.lk[1 + 3 * l + j2];
-      const v3 a1 = L3(k1.ax), a2 = L3(k2.ax), q1 = L3(k1.P), q2 = L3(k2.P);
+      const f3 a1 = ld3(k1.ax), a2 = ld3(k2.ax), q1 = ld3(k1.P), q2 = ld3(k2.P);
       float acc = 0.f;
       for (int i = j2; i < 3; ++i) {
         const Link& c = s.lk[1 + 3 * l + i];
-        const v3 C = L3(c.C);
-        acc += c.m * dot(cross(a1, C - q1), cross(a2, C - q2)) + dot(a1, symmul(c.I, a2));
+        const f3 C = ld3(c.C);
+        acc += c.m * dot(cross(a1, C - q1), cross(a2, C - q2)) + dot(a1, symv(c.I, a2));
       }
       s.Dl[l][e] = acc;
     }
-    sym3_inverse(s.Dl[l], s.Dinv[l]);
+    sym3_inv(s.Dl[l], s.Dinv[l]);
   }
   for (int j = 0; j < NJ; ++j) {
     const int l = j / 3, a = j % 3;
-    const float d0 = sym3_at(s.Dinv[l], a, 0), d1 = sym3_at(s.Dinv[l], a, 1), d2 = sym3_at(s.Dinv[l], a, 2);
+    const float d0 = sym3(s.Dinv[l], a, 0), d1 = sym3(s.Dinv[l], a, 1), d2 = sym3(s.Dinv[l], a, 2);
     for (int r = 0; r < 6; ++r) s.X[j][r] = d0 * s.Bc[3 * l][r] + d1 * s.Bc[3 * l + 1][r] + d2 * s.Bc[3 * l + 2][r];
   }
   const float* t = s.tot;
@@ -256,25 +194,25 @@ static void dynamics(Env& s) {
   }
   float inv[6];
   for (int c = 0; c < 6; ++c) {  // Cholesky S = L Lᵀ (packed lower)
-    float d = L[pk6(c, c)];
-    for (int k = 0; k < c; ++k) d -= L[pk6(c, k)] * L[pk6(c, k)];
+    float d = L[pk(c, c)];
+    for (int k = 0; k < c; ++k) d -= L[pk(c, k)] * L[pk(c, k)];
     inv[c] = 1.0f / sqrtf(fmaxf(d, 1e-12f));
     for (int r = c + 1; r < 6; ++r) {
-      float v = L[pk6(r, c)];
-      for (int k = 0; k < c; ++k) v -= L[pk6(r, k)] * L[pk6(c, k)];
-      L[pk6(r, c)] = v * inv[c];
+      float v = L[pk(r, c)];
+      for (int k = 0; k < c; ++k) v -= L[pk(r, k)] * L[pk(c, k)];
+      L[pk(r, c)] = v * inv[c];
     }
   }
   for (int col = 0; col < 6; ++col) {  // S⁻¹ e_col
     float x[6];
     for (int r = 0; r < 6; ++r) {
       float v = r == col ? 1.f : 0.f;
-      for (int k = 0; k < r; ++k) v -= L[pk6(r, k)] * x[k];
+      for (int k = 0; k < r; ++k) v -= L[pk(r, k)] * x[k];
       x[r] = v * inv[r];
     }
     for (int r = 5; r >= 0; --r) {
       float v = x[r];
-      for (int k = r + 1; k < 6; ++k) v -= L[pk6(k, r)] * x[k];
+      for (int k = r + 1; k < 6; ++k) v -= L[pk(k, r)] * x[k];
       x[r] = v * inv[r];
     }
     for (int r = 0; r < 6; ++r) s.Sinv[col][r] = x[r];
@@ -285,63 +223,26 @@ static void dynamics(Env& s) {
 // ------------------------------------------------------------------ terrain contact
 // The reference's trimesh (terrain_utils.py:382-465) rebuilt per query from the packed
 // per-vertex words (height | wall shift), as lgx_env.hip terrain_contact.
-static inline v3 mesh_vertex(const uint32_t* mesh, int cols, int i, int j, int ci, int cj, float hs, float vs) {
-  const uint32_t w = mesh[(size_t)i * cols + j];
-  const float h = (float)(int16_t)(w & 0xffffu);
-  const int dx = (int)((w >> 16) & 3u) - 1, dy = (int)((w >> 18) & 3u) - 1;
-  return V((float)(i - ci + dx) * hs, (float)(j - cj + dy) * hs, h * vs);
-}
-static v3 closest_on_triangle(v3 p, v3 a, v3 b, v3 c) {  // Ericson 5.1.5
-  const v3 ab = b - a, ac = c - a, ap = p - a;
-  const float d1 = dot(ab, ap), d2 = dot(ac, ap);
-  if (d1 <= 0.f && d2 <= 0.f) return a;
-  const v3 bp = p - b;
-  const float d3 = dot(ab, bp), d4 = dot(ac, bp);
-  if (d3 >= 0.f && d4 <= d3) return b;
-  const float vc = d1 * d4 - d3 * d2;
-  if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) return a + ab * (d1 / fmaxf(d1 - d3, 1e-30f));
-  const v3 cp = p - c;
-  const float d5 = dot(ab, cp), d6 = dot(ac, cp);
-  if (d6 >= 0.f && d5 <= d6) return c;
-  const float vb = d5 * d2 - d1 * d6;
-  if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) return a + ac * (d2 / fmaxf(d2 - d6, 1e-30f));
-  const float va = d3 * d6 - d5 * d4;
-  if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f)
-    return b + (c - b) * ((d4 - d3) / fmaxf((d4 - d3) + (d5 - d6), 1e-30f));
-  const float inv = 1.0f / fmaxf(va + vb + vc, 1e-30f);
-  return a + ab * (vb * inv) + ac * (vc * inv);
-}
-static bool height_in_triangle(v3 p, v3 a, v3 b, v3 c, float& z) {
-  const float e1x = b.x - a.x, e1y = b.y - a.y, e2x = c.x - a.x, e2y = c.y - a.y;
-  const float det = e1x * e2y - e1y * e2x;
-  if (fabsf(det) < 1e-10f) return false;
-  const float px = p.x - a.x, py = p.y - a.y;
-  const float u = (px * e2y - py * e2x) / det, v = (e1x * py - e1y * px) / det;
-  const float eps = -1e-6f;
-  if (u < eps || v < eps || u + v > 1.0f - eps) return false;
-  z = a.z + u * (b.z - a.z) + v * (c.z - a.z);
-  return true;
-}
 // penetration depth (> 0 overlapping) and unit normal (terrain -> sphere) at x, radius r
-static float terrain_contact(const lgx_task_params* P, const lgx_buffers* B, v3 x, float r, v3& n) {
+static float terrain_contact(const lgx_task_params* P, const lgx_buffers* B, f3 x, float r, f3& n) {
   const float hs = P->horizontal_scale, vs = P->vertical_scale;
   const int rows = P->hf_rows, cols = P->hf_cols;
   const float gx = x.x + P->border_size, gy = x.y + P->border_size;
   const int ci = (int)floorf(gx / hs), cj = (int)floorf(gy / hs);
-  const v3 p = V(gx - (float)ci * hs, gy - (float)cj * hs, x.z);
+  const f3 p = mk(gx - (float)ci * hs, gy - (float)cj * hs, x.z);
   const int i0 = std::max(ci + (int)ceilf((p.x - r) / hs) - 2, 0), i1 = std::min(ci + (int)floorf((p.x + r) / hs) + 1, rows - 2);
   const int j0 = std::max(cj + (int)ceilf((p.y - r) / hs) - 2, 0), j1 = std::min(cj + (int)floorf((p.y + r) / hs) + 1, cols - 2);
   float best = 3.0e38f, zs = -3.0e38f;
-  v3 q = V(0.f, 0.f, -3.0e38f), fn = V(0.f, 0.f, 1.f);
+  f3 q = mk(0.f, 0.f, -3.0e38f), fn = mk(0.f, 0.f, 1.f);
   for (int i = i0; i <= i1; ++i)
     for (int j = j0; j <= j1; ++j) {
-      const v3 v00 = mesh_vertex(B->terrain_mesh, cols, i, j, ci, cj, hs, vs);
-      const v3 v01 = mesh_vertex(B->terrain_mesh, cols, i, j + 1, ci, cj, hs, vs);
-      const v3 v10 = mesh_vertex(B->terrain_mesh, cols, i + 1, j, ci, cj, hs, vs);
-      const v3 v11 = mesh_vertex(B->terrain_mesh, cols, i + 1, j + 1, ci, cj, hs, vs);
+      const f3 v00 = mesh_vertex(B->terrain_mesh, cols, i, j, ci, cj, hs, vs);
+      const f3 v01 = mesh_vertex(B->terrain_mesh, cols, i, j + 1, ci, cj, hs, vs);
+      const f3 v10 = mesh_vertex(B->terrain_mesh, cols, i + 1, j, ci, cj, hs, vs);
+      const f3 v11 = mesh_vertex(B->terrain_mesh, cols, i + 1, j + 1, ci, cj, hs, vs);
       for (int t = 0; t < 2; ++t) {
-        const v3 a = v00, b = t == 0 ? v11 : v10, c = t == 0 ? v01 : v11;
-        const v3 cp = closest_on_triangle(p, a, b, c), d = p - cp;
+        const f3 a = v00, b = t == 0 ? v11 : v10, c = t == 0 ? v01 : v11;
+        const f3 cp = closest_on_triangle(p, a, b, c), d = p - cp;
         const float d2 = dot(d, d);
         if (d2 < best) { best = d2; q = cp; fn = cross(b - a, c - a); }
         float z;
@@ -349,7 +250,7 @@ static float terrain_contact(const lgx_task_params* P, const lgx_buffers* B, v3 
       }
     }
   if (best >= 3.0e38f) {
-    n = V(0.f, 0.f, 1.f);
+    n = mk(0.f, 0.f, 1.f);
     return -3.0e38f;
   }
   const float dist = sqrtf(best);
@@ -357,11 +258,12 @@ static float terrain_contact(const lgx_task_params* P, const lgx_buffers* B, v3 
   n = dist > 1e-6f ? (p - q) * ((below ? -1.0f : 1.0f) / dist) : fn * (1.0f / sqrtf(fmaxf(dot(fn, fn), 1e-30f)));
   return below ? r + dist : r - dist;
 }
-static void tangents(v3 n, v3& t1, v3& t2) {
-  v3 a = V(n.z, 0.f, -n.x);
+// not shared with the kernel's contact_tangents: this one divides by sqrtf(l2), the kernel uses rsqrtf(l2)
+static void tangents(f3 n, f3& t1, f3& t2) {
+  f3 a = mk(n.z, 0.f, -n.x);
   float l2 = a.x * a.x + a.z * a.z;
   if (l2 < 1e-8f) {
-    a = V(0.f, n.z, -n.y);
+    a = mk(0.f, n.z, -n.y);
     l2 = a.y * a.y + a.z * a.z;
   }
   t1 = a * (1.0f / sqrtf(l2));
@@ -444,7 +346,7 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
   for (int j = 0; j < NJ; ++j) {
     const int l = j / 3, a = j % 3;
     const float* Di = s.Dinv[l];
-    float bot = sym3_at(Di, a, 0) * fj[3 * l] + sym3_at(Di, a, 1) * fj[3 * l + 1] + sym3_at(Di, a, 2) * fj[3 * l + 2];
+    float bot = sym3(Di, a, 0) * fj[3 * l] + sym3(Di, a, 1) * fj[3 * l + 1] + sym3(Di, a, 2) * fj[3 * l + 2];
     for (int r = 0; r < 6; ++r) bot -= s.X[j][r] * zb[r];
     s.us[6 + j] = s.thd[j] + dt * bot;
   }
@@ -468,14 +370,14 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
   }
   s.nlim = n;
   int nc = 0;
-  const v3 p0 = L3(s.lk[0].P);
+  const f3 p0 = ld3(s.lk[0].P);
   for (int c = 0; c < M->num_candidates && nc < MAXC; ++c) {
     const int ck = M->cand_link[c];
     const Link& lc = s.lk[ck];
-    v3 xc = L3(lc.P) + rot(lc.R, L3(M->cand_pos[c]));
+    f3 xc = ld3(lc.P) + mv(lc.R, ld3(M->cand_pos[c]));
     const float r = M->cand_radius[c];
     float depth;
-    v3 dn = V(0, 0, 1), d1 = V(1, 0, 0), d2 = V(0, 1, 0);
+    f3 dn = mk(0, 0, 1), d1 = mk(1, 0, 0), d2 = mk(0, 1, 0);
     if (!terrain) {
       depth = r - xc.z;
       xc.z -= r;
@@ -485,13 +387,13 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
       tangents(dn, d1, d2);
     }
     if (!(depth > -P->contact_margin)) continue;
-    S3(s.cn[nc], dn);
+    st3(s.cn[nc], dn);
     const int leg = ck > 0 ? (ck - 1) / 3 : -1, pos = ck > 0 ? (ck - 1) % 3 : -1;
     const int kl = ck > 0 ? 1 + 3 * leg : 1;
-    const v3 a0 = L3(s.lk[kl].ax), a1 = L3(s.lk[kl + 1].ax), a2 = L3(s.lk[kl + 2].ax);
-    const v3 r0 = xc - L3(s.lk[kl].P), r1 = xc - L3(s.lk[kl + 1].P), r2 = xc - L3(s.lk[kl + 2].P), rb = xc - p0;
+    const f3 a0 = ld3(s.lk[kl].ax), a1 = ld3(s.lk[kl + 1].ax), a2 = ld3(s.lk[kl + 2].ax);
+    const f3 r0 = xc - ld3(s.lk[kl].P), r1 = xc - ld3(s.lk[kl + 1].P), r2 = xc - ld3(s.lk[kl + 2].P), rb = xc - p0;
     for (int t = 0; t < 3; ++t) {
-      const v3 d = t == 0 ? dn : (t == 1 ? d1 : d2), ang = cross(rb, d);
+      const f3 d = t == 0 ? dn : (t == 1 ? d1 : d2), ang = cross(rb, d);
       float* jr = s.J[n];
       jr[0] = d.x; jr[1] = d.y; jr[2] = d.z; jr[3] = ang.x; jr[4] = ang.y; jr[5] = ang.z;
       jr[6] = pos >= 0 ? dot(a0, cross(r0, d)) : 0.f;
@@ -606,10 +508,10 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
       if (!terrain) {
         f[2] += lam[r]; f[0] += lam[r + 1]; f[1] += lam[r + 2];
       } else {
-        v3 t1, t2;
-        const v3 nrm = L3(s.cn[c]);
+        f3 t1, t2;
+        const f3 nrm = ld3(s.cn[c]);
         tangents(nrm, t1, t2);
-        const v3 fc = nrm * lam[r] + t1 * lam[r + 1] + t2 * lam[r + 2];
+        const f3 fc = nrm * lam[r] + t1 * lam[r + 1] + t2 * lam[r + 2];
         f[0] += fc.x; f[1] += fc.y; f[2] += fc.z;
       }
     }
@@ -617,7 +519,7 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
       for (int i = 0; i < 3; ++i) s.cf[b][i] = s.cf[b][i] / dt;
   }
   // semi-implicit Euler
-  const v3 wv = V(s.up[3], s.up[4], s.up[5]);
+  const f3 wv = mk(s.up[3], s.up[4], s.up[5]);
   for (int i = 0; i < 3; ++i) s.pb[i] += dt * s.up[i];
   const float wn = sqrtf(dot(wv, wv)), ang = wn * dt;
   float dq[4];
@@ -642,91 +544,15 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
   }
 }
 
-// ------------------------------------------------------------------ post-physics helpers
-// (isaacgym torch_utils / legged_gym math, fp32, the reference's op order)
-static void quat_rotate_inverse(const float* q, const float* v, float* out) {
-  const float w = q[3], sc = 2.0f * (w * w) - 1.0f;
-  const float cx = q[1] * v[2] - q[2] * v[1], cy = q[2] * v[0] - q[0] * v[2], cz = q[0] * v[1] - q[1] * v[0];
-  const float d = q[0] * v[0] + q[1] * v[1] + q[2] * v[2];
-  out[0] = v[0] * sc - cx * w * 2.0f + q[0] * d * 2.0f;
-  out[1] = v[1] * sc - cy * w * 2.0f + q[1] * d * 2.0f;
-  out[2] = v[2] * sc - cz * w * 2.0f + q[2] * d * 2.0f;
-}
-static void quat_apply(const float* q, const float* b, float* out) {
-  const float t0 = (q[1] * b[2] - q[2] * b[1]) * 2.0f, t1 = (q[2] * b[0] - q[0] * b[2]) * 2.0f,
-              t2 = (q[0] * b[1] - q[1] * b[0]) * 2.0f;
-  out[0] = b[0] + q[3] * t0 + (q[1] * t2 - q[2] * t1);
-  out[1] = b[1] + q[3] * t1 + (q[2] * t0 - q[0] * t2);
-  out[2] = b[2] + q[3] * t2 + (q[0] * t1 - q[1] * t0);
-}
-static float torch_rem(float a, float b) {
-  float m = fmodf(a, b);
-  if (m != 0.0f && ((m < 0.0f) != (b < 0.0f))) m += b;
-  return m;
-}
-static float wrap_pi(float a) {
-  const float two_pi = 6.283185307179586f, pi = 3.141592653589793f;
-  float m = torch_rem(a, two_pi);
-  m -= two_pi * (float)(m > pi);
-  return m;
-}
-static inline float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
-static inline float sqr(float x) { return x * x; }
-static inline float len3(float a, float b, float c) { return sqrtf(a * a + b * b + c * c); }
-static inline float len2(float a, float b) { return sqrtf(a * a + b * b); }
-static inline float urange(float lo, float hi, float u) { return (float)((double)hi - (double)lo) * u + lo; }
-// with the reference's Python-float (double) bounds (lgx_buffers.command_ranges)
-static inline float urange_d(double lo, double hi, float u) { return (float)(hi - lo) * u + (float)lo; }
-
-static int rng_blocks(const lgx_task_params* P) { return 9 + (P->num_proprio + 3) / 4; }
+// ------------------------------------------------------------------ post-physics
+// (the helpers, command resampling and reward terms are lgx_env_common.h's)
 static void fill_uniforms(Env& s, const lgx_task_params* P, uint64_t seed, uint32_t gid, uint64_t step,
                           uint32_t stream) {
   for (int b = 0; b < rng_blocks(P); ++b) {
     uint32_t o[4];
-    philox(gid, (uint32_t)step, (uint32_t)b | (stream << 16), (uint32_t)(step >> 32), (uint32_t)seed,
-           (uint32_t)(seed >> 32), o);
-    for (int i = 0; i < 4; ++i) s.U[4 * b + i] = unit(o[i]);
-  }
-}
-
-// Go2Robot._resample_commands go2.py:413-464 / LeggedRobot legged_robot.py:406-437
-// R: lgx_buffers.command_ranges (mutable, double [8]) or NULL (the params' ranges)
-static void resample_commands(const lgx_task_params* P, const double* R, float* cmd, const float* U, int slot0,
-                              const float* quat) {
-  if (P->has_user_command) {
-    for (int i = 0; i < 4; ++i) cmd[i] = P->user_command[i];
-    return;
-  }
-  if (R) {
-    cmd[0] = urange_d(R[0], R[1], U[slot0 + 0]);
-    cmd[1] = urange_d(R[2], R[3], U[slot0 + 1]);
-    if (P->heading_command)
-      cmd[3] = urange_d(R[6], R[7], U[slot0 + 2]);
-    else
-      cmd[2] = urange_d(R[4], R[5], U[slot0 + 2]);
-  } else {
-    cmd[0] = urange(P->cmd_lin_vel_x[0], P->cmd_lin_vel_x[1], U[slot0 + 0]);
-    cmd[1] = urange(P->cmd_lin_vel_y[0], P->cmd_lin_vel_y[1], U[slot0 + 1]);
-    if (P->heading_command)
-      cmd[3] = urange(P->cmd_heading[0], P->cmd_heading[1], U[slot0 + 2]);
-    else
-      cmd[2] = urange(P->cmd_ang_vel_yaw[0], P->cmd_ang_vel_yaw[1], U[slot0 + 2]);
-  }
-  const float keep = (float)(len2(cmd[0], cmd[1]) > 0.2f);
-  cmd[0] = cmd[0] * keep;
-  cmd[1] = cmd[1] * keep;
-  if (P->zero_command && U[slot0 + 3] < P->zero_command_prob) {
-    if (P->task_kind == LGX_TASK_GO2) {
-      cmd[0] = cmd[0] * 0.0f; cmd[1] = cmd[1] * 0.0f; cmd[2] = cmd[2] * 0.0f;
-      if (P->heading_command) {
-        const float fwd[3] = {1.f, 0.f, 0.f};
-        float f[3];
-        quat_apply(quat, fwd, f);
-        cmd[3] = atan2f(f[1], f[0]);
-      }
-    } else {
-      for (int i = 0; i < 4; ++i) cmd[i] = cmd[i] * 0.0f;
-    }
+    philox4x32_10(gid, (uint32_t)step, (uint32_t)b | (stream << 16), (uint32_t)(step >> 32), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), o);
+    for (int i = 0; i < 4; ++i) s.U[4 * b + i] = u01(o[i]);
   }
 }
 
@@ -735,33 +561,10 @@ static void resample_commands(const lgx_task_params* P, const double* R, float* 
 static void reset_env(const lgx_task_params* P, const lgx_buffers* B, Env& s, int e, bool zero_carried, float* stats) {
   const int D = P->num_dof;
   const float* U = s.U;
-  float* root = s.root;
-  if (P->curriculum && B->terrain_levels) {  // legged_robot.py:543-574
-    const float dist = len2(root[0] - B->env_origins[e * 3 + 0], root[1] - B->env_origins[e * 3 + 1]);
-    const int up = dist > P->terrain_length * P->promote_threshold;
-    const int down = dist < len2(s.cmd[0], s.cmd[1]) * P->max_episode_length_s * P->demote_threshold;
-    int64_t lvl = B->terrain_levels[e] + up - down;
-    if (lvl >= P->max_terrain_level) {
-      lvl = (int64_t)(U[S_TERR] * (float)P->max_terrain_level);
-      if (lvl >= P->max_terrain_level) lvl = P->max_terrain_level - 1;
-    } else if (lvl < 0) {
-      lvl = 0;
-    }
-    B->terrain_levels[e] = lvl;
-    const float* o = B->terrain_origins + ((size_t)lvl * P->num_terrain_cols + B->terrain_types[e]) * 3;
-    for (int i = 0; i < 3; ++i) B->env_origins[e * 3 + i] = o[i];
-  }
-  for (int i = 0; i < 13; ++i) root[i] = P->base_init_state[i];  // legged_robot.py:509-532
-  for (int i = 0; i < 3; ++i) root[i] = root[i] + B->env_origins[e * 3 + i];
-  if (P->custom_origins) {
-    root[0] = root[0] + urange(-1.0f, 1.0f, U[S_ROOT_XY + 0]);
-    root[1] = root[1] + urange(-1.0f, 1.0f, U[S_ROOT_XY + 1]);
-  }
-  for (int i = 0; i < 6; ++i) root[7 + i] = urange(-0.5f, 0.5f, U[S_ROOT_VEL + i]);
-  resample_commands(P, B->command_ranges, s.cmd, U, S_RCMD, root + 3);
-  s.ep = 0;
+  // an env that resets is built: the terrain curriculum always applies here
+  reset_env_head(P, *B, s, U, e, true);
   for (int j = 0; j < D; ++j) {  // legged_robot.py:481-506
-    s.th[j] = P->default_dof_pos[j] + urange(0.0f, 0.9f, U[S_DOF + j]);
+    s.th[j] = P->default_dof_pos[j] + rand_range(0.0f, 0.9f, U[S_DOF + j]);
     s.thd[j] = 0.0f;
   }
   if (zero_carried) {
@@ -824,159 +627,36 @@ static void get_heights(const lgx_task_params* P, const lgx_buffers* B, Env& s) 
 }
 
 // sums over joints / height points shared by the reward terms (lgx_env.hip joint_sums)
-enum JSum { J_ACTION_RATE, J_DELTA_TORQUES, J_DOF_ACC, J_DOF_ERROR, J_DOF_POS_LIMITS, J_DOF_VEL, J_DOF_VEL_LIMITS,
-            J_STAND_ABS, J_TORQUE_LIMITS, J_TORQUES, J_HIP_POS, J_THIGH_POS, J_CALF_POS, J_HEIGHT, J_N };
 static void joint_sums(const lgx_task_params* P, const lgx_buffers* B, Env& s, int e) {
   const int D = P->num_dof, A = P->num_actions;
   for (int k = 0; k < J_N; ++k) s.jsum[k] = 0.f;
   for (int j = 0; j < D; ++j) {
     const float la = B->last_actions[(size_t)e * A + j], lt = B->last_torques[(size_t)e * D + j];
     const float q = s.th[j], qd = s.thd[j], tau = s.tau[j], dq = q - P->default_dof_pos[j];
-    s.jsum[J_ACTION_RATE] += sqr(la - s.act[j]);
-    s.jsum[J_DELTA_TORQUES] += sqr(tau - lt);
-    s.jsum[J_DOF_ACC] += sqr((s.ldv[j] - qd) / P->dt);
-    s.jsum[J_DOF_ERROR] += sqr(dq);
+    s.jsum[J_ACTION_RATE] += sq(la - s.act[j]);
+    s.jsum[J_DELTA_TORQUES] += sq(tau - lt);
+    s.jsum[J_DOF_ACC] += sq((s.ldv[j] - qd) / P->dt);
+    s.jsum[J_DOF_ERROR] += sq(dq);
     const float lo = q - P->dof_pos_limits[j][0], hi = q - P->dof_pos_limits[j][1];
     float o = -(lo < 0.0f ? lo : 0.0f);
     o += (hi > 0.0f ? hi : 0.0f);
     s.jsum[J_DOF_POS_LIMITS] += o;
-    s.jsum[J_DOF_VEL] += sqr(qd);
-    s.jsum[J_DOF_VEL_LIMITS] += clampf(fabsf(qd) - P->dof_vel_limits[j] * P->soft_dof_vel_limit, 0.0f, 1.0f);
+    s.jsum[J_DOF_VEL] += sq(qd);
+    s.jsum[J_DOF_VEL_LIMITS] += clipf(fabsf(qd) - P->dof_vel_limits[j] * P->soft_dof_vel_limit, 0.0f, 1.0f);
     s.jsum[J_STAND_ABS] += fabsf(dq);
     const float t = fabsf(tau) - P->torque_limits[j] * P->soft_torque_limit;
     s.jsum[J_TORQUE_LIMITS] += t > 0.0f ? t : 0.0f;
-    s.jsum[J_TORQUES] += sqr(tau);
+    s.jsum[J_TORQUES] += sq(tau);
     for (int i = 0; i < 4; ++i) {
-      if (P->hip_joint_idx[i] == j) s.jsum[J_HIP_POS] += sqr(dq);
-      if (P->thigh_joint_idx[i] == j) s.jsum[J_THIGH_POS] += sqr(dq);
-      if (P->calf_joint_idx[i] == j) s.jsum[J_CALF_POS] += sqr(dq);
+      if (P->hip_joint_idx[i] == j) s.jsum[J_HIP_POS] += sq(dq);
+      if (P->thigh_joint_idx[i] == j) s.jsum[J_THIGH_POS] += sq(dq);
+      if (P->calf_joint_idx[i] == j) s.jsum[J_CALF_POS] += sq(dq);
     }
   }
   for (int i = 0; i < P->num_height_points; ++i) s.jsum[J_HEIGHT] += s.root[2] - s.heights[i];
 }
 
-static inline float fnorm(const float* c) { return len3(c[0], c[1], c[2]); }
-
-// one reward term (the `_reward_<name>` methods; ids in include/lgx.h)
-static float reward_term(const lgx_task_params* P, Env& s, int id) {
-  const float* root = s.root;
-  float* cmd = s.cmd;
-  float r = 0.0f;
-  switch (id) {
-    case LGX_REW_ACTION_RATE: return s.jsum[J_ACTION_RATE];
-    case LGX_REW_ANG_VEL_XY: return sqr(s.bav[0]) + sqr(s.bav[1]);
-    case LGX_REW_BASE_HEIGHT: return sqr(s.jsum[J_HEIGHT] / (float)P->num_height_points - P->base_height_target);
-    case LGX_REW_CALF_COLLISION:
-      for (int i = 0; i < 4; ++i) r += (float)(fnorm(s.cf[P->calf_idx[i]]) > 0.1f);
-      return r;
-    case LGX_REW_CALF_POS: return s.jsum[J_CALF_POS];
-    case LGX_REW_CALF_SYMMETRY: {
-      const int* c = P->calf_joint_idx;
-      return fabsf(s.th[c[0]] - s.th[c[1]]) + fabsf(s.th[c[2]] - s.th[c[3]]);
-    }
-    case LGX_REW_COLLISION:
-      for (int i = 0; i < P->n_penalised; ++i) r += (float)(fnorm(s.cf[P->penalised_idx[i]]) > 0.1f);
-      return r;
-    case LGX_REW_DELTA_TORQUES: return s.jsum[J_DELTA_TORQUES];
-    case LGX_REW_DOF_ACC: return s.jsum[J_DOF_ACC];
-    case LGX_REW_DOF_ERROR: return s.jsum[J_DOF_ERROR];
-    case LGX_REW_DOF_POS_LIMITS: return s.jsum[J_DOF_POS_LIMITS];
-    case LGX_REW_DOF_VEL: return s.jsum[J_DOF_VEL];
-    case LGX_REW_DOF_VEL_LIMITS: return s.jsum[J_DOF_VEL_LIMITS];
-    case LGX_REW_FEET_AIR_TIME: {  // go2.py:819-832 (updates feet_air_time)
-      float rew = 0.0f;
-      for (int f = 0; f < P->num_feet; ++f) {
-        const int cfl = (s.cf[P->feet_idx[f]][2] > 1.0f) || s.lc[f];
-        const float first = (float)((s.fat[f] > 0.0f) && cfl);
-        s.fat[f] = s.fat[f] + P->dt;
-        rew += (s.fat[f] - 0.5f) * first;
-      }
-      rew = rew * (float)(len2(cmd[0], cmd[1]) > 0.1f);
-      for (int f = 0; f < P->num_feet; ++f) {
-        const int cfl = (s.cf[P->feet_idx[f]][2] > 1.0f) || s.lc[f];
-        s.fat[f] = s.fat[f] * (float)(!cfl);
-      }
-      return rew;
-    }
-    case LGX_REW_FEET_CONTACT_FORCES:
-      for (int f = 0; f < P->num_feet; ++f) {
-        const float v = fnorm(s.cf[P->feet_idx[f]]) - P->max_contact_force;
-        r += v > 0.0f ? v : 0.0f;
-      }
-      return r;
-    case LGX_REW_HEADING_ALIGNMENT: {
-      const float fwd[3] = {1.f, 0.f, 0.f};
-      float f[3];
-      quat_apply(root + 3, fwd, f);
-      const float heading = atan2f(f[1], f[0]);
-      float desired = 0.0f;
-      if (P->heading_command) {
-        cmd[3] = wrap_pi(cmd[3]);  // the reference wraps commands[:, 3] in place (go2.py:744)
-        desired = cmd[3];
-      }
-      return sqr(wrap_pi(desired - heading)) * (float)(len3(cmd[0], cmd[1], cmd[2]) >= 0.2f);
-    }
-    case LGX_REW_HIP_POS: return s.jsum[J_HIP_POS];
-    case LGX_REW_JUMP_ZONE_FORWARD_VEL:
-      return (root[7] > 0.0f ? root[7] : 0.0f) * (float)(s.jump > 0.0f) * (float)(len3(cmd[0], cmd[1], cmd[2]) >= 0.2f);
-    case LGX_REW_JUMP_ZONE_UPWARD_VEL:
-      return (root[9] > 0.0f ? root[9] : 0.0f) * (float)(s.jump > 0.0f) * (float)(len3(cmd[0], cmd[1], cmd[2]) >= 0.2f);
-    case LGX_REW_LIN_VEL_Z: return sqr(s.blv[2]);
-    case LGX_REW_MIN_HEIGHT:
-      return clampf(P->base_height_target - root[2], 0.0f, P->base_height_target) * (float)(s.jump > 0.0f);
-    case LGX_REW_ORIENTATION: return sqr(s.pg[0]) + sqr(s.pg[1]);
-    case LGX_REW_PHASE_CONTACT_MATCH: {
-      const float thr = 2.0f * P->percent_time_on_ground - 1.0f;
-      float rew = 0.0f;
-      for (int f = 0; f < 4; ++f) {
-        const int stance = sinf(6.283185307179586f * s.ph[f]) <= thr;
-        rew += (s.contact[f] == stance) ? 0.25f : -0.25f;
-      }
-      return rew;
-    }
-    case LGX_REW_PHASE_FOOT_LIFTING: {
-      const float thr = 2.0f * P->percent_time_on_ground - 1.0f;
-      float rew = 0.0f;
-      for (int f = 0; f < 4; ++f) {
-        const int stance = sinf(6.283185307179586f * s.ph[f]) <= thr;
-        const float nh = clampf(s.feet_z[f] - s.lch[f], 0.0f, P->max_foot_height) / P->max_foot_height;
-        rew += stance ? -nh : nh;
-      }
-      return rew / 2.0f;
-    }
-    case LGX_REW_REVERSE_PENALTY: return -(root[7] < 0.0f ? root[7] : 0.0f);
-    case LGX_REW_STAND_STILL: return s.jsum[J_STAND_ABS] * (float)(len2(cmd[0], cmd[1]) < 0.1f);
-    case LGX_REW_STUMBLE_CALVES: {
-      int any = 0;
-      for (int i = 0; i < 4; ++i) {
-        const float* c = s.cf[P->calf_idx[i]];
-        any |= len2(c[0], c[1]) > 5.0f * fabsf(c[2]);
-      }
-      return (float)any;
-    }
-    case LGX_REW_STUMBLE_FEET: {
-      int any = 0;
-      for (int f = 0; f < P->num_feet; ++f) {
-        const float* c = s.cf[P->feet_idx[f]];
-        any |= len2(c[0], c[1]) > 5.0f * fabsf(c[2]);
-      }
-      return (float)any;
-    }
-    case LGX_REW_THIGH_POS: return s.jsum[J_THIGH_POS];
-    case LGX_REW_THIGH_SYMMETRY: {
-      const int* c = P->thigh_joint_idx;
-      return fabsf(s.th[c[0]] - s.th[c[1]]) + fabsf(s.th[c[2]] - s.th[c[3]]);
-    }
-    case LGX_REW_TORQUE_LIMITS: return s.jsum[J_TORQUE_LIMITS];
-    case LGX_REW_TORQUES: return s.jsum[J_TORQUES];
-    case LGX_REW_TRACKING_ANG_VEL: return expf(-sqr(cmd[2] - s.bav[2]) / P->tracking_sigma);
-    case LGX_REW_TRACKING_LIN_VEL: return expf(-(sqr(cmd[0] - s.blv[0]) + sqr(cmd[1] - s.blv[1])) / P->tracking_sigma);
-    case LGX_REW_TRACKING_PITCH: return expf(-sqr(s.pitch * 57.29577951308232f - P->pitch_deg_target) / P->tracking_sigma);
-    case LGX_REW_TRACKING_ROLL: return expf(-sqr(s.roll * 57.29577951308232f - P->roll_deg_target) / P->tracking_sigma);
-    case LGX_REW_ZERO_CMD_DOF_ERROR: return s.jsum[J_DOF_ERROR] * (float)(len3(cmd[0], cmd[1], cmd[2]) < 0.2f);
-    default: return 0.0f;
-  }
-}
+static inline float fnorm(const float* c) { return nrm3(c[0], c[1], c[2]); }
 
 // rotation matrix -> quaternion xyzw with w >= 0 (rigid-body state tensor)
 static void mat_quat(const float* Rb, float* qq) {
@@ -1007,7 +687,7 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
   const bool go2 = P->task_kind == LGX_TASK_GO2;
   float* root_g = B->root_states + (size_t)e * 13;
   for (int j = 0; j < A; ++j) {  // clip actions legged_robot.py:74-75
-    const float a = clampf(B->actions_in[(size_t)e * A + j], -P->clip_actions, P->clip_actions);
+    const float a = clipf(B->actions_in[(size_t)e * A + j], -P->clip_actions, P->clip_actions);
     s.act[j] = a;
     B->actions[(size_t)e * A + j] = a;
   }
@@ -1033,9 +713,9 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     for (int i = 0; i < 4; ++i) s.qb[i] = r0[3 + i] * nq;
     for (int i = 0; i < 3; ++i) { s.pb[i] = r0[i]; s.wb[i] = r0[10 + i]; }
     float R[9];
-    quat_R(s.qb, R);
-    const v3 rc = rot(R, V(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
-    S3(s.vo, L3(r0 + 7) - cross(L3(s.wb), rc));  // COM velocity -> origin velocity
+    quat_to_R(s.qb, R);
+    const f3 rc = mv(R, mk(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
+    st3(s.vo, ld3(r0 + 7) - cross(ld3(s.wb), rc));  // COM velocity -> origin velocity
     for (int sub = 0; sub < P->decimation; ++sub) substep(s, M, P, B, e, sub == P->decimation - 1);
     // NaN/Inf guard (the kernel's rule, lgx_env.hip): a non-finite state after the substeps
     // becomes a finite stand-in and the env is reset below
@@ -1055,9 +735,9 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
       blew = 1;
     }
     kinematics<false>(s, M, P);
-    quat_R(s.qb, R);
-    const v3 rc2 = rot(R, V(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
-    const v3 vc = L3(s.vo) + cross(L3(s.wb), rc2);
+    quat_to_R(s.qb, R);
+    const f3 rc2 = mv(R, mk(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
+    const f3 vc = ld3(s.vo) + cross(ld3(s.wb), rc2);
     float* root = s.root;
     for (int i = 0; i < 3; ++i) root[i] = s.pb[i];
     for (int i = 0; i < 4; ++i) root[3 + i] = s.qb[i];
@@ -1065,11 +745,11 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     for (int i = 0; i < 3; ++i) root[10 + i] = s.wb[i];
     for (int b = 0; b < NB; ++b) {
       const Link& lk = s.lk[M->body_link[b]];
-      const v3 off = L3(M->body_offset[b]), o = rot(lk.R, off), pos = L3(lk.P) + o;
+      const f3 off = ld3(M->body_offset[b]), o = mv(lk.R, off), pos = ld3(lk.P) + o;
       const bool primary = off.x == 0.f && off.y == 0.f && off.z == 0.f;
-      const v3 lv = L3(lk.V) + cross(L3(lk.W), primary ? (L3(lk.C) - L3(lk.P)) : o);
+      const f3 lv = ld3(lk.V) + cross(ld3(lk.W), primary ? (ld3(lk.C) - ld3(lk.P)) : o);
       float Rb[9], qq[4];
-      matmul3(lk.R, M->body_rot[b], Rb);
+      mm(lk.R, M->body_rot[b], Rb);
       mat_quat(Rb, qq);
       float* rb = B->rigid_body_states + ((size_t)e * NB + b) * 13;
       rb[0] = pos.x; rb[1] = pos.y; rb[2] = pos.z;
@@ -1095,31 +775,31 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
   const long long ep = ep_prev + 1;
   s.ep = ep;
   const float g[3] = {0.f, 0.f, -1.f};
-  quat_rotate_inverse(root + 3, root + 7, s.blv);
-  quat_rotate_inverse(root + 3, root + 10, s.bav);
-  quat_rotate_inverse(root + 3, g, s.pg);
-  s.roll = s.pitch = s.yaw = 0.f;
-  for (int f = 0; f < 4; ++f) { s.ph[f] = 0.f; s.contact[f] = 0; s.feet_z[f] = 0.f; s.lc[f] = 0; s.lch[f] = 0.f; s.fat[f] = 0.f; }
+  quat_rotate_inverse(root + 3, root + 7, s.x.blv);
+  quat_rotate_inverse(root + 3, root + 10, s.x.bav);
+  quat_rotate_inverse(root + 3, g, s.x.pg);
+  s.x.roll = s.x.pitch = s.x.yaw = 0.f;
+  for (int f = 0; f < 4; ++f) { s.x.ph[f] = 0.f; s.x.contact[f] = 0; s.x.feet_z[f] = 0.f; s.lc[f] = 0; s.lch[f] = 0.f; s.fat[f] = 0.f; }
   if (go2) {  // update_feet_states go2.py:266-328
-    const float phase = torch_rem((float)ep * P->dt, P->period) / P->period;
-    const float pfr = torch_rem(phase + P->offset_fr, 1.0f), pbl = torch_rem(phase + P->offset_bl, 1.0f);
-    const float pfl = torch_rem(phase + P->offset_fl, 1.0f), pbr = torch_rem(phase + P->offset_br, 1.0f);
-    const float msk = (len3(cmd[0], cmd[1], cmd[2]) < 0.2f) ? 0.0f : 1.0f;
-    s.ph[0] = pfl * msk; s.ph[1] = pfr * msk; s.ph[2] = pbl * msk; s.ph[3] = pbr * msk;
+    const float phase = trem((float)ep * P->dt, P->period) / P->period;
+    const float pfr = trem(phase + P->offset_fr, 1.0f), pbl = trem(phase + P->offset_bl, 1.0f);
+    const float pfl = trem(phase + P->offset_fl, 1.0f), pbr = trem(phase + P->offset_br, 1.0f);
+    const float msk = (nrm3(cmd[0], cmd[1], cmd[2]) < 0.2f) ? 0.0f : 1.0f;
+    s.x.ph[0] = pfl * msk; s.x.ph[1] = pfr * msk; s.x.ph[2] = pbl * msk; s.x.ph[3] = pbr * msk;
     for (int f = 0; f < F; ++f) {
       const int lcf = B->last_contacts[e * F + f];
       const float lch = B->last_contact_heights[e * F + f];
       const int curc = s.cf[P->feet_idx[f]][2] > 1.0f;
-      s.contact[f] = curc || lcf;
+      s.x.contact[f] = curc || lcf;
       s.lc[f] = curc;
-      s.feet_z[f] = s.rbz[P->feet_idx[f]];
-      s.lch[f] = s.contact[f] ? s.feet_z[f] : lch;
+      s.x.feet_z[f] = s.rbz[P->feet_idx[f]];
+      s.lch[f] = s.x.contact[f] ? s.x.feet_z[f] : lch;
       if (B->feet_air_time) s.fat[f] = B->feet_air_time[e * F + f];
     }
     const float qx = root[3], qy = root[4], qz = root[5], qw = root[6];  // go2.py:11-31
-    s.roll = atan2f(2.0f * (qw * qx + qy * qz), 1.0f - 2.0f * (qx * qx + qy * qy));
-    s.pitch = asinf(clampf(2.0f * (qw * qy - qz * qx), -1.0f, 1.0f));
-    s.yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
+    s.x.roll = atan2f(2.0f * (qw * qx + qy * qz), 1.0f - 2.0f * (qx * qx + qy * qy));
+    s.x.pitch = asinf(clipf(2.0f * (qw * qy - qz * qx), -1.0f, 1.0f));
+    s.x.yaw = atan2f(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
   }
   // _post_physics_step_callback go2.py:390-410
   if (ep % P->resample_interval == 0) resample_commands(P, B->command_ranges, cmd, s.U, S_CMD, root + 3);
@@ -1127,21 +807,21 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     const float fwd[3] = {1.f, 0.f, 0.f};
     float f[3];
     quat_apply(root + 3, fwd, f);
-    cmd[2] = clampf(wrap_pi(cmd[3] - atan2f(f[1], f[0])) * (go2 ? P->heading_error_gain : 0.5f), -1.0f, 1.0f);
+    cmd[2] = clipf(wrap_to_pi(cmd[3] - atan2f(f[1], f[0])) * (go2 ? P->heading_error_gain : 0.5f), -1.0f, 1.0f);
   }
   if (P->push_robots && (step % (uint64_t)P->push_interval == 0)) {
-    root[7] = urange(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 0]);
-    root[8] = urange(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 1]);
+    root[7] = rand_range(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 0]);
+    root[8] = rand_range(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 1]);
   }
   // check_termination go2.py:186-204
   int reset = 0;
   for (int i = 0; i < P->n_termination; ++i) reset |= fnorm(s.cf[P->termination_idx[i]]) > 1.0f;
   const int tout = ep > P->max_episode_length && !blew;  // a blow-up is a termination (kernel)
   reset |= tout;
-  reset |= s.pg[2] > 0.0f;
+  reset |= s.x.pg[2] > 0.0f;
   if (P->parkour) reset |= root[2] < -1.0f;
   reset |= blew;
-  s.jump = jump_prev;
+  s.x.jump = jump_prev;
   get_heights(P, B, s);
   joint_sums(P, B, s, e);
   // compute_reward legged_robot.py:216-237: the terms in the reference's (alphabetical) order
@@ -1173,14 +853,14 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
   if (go2 && P->parkour) {
     int outl = 0;
     for (int i = 0; i < P->num_height_points; ++i) outl += fabsf(s.heights[i]) > 0.1f;
-    s.jump = (float)(outl >= 8);
+    s.x.jump = (float)(outl >= 8);
   }
   for (int i = 0; i < Pp; ++i) {
     float v;
     if (go2) {
-      if (i < 3) v = s.bav[i] * P->obs_scale_ang_vel;
-      else if (i == 3) v = s.roll;
-      else if (i == 4) v = s.pitch;
+      if (i < 3) v = s.x.bav[i] * P->obs_scale_ang_vel;
+      else if (i == 3) v = s.x.roll;
+      else if (i == 4) v = s.x.pitch;
       else if (i < 8) v = s.cmd[i - 5] * P->commands_scale[i - 5];
       else if (i < 8 + D) v = (s.th[i - 8] - P->default_dof_pos[i - 8]) * P->obs_scale_dof_pos;
       else if (i < 8 + 2 * D) v = s.thd[i - 8 - D] * P->obs_scale_dof_vel;
@@ -1188,18 +868,18 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
       else {
         const int q = i - (8 + 2 * D + A);  // sin/cos of FR, FL, BL, BR
         const int leg = (q >> 1) == 0 ? 1 : ((q >> 1) == 1 ? 0 : (q >> 1));
-        const float p = 6.283185307179586f * s.ph[leg];
+        const float p = 6.283185307179586f * s.x.ph[leg];
         v = (q & 1) ? cosf(p) : sinf(p);
       }
     } else {
-      if (i < 3) v = s.blv[i] * P->obs_scale_lin_vel;
-      else if (i < 6) v = s.bav[i - 3] * P->obs_scale_ang_vel;
-      else if (i < 9) v = s.pg[i - 6];
+      if (i < 3) v = s.x.blv[i] * P->obs_scale_lin_vel;
+      else if (i < 6) v = s.x.bav[i - 3] * P->obs_scale_ang_vel;
+      else if (i < 9) v = s.x.pg[i - 6];
       else if (i < 12) v = s.cmd[i - 9] * P->commands_scale[i - 9];
       else if (i < 12 + D) v = (s.th[i - 12] - P->default_dof_pos[i - 12]) * P->obs_scale_dof_pos;
       else if (i < 12 + 2 * D) v = s.thd[i - 12 - D] * P->obs_scale_dof_vel;
       else if (i < 12 + 2 * D + A) v = s.act[i - 12 - 2 * D];
-      else v = clampf(s.root[2] - 0.5f - s.heights[i - (12 + 2 * D + A)], -1.0f, 1.0f) * P->obs_scale_height;
+      else v = clipf(s.root[2] - 0.5f - s.heights[i - (12 + 2 * D + A)], -1.0f, 1.0f) * P->obs_scale_height;
     }
     if (P->add_noise) v = v + (2.0f * s.U[S_NOISE + i] - 1.0f) * P->noise_vec[i];
     s.cur[i] = v;
@@ -1210,12 +890,12 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
   float* obs = B->obs + (size_t)e * P->num_obs;
   float* cr = B->critic ? B->critic + (size_t)e * P->num_critic : nullptr;
   for (int i = 0; i < H * Pp; ++i) {
-    const float v = clampf(s.hist[i], -co, co);
+    const float v = clipf(s.hist[i], -co, co);
     obs[i] = v;
     if (go2 && cr) cr[i] = v;
   }
   for (int i = 0; i < Pp; ++i) {
-    const float v = clampf(s.cur[i], -co, co);
+    const float v = clipf(s.cur[i], -co, co);
     obs[H * Pp + i] = v;
     if (go2 && cr) cr[H * Pp + i] = v;
   }
@@ -1227,19 +907,19 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
       else if (i == 4) v = B->friction[e];
       else if (i < 5 + D) v = s.kpm[i - 5] - 1.0f;
       else v = s.kdm[i - 5 - D] - 1.0f;
-      v = clampf(v, -co, co);
+      v = clipf(v, -co, co);
       B->priv[(size_t)e * P->num_priv + i] = v;
       if (cr) cr[NO + i] = v;
     }
     for (int i = 0; i < 3; ++i) {
-      const float v = clampf(s.blv[i] * P->obs_scale_lin_vel, -co, co);
+      const float v = clipf(s.x.blv[i] * P->obs_scale_lin_vel, -co, co);
       B->est[(size_t)e * P->num_est + i] = v;
       if (cr) cr[NO + P->num_priv + i] = v;
     }
     for (int i = 0; i < P->num_scan; ++i) {
-      const float v = clampf(s.root[2] - 0.3f - s.heights[i], -1.0f, 1.0f);
+      const float v = clipf(s.root[2] - 0.3f - s.heights[i], -1.0f, 1.0f);
       B->scan[(size_t)e * P->num_scan + i] = v;
-      if (cr) cr[NO + P->num_priv + 3 + i] = clampf(v, -co, co);
+      if (cr) cr[NO + P->num_priv + 3 + i] = clipf(v, -co, co);
     }
   }
   for (int i = 0; i < H * Pp; ++i)  // history update go2.py:570-574
@@ -1253,10 +933,10 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     B->dof_state[((size_t)e * D + j) * 2 + 1] = s.thd[j];
   }
   memcpy(B->last_root_vel + e * 6, s.root + 7, sizeof(float) * 6);
-  memcpy(B->last_base_lin_vel + e * 3, s.blv, sizeof(float) * 3);
-  if (B->base_lin_vel) memcpy(B->base_lin_vel + e * 3, s.blv, sizeof(float) * 3);
-  if (B->base_ang_vel) memcpy(B->base_ang_vel + e * 3, s.bav, sizeof(float) * 3);
-  if (B->projected_gravity) memcpy(B->projected_gravity + e * 3, s.pg, sizeof(float) * 3);
+  memcpy(B->last_base_lin_vel + e * 3, s.x.blv, sizeof(float) * 3);
+  if (B->base_lin_vel) memcpy(B->base_lin_vel + e * 3, s.x.blv, sizeof(float) * 3);
+  if (B->base_ang_vel) memcpy(B->base_ang_vel + e * 3, s.x.bav, sizeof(float) * 3);
+  if (B->projected_gravity) memcpy(B->projected_gravity + e * 3, s.x.pg, sizeof(float) * 3);
   memcpy(root_g, s.root, sizeof(float) * 13);
   memcpy(B->commands + e * 4, s.cmd, sizeof(float) * 4);
   if (go2 && !reset)
@@ -1267,7 +947,7 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     }
   B->episode_length[e] = s.ep;
   if (B->rpy_phase) {
-    const float v[8] = {s.roll, s.pitch, s.yaw, s.ph[0], s.ph[1], s.ph[2], s.ph[3], s.jump};
+    const float v[8] = {s.x.roll, s.x.pitch, s.x.yaw, s.x.ph[0], s.x.ph[1], s.x.ph[2], s.x.ph[3], s.x.jump};
     memcpy(B->rpy_phase + e * 8, v, sizeof(v));
   }
   if (B->measured_heights)
@@ -1368,51 +1048,9 @@ void command_curriculum(const lgx_task_params* P, const lgx_buffers* B, uint64_t
     for (int e = 0; e < N; ++e)
       if (B->reset[e]) { S += (double)B->curriculum_vals[e]; Cn += 1.0; }
   }
-  if (Cn <= 0.0) return;
-  const float mean = ((float)S / (float)Cn) / (float)P->max_episode_length;
-  if (!(mean > P->curriculum_threshold)) return;
-  double* R = B->command_ranges;
-  const double lo = R[0], hi = R[1], d = P->curriculum_delta;
-  const double lo_max = P->curriculum_lo_free ? lo - d : P->curriculum_lo_max;
-  const double nlo = std::min(std::max(lo - d, P->curriculum_lo_min), lo_max);  // np.clip
-  const double nhi = std::min(std::max(hi + d, 0.0), P->curriculum_hi_max);
-  const bool changed = nlo != lo || nhi != hi;
-  R[0] = nlo;
-  R[1] = nhi;
-  if (float* L = B->command_range_log) {
-    if (P->command_curriculum == 1) { L[0] = (float)nhi; L[1] = (float)nlo; L[2] = (float)R[3]; L[3] = (float)R[5]; }
-    else { L[0] = (float)nhi; L[1] = (float)R[3]; L[2] = (float)R[5]; }
-  }
-  if (!changed) return;
-  const bool go2 = P->task_kind == LGX_TASK_GO2;
-  const int Pp = P->num_proprio, H = P->history_len, c0 = go2 ? 5 : 9;
-  const float co = P->clip_obs;
-  for (int e = 0; e < N; ++e) {
-    if (!B->reset[e]) continue;
-    const uint32_t gid = (uint32_t)(P->env_id_offset + e);
-    auto uni = [&](int slot) {
-      uint32_t o[4];
-      philox(gid, (uint32_t)step, (uint32_t)(slot >> 2), (uint32_t)(step >> 32), (uint32_t)seed,
-             (uint32_t)(seed >> 32), o);
-      return unit(o[slot & 3]);
-    };
-    float U[4];
-    for (int k = 0; k < 4; ++k) U[k] = uni(S_RCMD + k);
-    float* cmd = B->commands + e * 4;
-    resample_commands(P, R, cmd, U, 0, B->root_states + (size_t)e * 13 + 3);
-    float* obs = B->obs + (size_t)e * P->num_obs;
-    float* cr = (go2 && B->critic) ? B->critic + (size_t)e * P->num_critic : nullptr;
-    float* hist = B->obs_history + (size_t)e * H * Pp;
-    for (int j = 0; j < 3; ++j) {
-      const int i = c0 + j;
-      float v = cmd[j] * P->commands_scale[j];
-      if (P->add_noise) v = v + (2.0f * uni(S_NOISE + i) - 1.0f) * P->noise_vec[i];
-      const float vc = clampf(v, -co, co);
-      obs[H * Pp + i] = vc;
-      if (cr) cr[H * Pp + i] = vc;
-      for (int t = 0; t < H; ++t) hist[t * Pp + i] = v;
-    }
-  }
+  if (!curriculum_update_ranges(P, *B, S, Cn)) return;
+  for (int e = 0; e < N; ++e)
+    if (B->reset[e]) curriculum_rewrite_env(P, *B, seed, step, e);
 }
 
 void eval_begin(const lgx_task_params* P, const lgx_eval_buffers* E) {
