@@ -1,7 +1,9 @@
-"""ctypes mirror of include/lgx.h (the C ABI of liblgx.so).
+"""ctypes mirror of include/lgx.h (the C ABI of liblgx.so): the structs, the constants and the
+function signatures, with the three tables _cbind.py describes at the end.
 
-Field order and array sizes must match the header exactly; `check_layout()` compares
-sizeof against the values the native library (and the oracle) report.
+Field order and array sizes must match the header exactly: tests/test_abi.py compares every
+field's offset and size, every constant and every parameter count with the compiled header, and a
+loaded library (`_native.lib()`; the oracle through `check_layout()`) reports its own sizeof.
 """
 import ctypes as C
 
@@ -143,13 +145,53 @@ class EvalBuffers(C.Structure):
     _fields_ = [("acc", P), ("status", P), ("cells", P), ("overflow", P), ("cell_rows", i32), ("cell_cols", i32)]
 
 
+STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buffers,
+           "lgx_eval_buffers": EvalBuffers}
+SIZEOF = {"lgx_sizeof_" + name[len("lgx_"):]: name for name in STRUCTS}  # sizeof export -> typedef
+
+CONSTANTS = {
+    "LGX_ABI_VERSION": ABI_VERSION, "LGX_MAX_DOF": MAX_DOF, "LGX_MAX_LINKS": MAX_LINKS,
+    "LGX_MAX_BODIES": MAX_BODIES, "LGX_MAX_FEET": MAX_FEET, "LGX_MAX_PROPRIO": MAX_PROPRIO,
+    "LGX_MAX_HEIGHT_POINTS": MAX_HEIGHT_POINTS, "LGX_MAX_REWARDS": MAX_REWARDS,
+    "LGX_MAX_CANDIDATES": MAX_CANDIDATES, "LGX_MAX_CONTACTS": MAX_CONTACTS, "LGX_MAX_PENALISED": MAX_PENALISED,
+    "LGX_MAX_TERMINATION": MAX_TERMINATION, "LGX_EVAL_METRICS": EVAL_METRICS, "LGX_EVAL_CELL_COLS": EVAL_CELL_COLS,
+    "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
+    "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
+    **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},
+    **{"LGX_REW_" + name.upper(): v for name, v in REWARD_IDS.items()},
+    "LGX_REW_COUNT": len(REWARD_IDS),
+}
+
+u64, cint = C.c_uint64, C.c_int
+SIGNATURES = {
+    "lgx_abi_version": (i32, ()),
+    **{name: (C.c_int64, ()) for name in SIZEOF},
+    "lgx_create": (cint, (P, P, i32, C.POINTER(P))),
+    "lgx_bind": (cint, (P, P)),
+    "lgx_step": (cint, (P, u64, u64, P)),
+    "lgx_step_dev": (cint, (P, u64, P, P)),
+    "lgx_post_physics": (cint, (P, u64, u64, P)),
+    "lgx_physics": (cint, (P, P)),
+    "lgx_reset_envs": (cint, (P, P, u64, u64, P)),
+    "lgx_episode_extras": (cint, (P, P, P, P, P, P)),
+    "lgx_command_curriculum": (cint, (P, u64, u64, P, P, P)),
+    "lgx_set_envs_per_wave": (cint, (P, i32)),
+    "lgx_eval_begin": (cint, (P, P, P)),
+    "lgx_eval_accumulate": (cint, (P, P, P)),
+    "lgx_eval_reduce": (cint, (P, P, P)),
+    "lgx_last_error": (C.c_char_p, (P,)),
+    "lgx_destroy": (None, (P,)),
+}
+
+
 def check_layout(lib, prefix):
-    """Compare ctypes sizes with the native library's sizeof() exports."""
+    """Compare ctypes sizes with the `<prefix><name>` sizeof exports a library has (the oracle's
+    `oracle_sizeof_{model,params,buffers}`; liblgx.so's own are checked when `_native.lib()` loads it)."""
     for name, cls in (("model", Model), ("params", TaskParams), ("buffers", Buffers), ("eval_buffers", EvalBuffers)):
-        fn = getattr(lib, f"{prefix}{name}", None)
-        if fn is None:
+        try:
+            fn = C.CFUNCTYPE(C.c_int64)((prefix + name, lib))
+        except AttributeError:
             continue
-        fn.restype = C.c_int64
         n = fn()
         if n != C.sizeof(cls):
             raise RuntimeError(f"ABI layout mismatch for {name}: native {n} vs ctypes {C.sizeof(cls)}")

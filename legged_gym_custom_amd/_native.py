@@ -5,7 +5,7 @@ host memory) — chosen explicitly by --sim_device=cpu, never as a fallback."""
 import ctypes as C
 import os
 
-from . import _abi
+from . import _abi, _cbind
 
 LIB_PATH = os.environ.get("LGX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "liblgx.so")
 _lib = None
@@ -17,41 +17,13 @@ class LgxError(RuntimeError):
 
 def lib():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise LgxError(f"liblgx.so not built ({LIB_PATH}); run `python -m legged_gym_custom_amd.build_native`")
-    L = C.CDLL(LIB_PATH)
-    vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int32
-    L.lgx_abi_version.restype = i32
-    L.lgx_create.argtypes = [vp, vp, i32, C.POINTER(vp)]
-    L.lgx_create.restype = C.c_int
-    L.lgx_bind.argtypes = [vp, vp]
-    L.lgx_step.argtypes = [vp, u64, u64, vp]
-    L.lgx_step_dev.argtypes = [vp, u64, vp, vp]
-    L.lgx_post_physics.argtypes = [vp, u64, u64, vp]
-    L.lgx_physics.argtypes = [vp, vp]
-    L.lgx_reset_envs.argtypes = [vp, vp, u64, u64, vp]
-    L.lgx_episode_extras.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.lgx_command_curriculum.argtypes = [vp, u64, u64, vp, vp, vp]
-    L.lgx_set_envs_per_wave.argtypes = [vp, i32]
-    for fn in (L.lgx_eval_begin, L.lgx_eval_accumulate, L.lgx_eval_reduce):
-        fn.argtypes = [vp, vp, vp]
-    L.lgx_last_error.argtypes = [vp]
-    L.lgx_last_error.restype = C.c_char_p
-    L.lgx_destroy.argtypes = [vp]
-    L.lgx_destroy.restype = None
-    if L.lgx_abi_version() != _abi.ABI_VERSION:
-        raise LgxError("liblgx ABI version mismatch; rebuild")
-    _abi.check_layout(L, "lgx_sizeof_")
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _cbind.load(LIB_PATH, "liblgx", _abi.SIGNATURES, _abi.STRUCTS, ("lgx_abi_version", _abi.ABI_VERSION),
+                           _abi.SIZEOF, LgxError)
+    return _lib
 
 
-EXPORTED = ["lgx_abi_version", "lgx_sizeof_model", "lgx_sizeof_task_params", "lgx_sizeof_buffers", "lgx_create",
-            "lgx_bind", "lgx_step", "lgx_step_dev", "lgx_post_physics", "lgx_physics", "lgx_reset_envs", "lgx_last_error",
-            "lgx_destroy", "lgx_episode_extras", "lgx_command_curriculum", "lgx_set_envs_per_wave", "lgx_eval_begin",
-            "lgx_eval_accumulate", "lgx_eval_reduce"]
+EXPORTED = list(_abi.SIGNATURES)
 
 
 class NativeEnv:

@@ -889,8 +889,8 @@ class PPO:
         if not hip_mlp.adaptation_train_supported(mod, ac.num_proprio):
             return False  # outside lgx_adaptation_train's tiling
         why = None
-        if adapt.numel() > 65536:
-            why = "the adaptation segment exceeds lgx_clip_adam's one-block limit (65536)"
+        if adapt.numel() > hip_mlp.CLIP_ADAM_MAX:
+            why = f"the adaptation segment exceeds lgx_clip_adam's one-block limit ({hip_mlp.CLIP_ADAM_MAX})"
         else:
             off = adapt.data_ptr()
             for p in hip_mlp.adaptation_param_order(mod):

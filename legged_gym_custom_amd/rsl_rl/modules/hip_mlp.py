@@ -17,29 +17,18 @@ import os
 import torch
 import torch.nn as nn
 
-_LIB_PATH = os.environ.get("LGX_MLP_LIB") or os.path.join(
-    os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "lib", "liblgx_mlp.so")
-_lib = None
-ABI_VERSION = 11
-EPI_BIAS, EPI_ELU, EPI_DELU, EPI_ACCUM = 1, 2, 4, 8
-EXPORTED = ["lgx_mlp_abi_version", "lgx_mlp_sizeof_gemm_args", "lgx_mlp_pick_split", "lgx_gemm",
-            "lgx_mlp_last_error", "lgx_adam_step", "lgx_ppo_head_forward", "lgx_ppo_head_backward",
-            "lgx_copy_batch", "lgx_act_head", "lgx_store_transition", "lgx_splitk_reduce_batch",
-            "lgx_aux_loss_forward", "lgx_aux_loss_backward", "lgx_ppo_tail", "lgx_gemm_group",
-            "lgx_mlp_pick_split_group", "lgx_gae", "lgx_normalize_advantages",
-            "lgx_gather_rows", "lgx_transpose_batch", "lgx_loss_heads_forward", "lgx_loss_heads_backward",
-            "lgx_track_episodes", "lgx_chain", "lgx_adaptation_forward", "lgx_loss_heads_fused",
-            "lgx_loss_heads_tail", "lgx_adaptation_train", "lgx_clip_adam", "lgx_post_step"]
-TAIL_MAX_LOSSES = 8
-TAIL_S8_MAX = 32
+# the lgx_mlp.h mirror and loader (legged_gym_custom_amd/_abi_mlp.py), under the names callers use here
+from legged_gym_custom_amd._abi_mlp import (  # noqa: F401
+    ABI_VERSION, CHAIN_MAX, CHAIN_MAXL, CHAIN_MAXW, CLIP_ADAM_MAX, COPY_MAX, EPI_ACCUM, EPI_BIAS, EPI_DELU, EPI_ELU,
+    EXPORTED, GROUP_MAX, HEADS_TAIL_ROWS, SPLITK_MAX, TAIL_MAX_LOSSES, TAIL_S8_MAX, TRANSPOSE_MAX,
+    ActHeadArgs, AdaptArgs, AdaptTrainArgs, AuxArgs, ChainDesc, ChainLayer, CopyDesc, GaeArgs, GemmArgs, HeadArgs,
+    HeadsS8Args, HeadsTailArgs, SplitkDesc, TailArgs, TailS8Seg, TrackArgs, TransitionArgs, TransposeDesc,
+    MlpLibError, lib, check as _check)
+from legged_gym_custom_amd._cbind import ptr as _ptr, stream as _stream
+
 # dev knob: LGX_TAIL_S8=0 keeps the per-minibatch weight split launch (the optimizer tail then
 # writes no S8 copies)
 TAIL_S8 = os.environ.get("LGX_TAIL_S8", "1") != "0"
-COPY_MAX = 16
-SPLITK_MAX = 24
-GROUP_MAX = 20
-TRANSPOSE_MAX = 24
-CHAIN_MAX, CHAIN_MAXL, CHAIN_MAXW = 4, 3, 256
 # lgx_chain serves batches of at most CHAIN_ROWS rows (the rollout's 4096-row act pass): at the
 # update's 24,576 rows one grouped launch per depth measured faster (profiles/r03_chain.txt).
 # Dev knobs: LGX_CHAIN=0 (never chain), LGX_CHAIN_ROWS (the row limit).
@@ -49,146 +38,11 @@ USE_ADAPT_FUSED = os.environ.get("LGX_ADAPT_FUSED", "1") != "0"
 CHAIN_ROWS = int(os.environ.get("LGX_CHAIN_ROWS", "8192"))
 
 
-class GemmArgs(C.Structure):
-    """Mirror of lgx_gemm_args (include/lgx_mlp.h)."""
-    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("a_kcontig", C.c_int32),
-                ("B", C.c_void_p), ("ldb", C.c_int64), ("b_kcontig", C.c_int32),
-                ("C", C.c_void_p), ("ldc", C.c_int64),
-                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("epilogue", C.c_int32),
-                ("bias", C.c_void_p), ("act", C.c_void_p), ("ld_act", C.c_int64),
-                ("split_k", C.c_int32), ("workspace", C.c_void_p), ("colsum", C.c_void_p),
-                ("colsum_ws", C.c_void_p), ("defer_reduce", C.c_int32)]
-
-
-class SplitkDesc(C.Structure):
-    """Mirror of lgx_splitk_desc."""
-    _fields_ = [("ws", C.c_void_p), ("colsum_ws", C.c_void_p), ("C", C.c_void_p), ("ldc", C.c_int64),
-                ("colsum", C.c_void_p), ("M", C.c_int32), ("N", C.c_int32), ("split", C.c_int32),
-                ("epilogue", C.c_int32)]
-
-
-class HeadArgs(C.Structure):
-    """Mirror of lgx_ppo_head_args (include/lgx_mlp.h)."""
-    _fields_ = [(n, C.c_void_p) for n in ("mu", "value", "std", "actions", "old_logp", "adv", "target_values",
-                                          "returns", "old_mu", "old_sigma")] + \
-               [("B", C.c_int32), ("A", C.c_int32), ("clip", C.c_float), ("clipped_value", C.c_int32),
-                ("out", C.c_void_p), ("g", C.c_void_p), ("dmu", C.c_void_p), ("dvalue", C.c_void_p),
-                ("dstd", C.c_void_p), ("ws", C.c_void_p), ("counter", C.c_void_p), ("kl_dst", C.c_void_p),
-                ("accumulate_dstd", C.c_int32)]
-
-
-class AuxArgs(C.Structure):
-    """Mirror of lgx_aux_loss_args."""
-    _fields_ = [("p", C.c_void_p), ("a", C.c_void_p), ("L", C.c_int32), ("e", C.c_void_p), ("t", C.c_void_p),
-                ("E", C.c_int32), ("B", C.c_int32), ("out", C.c_void_p), ("g", C.c_void_p), ("dp", C.c_void_p),
-                ("de", C.c_void_p), ("ws", C.c_void_p), ("counter", C.c_void_p), ("ld_p", C.c_int64)]
-
-
-class HeadsS8Args(C.Structure):
-    """Mirror of lgx_heads_s8_args (pitches in S8 elements)."""
-    _fields_ = [("dmu_s8", C.c_void_p), ("ld_dmu", C.c_int64), ("dmu_cs", C.c_void_p),
-                ("dvalue_s8", C.c_void_p), ("ld_dvalue", C.c_int64), ("dvalue_cs", C.c_void_p),
-                ("de_s8", C.c_void_p), ("ld_de", C.c_int64), ("de_cs", C.c_void_p),
-                ("decisions_in", C.c_void_p), ("decisions_out", C.c_void_p)]
-
-
-class HeadsTailArgs(C.Structure):
-    """Mirror of lgx_heads_tail_args (ABI 9: the actor's / critic's last layers fused around the
-    PPO head; pitches in S8 elements)."""
-    _fields_ = [("y", C.c_void_p), ("ld_y", C.c_int64), ("W", C.c_void_p), ("b", C.c_void_p),
-                ("dy", C.c_void_p), ("ld_dy", C.c_int64), ("dy_cs", C.c_void_p),
-                ("yc", C.c_void_p), ("ld_yc", C.c_int64), ("Wc", C.c_void_p), ("bc", C.c_void_p),
-                ("dyc", C.c_void_p), ("ld_dyc", C.c_int64), ("dyc_cs", C.c_void_p),
-                ("mu_out", C.c_void_p), ("value_out", C.c_void_p), ("H", C.c_int32), ("Hc", C.c_int32)]
-
-
-HEADS_TAIL_ROWS = 32  # LGX_HEADS_TAIL_ROWS: rows of one column-sum partial of lgx_loss_heads_tail
-
-
-class TailArgs(C.Structure):
-    """Mirror of lgx_ppo_tail_args."""
-    _fields_ = [(n, C.c_void_p) for n in ("grads", "params", "exp_avg", "exp_avg_sq")] + \
-               [(n, C.c_int64) for n in ("main_lo", "main_hi", "est_lo", "est_hi", "adapt_lo", "adapt_hi",
-                                         "kl_index")] + \
-               [(n, C.c_float) for n in ("max_norm", "b1_main", "b2_main", "eps_main", "b1_est", "b2_est", "eps_est",
-                                         "est_lr")] + \
-               [("desired_kl", C.c_double), ("lr64", C.c_void_p), ("lr32", C.c_void_p), ("step_main", C.c_void_p),
-                ("step_est", C.c_void_p), ("loss_ptrs", C.c_void_p * TAIL_MAX_LOSSES), ("sums", C.c_void_p),
-                ("nloss", C.c_int32), ("ws", C.c_void_p), ("counter", C.c_void_p), ("s8", C.c_void_p),
-                ("n_s8", C.c_int32)]
-
-
-class TailS8Seg(C.Structure):
-    """Mirror of lgx_tail_s8_seg."""
-    _fields_ = [("p0", C.c_int64), ("N", C.c_int32), ("K", C.c_int32), ("c0", C.c_int32), ("w", C.c_int32),
-                ("dst", C.c_void_p), ("ld", C.c_int32), ("packed", C.c_int32)]
-
-
 def tail_s8_table(segs):
     """[(p0, N, K, c0, w, dst, ld, packed)] -> the host table lgx_ppo_tail reads (sorted by p0,
     a weight's entries consecutive)."""
     segs = sorted(segs, key=lambda q: q[0])
     return (TailS8Seg * len(segs))(*[TailS8Seg(*q) for q in segs])
-
-
-class CopyDesc(C.Structure):
-    """Mirror of lgx_copy_desc."""
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("nbytes", C.c_int64), ("dst_stride", C.c_int64)]
-
-
-class ActHeadArgs(C.Structure):
-    """Mirror of lgx_act_head_args."""
-    _fields_ = [(n, C.c_void_p) for n in ("mean", "std", "eps", "actions", "mu", "sigma", "logp")] + \
-               [("B", C.c_int32), ("A", C.c_int32), ("actions_copy", C.c_void_p), ("step_dev", C.c_void_p),
-                ("seed", C.c_uint64), ("env_offset", C.c_int64)]
-
-
-class TransitionArgs(C.Structure):
-    """Mirror of lgx_transition_args."""
-    _fields_ = [(n, C.c_void_p) for n in ("rewards", "dones", "time_outs", "values", "rewards_out", "dones_out",
-                                          "values_out")] + [("gamma", C.c_float), ("B", C.c_int32)]
-
-
-class TrackArgs(C.Structure):
-    """Mirror of lgx_track_args."""
-    _fields_ = [(n, C.c_void_p) for n in ("rewards", "dones", "cur_rew", "cur_len", "rew_ring", "len_ring", "ptr",
-                                          "n", "ep_a", "ep_b", "ep_sum", "ep_cnt")] + \
-        [("N", C.c_int32), ("na", C.c_int32), ("nb", C.c_int32)]
-
-
-class TransposeDesc(C.Structure):
-    """Mirror of lgx_transpose_desc."""
-    _fields_ = [("src", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
-                ("dst", C.c_void_p)]
-
-
-class ChainLayer(C.Structure):
-    """Mirror of lgx_chain_layer."""
-    _fields_ = [("B", C.c_void_p), ("ldb", C.c_int64), ("C", C.c_void_p), ("ldc", C.c_int64),
-                ("K", C.c_int32), ("N", C.c_int32), ("epilogue", C.c_int32), ("bias", C.c_void_p),
-                ("act", C.c_void_p), ("ld_act", C.c_int64)]
-
-
-class ChainDesc(C.Structure):
-    """Mirror of lgx_chain_desc."""
-    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("rows", C.c_int32), ("nlayers", C.c_int32),
-                ("layers", ChainLayer * CHAIN_MAXL)]
-
-
-class AdaptArgs(C.Structure):
-    """Mirror of lgx_adapt_args."""
-    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("B", C.c_int32), ("H", C.c_int32), ("P", C.c_int32),
-                ("w0", C.c_void_p), ("b0", C.c_void_p), ("C1", C.c_int32),
-                ("w1", C.c_void_p), ("b1", C.c_void_p), ("C2", C.c_int32), ("k1", C.c_int32), ("s1", C.c_int32),
-                ("w2", C.c_void_p), ("b2", C.c_void_p), ("C3", C.c_int32), ("k2", C.c_int32), ("s2", C.c_int32),
-                ("wf", C.c_void_p), ("bf", C.c_void_p), ("NO", C.c_int32),
-                ("out", C.c_void_p), ("ldo", C.c_int64)]
-
-
-class AdaptTrainArgs(C.Structure):
-    """Mirror of lgx_adapt_train_args (ABI 9)."""
-    _fields_ = [("f", AdaptArgs), ("target", C.c_void_p), ("ldt", C.c_int64), ("gws", C.c_void_p),
-                ("loss_ws", C.c_void_p), ("blocks", C.c_int32)]
 
 
 ADAPT_TRAIN_ROWS = 16  # rows per chunk of lgx_adaptation_train (lgx_mlp.hip ATR)
@@ -253,91 +107,6 @@ def adaptation_train(mod, obs_rows, hist_cols, target, gws, loss_ws, blocks):
     return (W1, W2, Wf)  # keep the re-laid weights alive until the launch has run (stream order)
 
 
-class GaeArgs(C.Structure):
-    """Mirror of lgx_gae_args."""
-    _fields_ = [(n, C.c_void_p) for n in ("rewards", "dones", "values", "last_values", "returns", "advantages")] + \
-               [("T", C.c_int32), ("N", C.c_int32), ("gamma", C.c_float), ("lam", C.c_float)] + \
-               [(n, C.c_void_p) for n in ("moments", "ws", "counter")]
-
-
-class MlpLibError(RuntimeError):
-    pass
-
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_LIB_PATH):
-        raise MlpLibError(f"liblgx_mlp.so not built ({_LIB_PATH}); run `python -m legged_gym_custom_amd.build_native`")
-    L = C.CDLL(_LIB_PATH)
-    L.lgx_mlp_abi_version.restype = C.c_int32
-    L.lgx_mlp_pick_split.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.lgx_mlp_pick_split.restype = C.c_int32
-    L.lgx_gemm.argtypes = [C.c_void_p, C.c_void_p]
-    L.lgx_gemm.restype = C.c_int32
-    L.lgx_mlp_last_error.restype = C.c_char_p
-    vp, f32 = C.c_void_p, C.c_float
-    L.lgx_ppo_head_forward.argtypes = [vp, vp]
-    L.lgx_ppo_head_forward.restype = C.c_int32
-    L.lgx_ppo_head_backward.argtypes = [vp, vp]
-    L.lgx_ppo_head_backward.restype = C.c_int32
-    L.lgx_adam_step.argtypes = [vp, vp, vp, vp, C.c_int64, vp, f32, f32, f32, f32, vp, vp, vp]
-    L.lgx_adam_step.restype = C.c_int32
-    L.lgx_clip_adam.argtypes = [vp, vp, vp, vp, C.c_int64, vp, f32, f32, f32, f32, vp, f32, vp, vp]
-    L.lgx_clip_adam.restype = C.c_int32
-    L.lgx_copy_batch.argtypes = [vp, C.c_int32, vp]
-    L.lgx_copy_batch.restype = C.c_int32
-    L.lgx_act_head.argtypes = [vp, vp]
-    L.lgx_act_head.restype = C.c_int32
-    L.lgx_store_transition.argtypes = [vp, vp]
-    L.lgx_store_transition.restype = C.c_int32
-    L.lgx_track_episodes.argtypes = [vp, vp]
-    L.lgx_track_episodes.restype = C.c_int32
-    for fn in ("lgx_loss_heads_forward", "lgx_loss_heads_backward"):
-        getattr(L, fn).argtypes = [vp, vp, vp]
-        getattr(L, fn).restype = C.c_int32
-    L.lgx_loss_heads_fused.argtypes = [vp, vp, vp, vp]
-    L.lgx_loss_heads_fused.restype = C.c_int32
-    L.lgx_loss_heads_tail.argtypes = [vp, vp, vp, vp, vp]
-    L.lgx_loss_heads_tail.restype = C.c_int32
-    L.lgx_adaptation_train.argtypes = [vp, vp]
-    L.lgx_adaptation_train.restype = C.c_int32
-    for fn in ("lgx_aux_loss_forward", "lgx_aux_loss_backward", "lgx_ppo_tail"):
-        getattr(L, fn).argtypes = [vp, vp]
-        getattr(L, fn).restype = C.c_int32
-    L.lgx_gemm_group.argtypes = [vp, C.c_int32, vp]
-    L.lgx_gemm_group.restype = C.c_int32
-    L.lgx_mlp_pick_split_group.argtypes = [vp, vp, vp, C.c_int32, vp]
-    L.lgx_mlp_pick_split_group.restype = C.c_int32
-    L.lgx_transpose_batch.argtypes = [vp, C.c_int32, vp]
-    L.lgx_transpose_batch.restype = C.c_int32
-    L.lgx_gather_rows.argtypes = [vp, C.c_int32, vp, C.c_int64, vp]
-    L.lgx_gather_rows.restype = C.c_int32
-    L.lgx_gae.argtypes = [vp, vp]
-    L.lgx_gae.restype = C.c_int32
-    L.lgx_normalize_advantages.argtypes = [vp, C.c_int64, vp, C.c_double, vp]
-    L.lgx_normalize_advantages.restype = C.c_int32
-    L.lgx_splitk_reduce_batch.argtypes = [vp, C.c_int32, vp]
-    L.lgx_splitk_reduce_batch.restype = C.c_int32
-    L.lgx_chain.argtypes = [vp, C.c_int32, vp]
-    L.lgx_chain.restype = C.c_int32
-    L.lgx_adaptation_forward.argtypes = [vp, vp]
-    L.lgx_adaptation_forward.restype = C.c_int32
-    if L.lgx_mlp_abi_version() != ABI_VERSION:
-        raise MlpLibError("liblgx_mlp ABI version mismatch; rebuild")
-    L.lgx_mlp_sizeof_gemm_args.restype = C.c_int32
-    if L.lgx_mlp_sizeof_gemm_args() != C.sizeof(GemmArgs):
-        raise MlpLibError(f"lgx_gemm_args layout mismatch: C {L.lgx_mlp_sizeof_gemm_args()} vs ctypes "
-                          f"{C.sizeof(GemmArgs)}")
-    _lib = L
-    return L
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _run(args):
     L = lib()
     rc = L.lgx_gemm(C.byref(args), C.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -347,15 +116,6 @@ def _run(args):
 
 def _rowmajor(t):
     return t if t.stride(-1) == 1 else t.contiguous()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise MlpLibError(f"{what}: " + lib().lgx_mlp_last_error().decode())
 
 
 def copy_batch(dsts, srcs):
@@ -471,7 +231,7 @@ def normalize_advantages(advantages, moments, count):
 
 def clip_adam(p, g, m, v, step, lr, beta1, beta2, eps, max_norm, coef_out=None):
     """lgx_clip_adam: clip_grad_norm_(g, max_norm) in place, step += 1 and one Adam step over one
-    small flat segment (<= 65536 entries), in one launch; lr: float or 0-dim device tensor."""
+    small flat segment (<= CLIP_ADAM_MAX entries), in one launch; lr: float or 0-dim device tensor."""
     lr_dev = lr.data_ptr() if isinstance(lr, torch.Tensor) else None
     lr_f = 0.0 if isinstance(lr, torch.Tensor) else float(lr)
     _check(lib().lgx_clip_adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), g.numel(), lr_dev, lr_f,

@@ -10,6 +10,9 @@ import os
 
 import torch
 
+from legged_gym_custom_amd import _cbind
+from legged_gym_custom_amd._cbind import ptr as _ptr, stream as _stream
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("LGX_S8_LIB") or os.path.join(os.path.dirname(os.path.dirname(_HERE)), "lib", "liblgx_s8.so")  # env: A/B builds
 _lib = None
@@ -21,10 +24,6 @@ GROUP_MAX = 20
 BATCH_MAX = 48
 TILE_M = 64  # rows of one FWD / DX column-sum partial (lgx_s8.h LGX_S8_TILE_M)
 SPLIT_ROWS = 256
-EXPORTED = ("lgx_s8_abi_version", "lgx_s8_sizeof_gemm_args", "lgx_s8_last_error", "lgx_s8_gemm_group",
-            "lgx_s8_pick_split", "lgx_s8_split", "lgx_s8_reduce", "lgx_s8_act", "lgx_s8_act_last_error",
-            "lgx_s8_sizeof_act_args", "lgx_s8_act_pack", "lgx_s8_sizeof_act_pack_args", "lgx_s8_chain",
-            "lgx_s8_sizeof_chain_args")
 CHAIN_MAX, CHAIN_MAXL, CHAIN_MAXW = 4, 3, 256
 ACT_ROWS, ACT_MAXIN, ACT_MAXH, ACT_MAXENC, ACT_MAXL = 32, 640, 512, 256, 6
 
@@ -85,48 +84,43 @@ def flat_reduce(ws, stride, out, n, nsplit, accumulate=0):
                       accumulate=accumulate)
 
 
+# the three tables of the lgx_s8.h mirror (legged_gym_custom_amd/_cbind.py; tests/test_abi.py checks them)
+STRUCTS = {"lgx_s8_gemm_args": GemmArgs, "lgx_s8_split_args": SplitArgs, "lgx_s8_reduce_args": ReduceArgs,
+           "lgx_s8_act_layer": ActLayer, "lgx_s8_act_args": ActArgs, "lgx_s8_act_pack_args": ActPackArgs,
+           "lgx_s8_chain_layer": ChainLayer, "lgx_s8_chain_args": ChainArgs}
+SIZEOF = {"lgx_s8_sizeof_" + n: "lgx_s8_" + n for n in ("gemm_args", "act_pack_args", "chain_args", "act_args")}
+CONSTANTS = {
+    "LGX_S8_ABI_VERSION": ABI_VERSION, "LGX_S8_FWD": FWD, "LGX_S8_DX": DX, "LGX_S8_DW": DW,
+    "LGX_S8_EPI_BIAS": EPI_BIAS, "LGX_S8_EPI_ELU": EPI_ELU, "LGX_S8_EPI_DELU": EPI_DELU,
+    "LGX_S8_EPI_ACCUM": EPI_ACCUM, "LGX_S8_GROUP_MAX": GROUP_MAX, "LGX_S8_BATCH_MAX": BATCH_MAX,
+    "LGX_S8_TILE_M": TILE_M, "LGX_S8_SPLIT_ROWS": SPLIT_ROWS, "LGX_S8_CHAIN_MAX": CHAIN_MAX,
+    "LGX_S8_CHAIN_MAXL": CHAIN_MAXL, "LGX_S8_CHAIN_MAXW": CHAIN_MAXW, "LGX_S8_ACT_ROWS": ACT_ROWS,
+    "LGX_S8_ACT_MAXIN": ACT_MAXIN, "LGX_S8_ACT_MAXH": ACT_MAXH, "LGX_S8_ACT_MAXENC": ACT_MAXENC,
+    "LGX_S8_ACT_MAXL": ACT_MAXL,
+}
+SIGNATURES = {
+    "lgx_s8_abi_version": (i32, ()),
+    **{name: (i32, ()) for name in SIZEOF},
+    "lgx_s8_last_error": (C.c_char_p, ()),
+    "lgx_s8_gemm_group": (i32, (vp, i32, i32, vp)),
+    "lgx_s8_pick_split": (i32, (vp, vp, vp, i32, vp)),
+    "lgx_s8_split": (i32, (vp, i32, vp)),
+    "lgx_s8_reduce": (i32, (vp, i32, vp)),
+    "lgx_s8_act": (i32, (vp, vp)),
+    "lgx_s8_act_pack": (i32, (vp, i32, vp)),
+    "lgx_s8_act_last_error": (C.c_char_p, ()),
+    "lgx_s8_chain": (i32, (vp, i32, vp)),
+}
+EXPORTED = list(SIGNATURES)
+
+
 class S8LibError(RuntimeError):
     pass
 
 
 def load(path=_LIB_PATH):
     """A liblgx_s8 handle (the product library by default; dev tools load build variants)."""
-    if not os.path.exists(path):
-        raise S8LibError(f"liblgx_s8.so not built ({path}); run `python -m legged_gym_custom_amd.build_native`")
-    L = C.CDLL(path)
-    L.lgx_s8_abi_version.restype = i32
-    L.lgx_s8_sizeof_gemm_args.restype = i32
-    L.lgx_s8_last_error.restype = C.c_char_p
-    L.lgx_s8_gemm_group.argtypes = [vp, i32, i32, vp]
-    L.lgx_s8_gemm_group.restype = i32
-    L.lgx_s8_pick_split.argtypes = [vp, vp, vp, i32, vp]
-    L.lgx_s8_pick_split.restype = i32
-    for fn in ("lgx_s8_split", "lgx_s8_reduce"):
-        getattr(L, fn).argtypes = [vp, i32, vp]
-        getattr(L, fn).restype = i32
-    L.lgx_s8_act.argtypes = [vp, vp]
-    L.lgx_s8_act.restype = i32
-    L.lgx_s8_act_last_error.restype = C.c_char_p
-    L.lgx_s8_sizeof_act_args.restype = i32
-    L.lgx_s8_act_pack.argtypes = [vp, i32, vp]
-    L.lgx_s8_act_pack.restype = i32
-    L.lgx_s8_sizeof_act_pack_args.restype = i32
-    L.lgx_s8_chain.argtypes = [vp, i32, vp]
-    L.lgx_s8_chain.restype = i32
-    L.lgx_s8_sizeof_chain_args.restype = i32
-    if L.lgx_s8_abi_version() != ABI_VERSION:
-        raise S8LibError("liblgx_s8 ABI version mismatch; rebuild")
-    if L.lgx_s8_sizeof_gemm_args() != C.sizeof(GemmArgs):
-        raise S8LibError(f"lgx_s8_gemm_args layout mismatch: C {L.lgx_s8_sizeof_gemm_args()} vs ctypes "
-                         f"{C.sizeof(GemmArgs)}")
-    if L.lgx_s8_sizeof_act_pack_args() != C.sizeof(ActPackArgs):
-        raise S8LibError("lgx_s8_act_pack_args layout mismatch")
-    if L.lgx_s8_sizeof_chain_args() != C.sizeof(ChainArgs):
-        raise S8LibError("lgx_s8_chain_args layout mismatch")
-    if L.lgx_s8_sizeof_act_args() != C.sizeof(ActArgs):
-        raise S8LibError(f"lgx_s8_act_args layout mismatch: C {L.lgx_s8_sizeof_act_args()} vs ctypes "
-                         f"{C.sizeof(ActArgs)}")
-    return L
+    return _cbind.load(path, "liblgx_s8", SIGNATURES, STRUCTS, ("lgx_s8_abi_version", ABI_VERSION), SIZEOF, S8LibError)
 
 
 def lib():
@@ -136,17 +130,9 @@ def lib():
     return _lib
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _check(rc, what):
     if rc != 0:
         raise S8LibError(f"{what}: " + lib().lgx_s8_last_error().decode())
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def rup(x, m):
