@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 7
+#define LGX_ABI_VERSION 8
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -47,6 +47,7 @@ extern "C" {
 #define LGX_MAX_TERMINATION 8
 #define LGX_EVAL_METRICS 8        /* per-env record columns (lgx_eval_buffers.acc) */
 #define LGX_EVAL_CELL_COLS 12     /* per-cell output columns (lgx_eval_buffers.cells) */
+#define LGX_MAX_ACTION_HISTORY 4  /* control steps of actuation latency (action_history rows) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -229,6 +230,9 @@ typedef struct lgx_task_params {
   float curriculum_threshold;       /* fp32(0.8 * reward_scales['tracking_lin_vel']) (dt-scaled) */
   int32_t curriculum_lo_free;       /* 1: lo_max = lo - delta (go2, max_reverse_vel >= 0) */
   double curriculum_delta, curriculum_lo_min, curriculum_lo_max, curriculum_hi_max;
+  /* actuation latency (ABI v8): H, the rows of lgx_buffers.action_history = the largest latency
+     in control steps; 0 = no latency support. lgx_create refuses H > LGX_MAX_ACTION_HISTORY. */
+  int32_t action_history_len;
 } lgx_task_params;
 
 /* Every per-env buffer the step reads/writes. NULL = not present. */
@@ -299,6 +303,27 @@ typedef struct lgx_buffers {
   float* curriculum_vals;      /* [N] an env's tracking_lin_vel episode sum at its in-step reset */
   float* command_range_log;    /* [4] extras['episode'] values: go2 max_command_x, min_command_x,
                                   max_command_y, max_command_yaw; base: max x, max y, max yaw */
+  /* Actuator randomisation (ABI v8; the reference has neither). All three optional; NULL = the
+     ideal actuator of ABI 7, bit for bit.
+     Latency: with n = decimation, H = params.action_history_len, d = action_delay[e] clamped into
+     [0, H*n] by the step (it never indexes with an unclamped value) and a[t] the clipped action of
+     step t, the actuator's action input in substep s of step t (the PD / V / T torque and the
+     actuator net's position-error input) is a[t - ceil(max(d - s, 0) / n)]: with k = ceil(d / n)
+     and r = d - (k - 1) n, substeps s < r use a[t - k], the rest a[t - k + 1]. Only the actuator
+     sees the delayed action: the observation's action term, actions, last_actions and the
+     action-rate reward use a[t].
+     action_history[e][i] holds a[t - 1 - i] at the start of step t. Row 0 equals last_actions[e]
+     bit for bit after every step and every reset (it follows every write of last_actions: zero
+     after lgx_reset_envs, this step's actions after a step, also one that resets or blows up);
+     rows >= 1 shift down by one at the end of a step and are zeroed for an env that the step or
+     lgx_reset_envs resets. lgx_bind refuses action_delay without action_history or with H = 0,
+     and action_history with H = 0.
+     Motor strength: each substep's torque is motor_strength[e][j] * t before the clip to
+     torque_limits, in all three control modes; with the actuator net it multiplies the net's
+     output torque. */
+  const int32_t* action_delay; /* [N] latency of each env in physics substeps */
+  float* action_history;       /* [N,H,A] state */
+  const float* motor_strength; /* [N,D] */
 } lgx_buffers;
 
 typedef struct lgx_env lgx_env;

@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -21,6 +21,7 @@ MAX_PENALISED = 24
 MAX_TERMINATION = 8
 EVAL_METRICS = 8     # per-env record columns (lgx_eval_buffers.acc)
 EVAL_CELL_COLS = 12  # per-cell output columns (lgx_eval_buffers.cells)
+MAX_ACTION_HISTORY = 4  # control steps of actuation latency (rows of lgx_buffers.action_history)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -116,6 +117,7 @@ class TaskParams(C.Structure):
         ("command_curriculum", i32), ("curriculum_term", i32), ("curriculum_threshold", f32),
         ("curriculum_lo_free", i32), ("curriculum_delta", C.c_double), ("curriculum_lo_min", C.c_double),
         ("curriculum_lo_max", C.c_double), ("curriculum_hi_max", C.c_double),
+        ("action_history_len", i32),
     ]
 
 
@@ -134,6 +136,7 @@ class Buffers(C.Structure):
         "friction", "mass_params", "kp_kd", "env_origins", "terrain_levels", "terrain_types",
         "terrain_origins", "height_samples", "terrain_mesh", "sea_hidden", "sea_cell", "episode_stats",
         "blew_up", "blowup_count", "command_ranges", "curriculum_vals", "command_range_log",
+        "action_delay", "action_history", "motor_strength",
     ]]
 
 
@@ -155,6 +158,7 @@ CONSTANTS = {
     "LGX_MAX_HEIGHT_POINTS": MAX_HEIGHT_POINTS, "LGX_MAX_REWARDS": MAX_REWARDS,
     "LGX_MAX_CANDIDATES": MAX_CANDIDATES, "LGX_MAX_CONTACTS": MAX_CONTACTS, "LGX_MAX_PENALISED": MAX_PENALISED,
     "LGX_MAX_TERMINATION": MAX_TERMINATION, "LGX_EVAL_METRICS": EVAL_METRICS, "LGX_EVAL_CELL_COLS": EVAL_CELL_COLS,
+    "LGX_MAX_ACTION_HISTORY": MAX_ACTION_HISTORY,
     "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
     "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
     **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},

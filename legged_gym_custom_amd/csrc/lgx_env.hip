@@ -773,12 +773,49 @@ LGX_DEV void sea_unit_k(const float* __restrict__ w_ih, const float* __restrict_
   c = fg * c + ig * gg;
   h = og * (2.0f * sg(2.0f * c) - 1.0f);
 }
+// Actuation latency (include/lgx.h, ABI 8), called before a substep's torques when action_delay is
+// bound (a wave-uniform branch): the actuator reads s.act, so a delayed env's s.act takes the action
+// of the age this substep prescribes whenever that age changes (at most twice a step): a row of
+// the history, or this step's own action back from B.actions. No LDS, and nothing is kept live
+// across a substep (the table and the lane are re-read here); with the feature off the cost is one
+// scalar load per substep. The caller puts a barrier between this and the torques.
+LGX_DEV void stage_actuator_action(Sh& s, const lgx_task_params* Pm_, const lgx_buffers& B, int e, int lane_, int sub) {
+  const lgx_task_params* Pm = opaque(Pm_);
+  const int AH = Pm->action_history_len, n = Pm->decimation, A = Pm->num_actions;
+  const int d = action_delay_clamp(B.action_delay[e], AH, n);
+  const int age = action_age(d, sub, n);  // 0..AH
+  const int lane = opaque_lane(lane_);
+  if (lane < A && age != (sub ? action_age(d, sub - 1, n) : 0))
+    s.act[lane] = age ? B.action_history[((size_t)e * AH + (age - 1)) * A + lane] : B.actions[(size_t)e * A + lane];
+}
+
+// The same rule for the actuator net, whose unit lanes read joint j's action (of another lane): a
+// delayed one straight from the history in global memory. (Staging it into s.act as above cost this
+// instance a spilled VGPR on the terrain, reading it here costs the PD instances three.)
+LGX_DEV float sea_action(const Sh& s, const lgx_task_params* Pm, const lgx_buffers& B, int e, int j, int sub) {
+  float a = s.act[j];
+  if (B.action_delay) {
+    const int AH = Pm->action_history_len, n = Pm->decimation, A = Pm->num_actions;
+    const int age = action_age(action_delay_clamp(B.action_delay[e], AH, n), sub, n);  // 0..AH
+    if (age > 0 && j < A) a = B.action_history[((size_t)e * AH + (age - 1)) * A + j];
+  }
+  return a;
+}
+
+// Motor strength (include/lgx.h, ABI 8), read from global memory in the substep (a dozen lanes, L1 /
+// L2 hits after the first substep) under a wave-uniform branch on the bound pointer: no LDS,
+// nothing live across the substeps, and one scalar load with the feature off.
+LGX_DEV float motor_strength(const lgx_task_params* Pm, const lgx_buffers& B, int e, int j) {
+  return B.motor_strength ? B.motor_strength[(size_t)e * Pm->num_dof + j] : 1.0f;
+}
+
 // all 12 joints' SEA torques into s.tau (every lane of the wave takes part), one unit per lane
 // over two passes. (Two units per lane in one pass measured 425-459 us vs 433 for C3's kernel,
 // with 33-38 spilled VGPRs: not kept, profiles/r03_sea_spill_fix.txt.)
 // inlined (54 VGPRs spill at the 4-waves-per-SIMD budget, yet C3's kernel is 589 us against 611
 // as a call and 642 one joint per lane: profiles/r03_bench_anymal_c_rough_sea_waves.txt)
-LGX_DEV void sea_torques_lanes(Sh& s, float* A, const lgx_task_params* Pm_, const lgx_buffers& B, int e, int lane) {
+LGX_DEV void sea_torques_lanes(Sh& s, float* A, const lgx_task_params* Pm_, const lgx_buffers& B, int e, int lane,
+                               int sub) {
   const size_t NT = (size_t)Pm_->num_envs * Pm_->num_dof;
   const int u = lane & 7;
   // The net's 972 floats (sea_in_scale .. sea_lin_w, contiguous in lgx_task_params) are copied
@@ -804,7 +841,7 @@ LGX_DEV void sea_torques_lanes(Sh& s, float* A, const lgx_task_params* Pm_, cons
     const size_t r = (size_t)e * Pm->num_dof + jj;
     float h0 = B.sea_hidden[r * 8 + u], c0 = B.sea_cell[r * 8 + u];
     float h1 = B.sea_hidden[(NT + r) * 8 + u], c1 = B.sea_cell[(NT + r) * 8 + u];
-    const float in0 = (s.act[jj] * Pm->action_scale + Pm->default_dof_pos[jj]) - s.th[jj];
+    const float in0 = (sea_action(s, Pm, B, e, jj, sub) * Pm->action_scale + Pm->default_dof_pos[jj]) - s.th[jj];
     const float x[2] = {in0 * Pm->sea_in_scale[0], s.thd[jj] * Pm->sea_in_scale[1]};
     sea_unit_k<2, false>(W.w(SEA_OFF(sea_w_ih0)), W.w(SEA_OFF(sea_w_hh0)), W.w(SEA_OFF(sea_b_ih0)),
                          W.w(SEA_OFF(sea_b_hh0)), u, x, 0.0f, h0, h0, c0);
@@ -826,7 +863,10 @@ LGX_DEV void sea_torques_lanes(Sh& s, float* A, const lgx_task_params* Pm_, cons
       }
       y += W.w(SEA_OFF(sea_lin_w))[k] * hk;
     }
-    if (on && u == 0) s.tau[j] = Pm->sea_out_scale * (y + Pm->sea_lin_b);
+    if (on && u == 0) {
+      const float t = Pm->sea_out_scale * (y + Pm->sea_lin_b);
+      s.tau[j] = B.motor_strength ? motor_strength(Pm, B, e, j) * t : t;
+    }
   }
 }
 
@@ -1021,7 +1061,7 @@ LGX_DEV void solve_rows(Sh& s, float* A, const lgx_task_params* Pm, int lane, in
 // for the wide constraint solve (an env with more than 32 rows: each env in turn on all 64 lanes).
 template <bool TERRAIN, bool ACTNET, int WL>
 LGX_DEV void substep(Sh& s, float* A, Sh* S0, float* A0, int astride, const lgx_model* M_,
-                     const lgx_task_params* Pm_, const lgx_buffers& B, int lane_, int e, bool last) {
+                     const lgx_task_params* Pm_, const lgx_buffers& B, int lane_, int e, int sub, bool last) {
   // The model and task tables are re-read each substep (L1 / scalar-cache hits) rather than
   // hoisted out of the decimation loop, where ~40 lane-indexed constants would otherwise stay
   // live in VGPRs across the whole step. Likewise the lane index, so that per-lane index and
@@ -1034,7 +1074,7 @@ LGX_DEV void substep(Sh& s, float* A, Sh* S0, float* A0, int astride, const lgx_
   {
 #pragma clang fp contract(off)
     if (ACTNET) {
-      sea_torques_lanes(s, A, Pm, B, e, lane);
+      sea_torques_lanes(s, A, Pm, B, e, lane, sub);
     } else if (lane < NJ) {
       const int j = lane;
       float as = s.act[j] * Pm->action_scale;
@@ -1050,6 +1090,7 @@ LGX_DEV void substep(Sh& s, float* A, Sh* S0, float* A0, int astride, const lgx_
       } else {
         t = as;
       }
+      if (B.motor_strength) t = motor_strength(Pm, B, e, j) * t;
       s.tau[j] = fminf(fmaxf(t, -Pm->torque_limits[j]), Pm->torque_limits[j]);
     }
   }
@@ -1346,6 +1387,8 @@ LGX_DEV void reset_env(const lgx_task_params* Pm, const lgx_buffers& B, Sh& s, f
   if (zero_carried) {
     const int A = Pm->num_actions, H = Pm->history_len * Pm->num_proprio;
     if (lane < A) B.last_actions[(size_t)e * A + lane] = 0.f;
+    if (B.action_history)
+      for (int i = lane; i < Pm->action_history_len * A; i += WL) B.action_history[(size_t)e * Pm->action_history_len * A + i] = 0.f;
     if (lane < D) { B.last_dof_vel[(size_t)e * D + lane] = 0.f; B.last_torques[(size_t)e * D + lane] = 0.f; }
     if (lane < 6) B.last_root_vel[e * 6 + lane] = 0.f;
     if (lane < 3) B.last_base_lin_vel[e * 3 + lane] = 0.f;
@@ -1569,8 +1612,18 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
     }
     __syncthreads();
     PH(0);
-    for (int sub = 0; sub < Pm->decimation; ++sub)
-      substep<TERRAIN, ACTNET, WL>(s, AR, S_, lgx_dyn, astride, M, Pm, B, lane, e, sub == Pm->decimation - 1);
+    for (int sub = 0; sub < Pm->decimation; ++sub) {
+      if (!ACTNET && B.action_delay) {  // (the actuator net: sea_action)
+        stage_actuator_action(s, Pm, B, e, lane, sub);
+        __syncthreads();
+      }
+      substep<TERRAIN, ACTNET, WL>(s, AR, S_, lgx_dyn, astride, M, Pm, B, lane, e, sub, sub == Pm->decimation - 1);
+    }
+    // the rest of the step (guard, observation, last_actions, rewards) sees this step's action
+    if (!ACTNET && B.action_delay) {
+      const int ln = opaque_lane(lane), A = opaque(Pm)->num_actions;
+      if (ln < A) s.act[ln] = B.actions[(size_t)e * A + ln];
+    }
     __syncthreads();
     // NaN/Inf guard (SURVEY.md §5 "Failure detection"; the reference has none): a state that
     // went non-finite in any substep stays non-finite, so one check after the substeps sees it.
@@ -1905,6 +1958,10 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
     }
   // last_* copies go2.py:380-384 and state write-back
   if (lane < A) B.last_actions[(size_t)e * A + lane] = s.act[lane];
+  if (B.action_history && lane < A) {  // each lane its own column: the substeps' reads are done
+    const int AH = Pm->action_history_len;
+    action_history_push(B.action_history + (size_t)e * AH * A, AH, A, lane, s.act[lane], reset != 0);
+  }
   if (lane < D) {
     B.last_dof_vel[(size_t)e * D + lane] = s.thd[lane];
     B.last_torques[(size_t)e * D + lane] = s.tau[lane];
@@ -2035,6 +2092,8 @@ int lgx_create(const lgx_model* model, const lgx_task_params* params, int32_t de
   if (params->num_proprio > LGX_MAX_PROPRIO || params->num_height_points > LGX_MAX_HEIGHT_POINTS)
     return fail(env, "observation too large");
   if (params->num_reward_terms + 1 > 64) return fail(env, "too many reward terms");
+  if (params->action_history_len < 0 || params->action_history_len > LGX_MAX_ACTION_HISTORY)
+    return fail(env, "action_history_len outside 0..LGX_MAX_ACTION_HISTORY");
   // observation layout the step writes (go2.py:467-574 / legged_robot.py:240-273): obs =
   // [history (H x P) | current (P)]; Go2 critic = [obs | priv | est (3) | scan]. A config whose
   // declared sizes disagree (the reference's anymal_c_flat: 48-wide obs, 235-wide proprio)
@@ -2100,6 +2159,10 @@ int lgx_bind(lgx_env* env, const lgx_buffers* b) {
   if (env->params.actuator_net &&
       ((reinterpret_cast<uintptr_t>(b->sea_hidden) | reinterpret_cast<uintptr_t>(b->sea_cell)) & 15))
     return fail(env, "lgx_bind: sea_hidden/sea_cell must be 16-byte aligned");
+  if (b->action_delay && (!b->action_history || env->params.action_history_len <= 0))
+    return fail(env, "lgx_bind: action_delay needs action_history and params.action_history_len > 0");
+  if (b->action_history && env->params.action_history_len <= 0)
+    return fail(env, "lgx_bind: action_history with params.action_history_len = 0");
   if (env->params.curriculum && (!b->terrain_levels || !b->terrain_types || !b->terrain_origins))
     return fail(env, "lgx_bind: terrain curriculum needs terrain_levels/terrain_types/terrain_origins");
   env->buffers = *b;

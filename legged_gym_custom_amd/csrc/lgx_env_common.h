@@ -236,6 +236,31 @@ LGX_HD float rand_range(float lo, float hi, float u) {
 // enter the fp32 tensor ops as fp32 scalars
 LGX_HD float rand_range_d(double lo, double hi, float u) { return (float)(hi - lo) * u + (float)lo; }
 
+// Actuation latency (lgx_buffers.action_delay, include/lgx.h). d: an env's latency in physics
+// substeps, clamped by action_delay_clamp into [0, H * decimation]. action_age: how many control
+// steps old the action is that the actuator sees in substep `sub` of a step,
+// ceil(max(d - sub, 0) / decimation) in 0..H: 0 = this step's action, i >= 1 = action_history
+// row i - 1.
+LGX_HD int action_delay_clamp(int d, int H, int decimation) {
+  const int hi = H * decimation;
+  return d < 0 ? 0 : (d > hi ? hi : d);
+}
+LGX_HD int action_age(int d, int sub, int decimation) {
+  // ceil(x / n) for x <= LGX_MAX_ACTION_HISTORY * n counts the multiples i * n below x: no integer
+  // division (on the GPU that is a float reciprocal sequence in vector registers)
+  const int left = d - sub;
+  int age = 0;
+  LGX_UNROLL
+  for (int i = 0; i < LGX_MAX_ACTION_HISTORY; ++i) age += (int)(left > i * decimation);
+  return age;
+}
+// The end of a step for element j of env e's history ([H, A] at h): rows shift down by one (zeroed
+// instead when the env reset in this step) and row 0 takes `last`, the value last_actions gets.
+LGX_HD void action_history_push(float* h, int H, int A, int j, float last, bool reset) {
+  for (int i = H - 1; i >= 1; --i) h[i * A + j] = reset ? 0.f : h[(i - 1) * A + j];
+  h[j] = last;
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];

@@ -306,14 +306,24 @@ static float sea_torque(const lgx_task_params* P, const lgx_buffers* B, int e, i
 }
 
 // ------------------------------------------------------------------ one physics substep
-static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const lgx_buffers* B, int e, bool last) {
+static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const lgx_buffers* B, int e, int sub,
+                    bool last) {
   const float dt = P->sim_dt;
   const bool terrain = P->mesh_type != LGX_MESH_PLANE;
   // PD torques: LeggedRobot._compute_torques legged_robot.py:440-478 (or the SEA net)
+  // actuation latency and motor strength (include/lgx.h, ABI 8): the kernel's rule
+  int age = 0;
+  if (B->action_delay)
+    age = action_age(action_delay_clamp(B->action_delay[e], P->action_history_len, P->decimation), sub, P->decimation);
   for (int j = 0; j < NJ; ++j) {
-    const float as = s.act[j] * P->action_scale;
+    const float a = (age > 0 && j < P->num_actions)
+                        ? B->action_history[((size_t)e * P->action_history_len + (age - 1)) * P->num_actions + j]
+                        : s.act[j];
+    const float as = a * P->action_scale;
+    const float ms = B->motor_strength ? B->motor_strength[(size_t)e * P->num_dof + j] : 1.0f;
     if (P->actuator_net) {
-      s.tau[j] = sea_torque(P, B, e, j, (as + P->default_dof_pos[j]) - s.th[j], s.thd[j]);
+      const float t = sea_torque(P, B, e, j, (as + P->default_dof_pos[j]) - s.th[j], s.thd[j]);
+      s.tau[j] = B->motor_strength ? ms * t : t;
       continue;
     }
     float t;
@@ -326,6 +336,7 @@ static void substep(Env& s, const lgx_model* M, const lgx_task_params* P, const 
     } else {
       t = as;
     }
+    if (B->motor_strength) t = ms * t;
     s.tau[j] = fminf(fmaxf(t, -P->torque_limits[j]), P->torque_limits[j]);
   }
   kinematics<true>(s, M, P);
@@ -570,6 +581,8 @@ static void reset_env(const lgx_task_params* P, const lgx_buffers* B, Env& s, in
   if (zero_carried) {
     const int A = P->num_actions, H = P->history_len * P->num_proprio;
     memset(B->last_actions + (size_t)e * A, 0, sizeof(float) * A);
+    if (B->action_history)
+      memset(B->action_history + (size_t)e * P->action_history_len * A, 0, sizeof(float) * P->action_history_len * A);
     memset(B->last_dof_vel + (size_t)e * D, 0, sizeof(float) * D);
     memset(B->last_torques + (size_t)e * D, 0, sizeof(float) * D);
     memset(B->last_root_vel + (size_t)e * 6, 0, sizeof(float) * 6);
@@ -716,7 +729,7 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     quat_to_R(s.qb, R);
     const f3 rc = mv(R, mk(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
     st3(s.vo, ld3(r0 + 7) - cross(ld3(s.wb), rc));  // COM velocity -> origin velocity
-    for (int sub = 0; sub < P->decimation; ++sub) substep(s, M, P, B, e, sub == P->decimation - 1);
+    for (int sub = 0; sub < P->decimation; ++sub) substep(s, M, P, B, e, sub, sub == P->decimation - 1);
     // NaN/Inf guard (the kernel's rule, lgx_env.hip): a non-finite state after the substeps
     // becomes a finite stand-in and the env is reset below
     bool bad = false;
@@ -926,6 +939,10 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     hist_g[i] = (s.ep <= 1) ? s.cur[i % Pp] : (i < (H - 1) * Pp ? s.hist[i + Pp] : s.cur[i - (H - 1) * Pp]);
   // last_* copies go2.py:380-384 and state write-back
   memcpy(B->last_actions + (size_t)e * A, s.act, sizeof(float) * A);
+  if (B->action_history)
+    for (int j = 0; j < A; ++j)
+      action_history_push(B->action_history + (size_t)e * P->action_history_len * A, P->action_history_len, A, j,
+                          s.act[j], reset != 0);
   for (int j = 0; j < D; ++j) {
     B->last_dof_vel[(size_t)e * D + j] = s.thd[j];
     B->last_torques[(size_t)e * D + j] = s.tau[j];

@@ -56,6 +56,8 @@ class LeggedRobot(BaseTask):
         # step's number and lgx_episode_extras advances it), so a captured rollout replays with
         # the right step numbers; the host mirror follows
         self._csc += 1
+        if not self._captured and self.sim_device_id >= 0 and torch.cuda.is_current_stream_capturing():
+            self._captured = True  # a graph now holds this binding's addresses (set_motor_strength)
         self._native.step_dev(self.seed, self._step_dev, self._stream())
         if self._cmd_curriculum:
             self._command_curriculum()
@@ -379,6 +381,7 @@ class LeggedRobot(BaseTask):
             :, self.env_id_offset:self.env_id_offset + n].contiguous()
         if not getattr(dr, "randomize_kp_kd", False):
             self.kp_kd_multipliers.fill_(1.0)
+        self._init_actuator_randomisation()  # after every existing setup draw: those keep their values
         self.default_dof_pos = torch.tensor([self.cfg.init_state.default_joint_angles[nm] for nm in self.dof_names],
                                             device=dev).unsqueeze(0)
         self._dof_state3[..., 0] = self.default_dof_pos
@@ -456,8 +459,78 @@ class LeggedRobot(BaseTask):
             "terrain_mesh": self._terrain_mesh, "blew_up": self.blew_up_buf, "blowup_count": self._blowup_count,
             "command_ranges": self._command_ranges_buf, "curriculum_vals": self._curriculum_vals,
             "command_range_log": self._command_range_log if self._cmd_curriculum else None,
+            "action_delay": self.action_delay_substeps, "action_history": self.action_history,
+            "motor_strength": self.motor_strengths,
             **self._sea_buffers,
         })
+
+    # ------------------------------------------------------------------ actuator randomisation
+    def _init_actuator_randomisation(self):
+        """Actuation latency and motor strength (include/lgx.h ABI 8; domain_rand keys of
+        params.actuator_randomisation). Buffers exist, and are bound, only when a feature is on or
+        max_action_delay_s > 0; otherwise the three attributes are None and the step is the ideal
+        actuator's. Draws only for an enabled feature, for all global envs and sliced as
+        kp_kd_multipliers is, fixed per env: d_e = round(U(lo, hi) / sim_dt) physics substeps, one
+        strength per env and joint."""
+        n, na, d, dev = self.num_envs, self.num_actions, self.num_dof, self.device
+        total, sl = self.num_envs_total, slice(self.env_id_offset, self.env_id_offset + self.num_envs)
+        ar = prm.actuator_randomisation(self.cfg, self.sim_params.dt)
+        self._action_history_len = H = ar["history_len"]
+        self._action_delay_capacity = H * int(self.cfg.control.decimation)  # substeps
+        self.action_delay_substeps = self.action_history = self.motor_strengths = None
+        self._captured = False
+        if H > 0:
+            self.action_delay_substeps = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.action_history = torch.zeros(n, H, na, device=dev)
+        if ar["delay_on"] and H > 0:  # (a range of [0, 0] s needs no history: nothing to draw)
+            lo, hi = ar["delay_range_s"]
+            delay_s = ((hi - lo) * torch.rand(total, device=dev) + lo)[sl]
+            self.set_action_delay(delay_s)
+        if ar["strength_on"]:
+            lo, hi = ar["strength_range"]
+            self.motor_strengths = ((hi - lo) * torch.rand(total, d, device=dev) + lo)[sl].contiguous()
+
+    def set_action_delay(self, seconds):
+        """Actuation latency of every env: a number of seconds or a tensor [num_envs] of seconds, rounded
+        to physics substeps (round(s / sim_dt)). Written in place (a captured graph keeps replaying
+        on the same address). ValueError when negative, or beyond the capacity the env was built
+        with (domain_rand.max_action_delay_s)."""
+        if self.action_delay_substeps is None:
+            raise ValueError("this env was built without actuation latency support: set "
+                             "domain_rand.max_action_delay_s (or randomize_action_delay) in its config")
+        s = torch.as_tensor(seconds, dtype=torch.float64, device=self.device)
+        if s.dim() not in (0, 1) or (s.dim() == 1 and s.shape[0] != self.num_envs):
+            raise ValueError(f"action delay: a number or a tensor [{self.num_envs}], got shape {list(s.shape)}")
+        sub = torch.round(s / float(self.sim_params.dt))
+        lo, hi = float(sub.min()), float(sub.max())
+        if not (lo >= 0.0 and hi <= self._action_delay_capacity):  # also refuses NaN
+            raise ValueError(f"action delay of {lo:g}..{hi:g} physics substeps is outside 0..{self._action_delay_capacity} "
+                             f"(capacity: {self._action_history_len} control steps, domain_rand.max_action_delay_s)")
+        self.action_delay_substeps.copy_(sub.to(torch.int32).expand(self.num_envs))
+
+    def set_motor_strength(self, value):
+        """Motor strength factors: a number, or a tensor [num_envs] or [num_envs, num_dof]. Written
+        in place once the buffer exists; the first call on an env built without
+        randomize_motor_strength allocates it and re-binds, which a captured graph of this env's
+        step would not see: RuntimeError once a step of this env has been captured (build the env
+        with randomize_motor_strength, or set a strength before the capture).
+        ValueError when negative or not finite."""
+        v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        if v.dim() == 1 and v.shape[0] == self.num_envs:
+            v = v.unsqueeze(1)
+        if v.dim() not in (0, 2) or (v.dim() == 2 and tuple(v.shape) not in ((self.num_envs, 1), (self.num_envs, self.num_dof))):
+            raise ValueError(f"motor strength: a number or a tensor [{self.num_envs}] or [{self.num_envs}, {self.num_dof}], "
+                             f"got shape {list(v.shape)}")
+        if not bool(torch.isfinite(v).all()) or float(v.min()) < 0.0:
+            raise ValueError("motor strength factors must be finite and >= 0")
+        if self.motor_strengths is None:
+            if self._captured:
+                raise RuntimeError("set_motor_strength: this env has no motor_strength buffer and its step has been captured "
+                                   "in a graph, which would go on replaying the old binding; build the env with "
+                                   "domain_rand.randomize_motor_strength or set a strength before the capture")
+            self.motor_strengths = torch.ones(self.num_envs, self.num_dof, device=self.device)
+            self._bind()
+        self.motor_strengths.copy_(v.expand(self.num_envs, self.num_dof))
 
     @property
     def physics_blowups(self):

@@ -87,6 +87,37 @@ def soft_dof_limits(lower, upper, soft):
     return np.stack([m - (F32(0.5) * r) * F32(soft), m + (F32(0.5) * r) * F32(soft)], 1).astype(F32)
 
 
+def actuator_randomisation(cfg, sim_dt):
+    """The actuator keys of cfg.domain_rand (all optional, read with getattr: the shipped config
+    classes do not carry them) -> dict:
+      delay_on / delay_range_s [lo, hi] / max_delay_s   randomize_action_delay, action_delay_range_s,
+                                                        max_action_delay_s (default: the range's upper end)
+      strength_on / strength_range                      randomize_motor_strength, motor_strength_range
+      history_len   H = ceil(round(max_action_delay_s / sim_dt) / decimation): the control steps of
+                    action history the largest latency needs (lgx_task_params.action_history_len)
+    A ValueError when H exceeds LGX_MAX_ACTION_HISTORY or a range is not 0 <= lo <= hi."""
+    dr = cfg.domain_rand
+    delay_on = bool(getattr(dr, "randomize_action_delay", False))
+    lo, hi = (float(v) for v in getattr(dr, "action_delay_range_s", [0.0, 0.0]))
+    max_s = float(getattr(dr, "max_action_delay_s", hi))
+    if not (0.0 <= lo <= hi) or max_s < 0.0:
+        raise ValueError(f"domain_rand.action_delay_range_s {[lo, hi]} / max_action_delay_s {max_s}: need 0 <= lo <= hi")
+    if delay_on and hi > max_s:
+        raise ValueError(f"domain_rand.action_delay_range_s upper end {hi} s exceeds max_action_delay_s {max_s} s")
+    n = int(cfg.control.decimation)
+    max_sub = int(round(max_s / sim_dt))
+    H = -(-max_sub // n)
+    if H > _abi.MAX_ACTION_HISTORY:
+        raise ValueError(f"domain_rand.max_action_delay_s = {max_s} s is {max_sub} physics substeps = {H} control steps "
+                         f"of action history; at most {_abi.MAX_ACTION_HISTORY} (LGX_MAX_ACTION_HISTORY)")
+    slo, shi = (float(v) for v in getattr(dr, "motor_strength_range", [0.9, 1.1]))
+    strength_on = bool(getattr(dr, "randomize_motor_strength", False))
+    if strength_on and not (0.0 <= slo <= shi):
+        raise ValueError(f"domain_rand.motor_strength_range {[slo, shi]}: need 0 <= lo <= hi")
+    return dict(delay_on=delay_on, delay_range_s=[lo, hi], max_delay_s=max_s, history_len=H,
+                strength_on=strength_on, strength_range=[slo, shi])
+
+
 def build_task_params(cfg, model, num_envs, num_envs_total=None, env_id_offset=0, sim_dt=None, go2=True,
                       terrain_shape=None):
     P = _abi.TaskParams()
@@ -118,6 +149,7 @@ def build_task_params(cfg, model, num_envs, num_envs_total=None, env_id_offset=0
     P.control_type = _abi.CONTROL[cfg.control.control_type]
     dr = cfg.domain_rand
     P.randomize_kp_kd = int(getattr(dr, "randomize_kp_kd", False))
+    P.action_history_len = actuator_randomisation(cfg, sdt)["history_len"]
     links = model["links"][1:]
     for i, dn in enumerate(model["dof_names"]):
         P.default_dof_pos[i] = cfg.init_state.default_joint_angles[dn]

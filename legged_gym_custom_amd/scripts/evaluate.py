@@ -6,9 +6,15 @@ command tracking and cost of transport are reported per terrain level x type
 stays as trained: observation noise, pushes, friction / mass / gain randomisation.
 
   python legged_gym/scripts/evaluate.py --task=go2_parkour --num_envs=4096 [--policy student|teacher]
-         [--eval_steps N]
+         [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
 
-One JSON document is printed and written next to the checkpoint (eval_<policy>.json)."""
+--action_delay_ms: a constant actuation latency for all envs (the env is built with the action
+history the largest one needs); several values give one report each under "sweep", on one captured
+loop. --motor_strength: a constant motor strength factor. Without them the config's own actuator
+randomisation applies, as trained.
+
+One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
+eval_<policy>_latency.json)."""
 import argparse
 import json
 import os
@@ -27,10 +33,15 @@ from legged_gym.utils import get_args, get_load_path, task_registry  # noqa: E40
 from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 
-def evaluate(args, policy="student", eval_steps=None, root=None, graph=True):
+def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
+    delays_s = [float(ms) / 1000.0 for ms in (action_delay_ms or [])]
+    if delays_s:  # the capacity the largest delay needs (never less than the config's own)
+        dr = env_cfg.domain_rand
+        own = getattr(dr, "max_action_delay_s", getattr(dr, "action_delay_range_s", [0.0, 0.0])[1])
+        dr.max_action_delay_s = max(float(own), max(delays_s))
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
 
     train_cfg.runner.resume = True
@@ -39,9 +50,16 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True):
     runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg,
                                                       log_root=log_root)
     checkpoint = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
-    report = PolicyEvaluator(env, runner, policy=policy).run(eval_steps, graph=graph)
-    report = dict(task=args.task, checkpoint=checkpoint, iteration=int(runner.current_learning_iteration), **report)
-    out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}.json")
+    ev = PolicyEvaluator(env, runner, policy=policy)
+    head = dict(task=args.task, checkpoint=checkpoint, iteration=int(runner.current_learning_iteration))
+    if len(delays_s) > 1:
+        sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength)
+        report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_latency.json")
+    else:
+        report = dict(**head, **ev.run(eval_steps, graph=graph, action_delay_s=delays_s[0] if delays_s else None,
+                                       motor_strength=motor_strength))
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}.json")
     with open(out, "w") as f:
         json.dump(report, f, indent=1)
     return report, out
@@ -51,9 +69,12 @@ def main(argv=None):
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument("--policy", choices=("student", "teacher"), default="student")
     p.add_argument("--eval_steps", type=int, default=None)
+    p.add_argument("--action_delay_ms", type=lambda s: [float(v) for v in s.split(",")], default=None)
+    p.add_argument("--motor_strength", type=float, default=None)
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
-    report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps)
+    report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
+                         action_delay_ms=own.action_delay_ms, motor_strength=own.motor_strength)
     print(json.dumps(report))
     return report
 

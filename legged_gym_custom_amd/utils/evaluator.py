@@ -46,6 +46,10 @@ def cell_report(cell, dt, weight):
             "cost_of_transport": div(s[5], weight * s[4]), "mean_peak_foot_force": div(s[7], ep)}
 
 
+def _min_max(t, kind):
+    return None if t is None else [kind(t.min()), kind(t.max())]
+
+
 class PolicyEvaluator:
     def __init__(self, env, runner, policy="student"):
         if policy not in ("student", "teacher"):
@@ -132,16 +136,44 @@ class PolicyEvaluator:
         self._graph = g
 
     # ------------------------------------------------------------------ run
-    def run(self, num_steps=None, graph=True):
+    def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None):
         """Evaluate: reset, num_steps x {act, step, accumulate}, reduce, one host read; returns the
         report (JSON-serialisable): per-cell and total entries REPORT_KEYS, None where a cell has
         no data (never NaN).
+
+        action_delay_s / motor_strength: a constant actuation latency (seconds) / motor strength
+        factor for all envs for this run only, set through env.set_action_delay / set_motor_strength
+        (in place: the captured loop keeps replaying); the env's own per-env values are put back, in
+        place, when the run ends. None leaves the env's values. The env must have been built with
+        the capacity (domain_rand.max_action_delay_s). The report's action_delay_substeps /
+        motor_strength are the [min, max] over the envs during the run, None when the env has no
+        such buffer.
 
         num_steps defaults to max_episode_length + 1: the step kernel's rule is time_out =
         episode_length > max_episode_length (lgx_env.hip env_step_kernel, go2.py:186-204), the
         length counting from 0, so by then every env has finished once and `running` is 0.
         graph: replay the captured loop body where the env allows it (GPU, env.graph_capturable);
         False forces the eager loop. Both give bit-identical cells."""
+        env = self.env
+        saved = []  # (buffer, its values before this run)
+        try:
+            if action_delay_s is not None:
+                if env.action_delay_substeps is not None:
+                    saved.append((env.action_delay_substeps, env.action_delay_substeps.clone()))
+                env.set_action_delay(action_delay_s)
+            if motor_strength is not None:
+                had = env.motor_strengths is not None
+                if had:
+                    saved.append((env.motor_strengths, env.motor_strengths.clone()))
+                env.set_motor_strength(motor_strength)  # (the first one allocates: refused once a loop is captured)
+                if not had:
+                    saved.append((env.motor_strengths, torch.ones_like(env.motor_strengths)))
+            return self._run(num_steps, graph)
+        finally:
+            for buf, old in saved:
+                buf.copy_(old)
+
+    def _run(self, num_steps, graph):
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
@@ -163,6 +195,13 @@ class PolicyEvaluator:
         self.last_cells = cells  # [rows, cols, 12] float64, as lgx_eval_reduce wrote them
         return self.report(cells, steps, wall, use_graph)
 
+    def sweep_action_delay(self, delays_s, **run_kwargs):
+        """One report per actuation latency (seconds) of delays_s, each a full run() with that
+        constant latency for all envs. The latency is written in place, so the loop is captured
+        once (at the first run) and replayed for every entry; the env's own latencies are back in
+        place afterwards."""
+        return [self.run(action_delay_s=float(d), **run_kwargs) for d in delays_s]
+
     def report(self, cells, steps=None, wall=None, graph=None):
         env = self.env
         dt, w = float(env.dt), self.mass * self.gravity
@@ -171,6 +210,8 @@ class PolicyEvaluator:
         total = cells.reshape(-1, _abi.EVAL_CELL_COLS).sum(0)
         out = {"policy": self.policy, "num_envs": int(env.num_envs), "num_steps": steps, "dt": dt,
                "nominal_mass": self.mass, "graph": graph, "terrain_levels": rows, "terrain_types": cols,
+               "action_delay_substeps": _min_max(getattr(env, "action_delay_substeps", None), int),
+               "motor_strength": _min_max(getattr(env, "motor_strengths", None), float),
                "total": cell_report(total, dt, w),
                "cells": [[cell_report(cells[r, c], dt, w) for c in range(cols)] for r in range(rows)]}
         if wall is not None and steps:
