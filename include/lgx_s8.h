@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LGX_S8_ABI_VERSION 4
+#define LGX_S8_ABI_VERSION 5
 
 enum { LGX_S8_FWD = 0, LGX_S8_DX = 1, LGX_S8_DW = 2 };  /* GEMM kinds (operand modes above) */
 
@@ -42,7 +42,10 @@ enum {
   LGX_S8_EPI_BIAS = 1,   /* FWD: + bias[n] */
   LGX_S8_EPI_ELU = 2,    /* FWD: then ELU(alpha = 1) */
   LGX_S8_EPI_DELU = 4,   /* DX: * ELU'(z) from the ELU output y = act (S8): y > 0 ? 1 : y + 1 */
-  LGX_S8_EPI_ACCUM = 8   /* DW with split 1: C += result */
+  LGX_S8_EPI_ACCUM = 8,  /* DW with split 1: C += result */
+  /* ABI 5, lgx_s8_heads_fwd only: the tile also runs the PPO loss head on its rows (below) */
+  LGX_S8_EPI_HEAD_ACTOR = 16,  /* the actor's last hidden layer: policy half of the head */
+  LGX_S8_EPI_HEAD_CRITIC = 32  /* the critic's last hidden layer: value half of the head */
 };
 
 typedef struct lgx_s8_gemm_args {
@@ -103,6 +106,45 @@ int32_t lgx_s8_gemm_group(const lgx_s8_gemm_args* args, int32_t n, int32_t kind,
 int32_t lgx_s8_pick_split(const int32_t* M, const int32_t* N, const int32_t* K, int32_t n, int32_t* out);
 int32_t lgx_s8_split(const lgx_s8_split_args* args, int32_t n, void* stream);
 int32_t lgx_s8_reduce(const lgx_s8_reduce_args* args, int32_t n, void* stream);
+
+/* ---- ABI 5: the last forward level with the loss heads in its epilogue. n forward GEMMs as
+ * lgx_s8_gemm_group(LGX_S8_FWD) in one launch, where a problem with LGX_S8_EPI_HEAD_ACTOR /
+ * LGX_S8_EPI_HEAD_CRITIC (at most one of each, listed first; N <= 128 and a multiple of 8, so one
+ * 128-row tile holds whole rows; bias + ELU, C set) is the actor's / critic's last hidden layer
+ * y = ELU(x W^T + b), and its tiles go on, from the rows they hold, with exactly what
+ * lgx_loss_heads_tail (lgx_mlp.h) does after reading y back: the last layer (mu = y W^T + b, or
+ * value = y_c W_c^T + b_c, on y as its S8 hi + lo), the PPO head rows, the last layer's input
+ * gradient dy = (dmu W) * ELU'(y) (or dvalue W_c) in S8 with its column sums, and the head's
+ * partials, per LGX_HEADS_TAIL_ROWS rows, in the same places and the same summation order: the
+ * outputs equal, bit for bit, those of the forward launch followed by lgx_loss_heads_tail on the
+ * same arguments (tests/test_gpu_s8_heads_fwd.py). Actor tiles form the surrogate, the KL, dmu and
+ * the dstd partials, critic tiles the value loss and dvalue; head->ws rows are written in part by
+ * each. `tail`: lgx_heads_tail_args as for lgx_loss_heads_tail (y / yc are not read: H = the
+ * actor problem's N, Hc = the critic problem's N); `s8`: its dmu / dvalue fields and decisions_in;
+ * the de fields and the aux head are NOT run here (lgx_s8_dx_group_aux). head->A <=
+ * LGX_S8_HEADS_MAXA. Decisions (test hook): two tiles hold a row's two halves, so s8->
+ * decisions_out receives bits 0-2 only and decisions_critic (set with it) bits 3-5 of each byte;
+ * the caller ORs them. */
+#define LGX_S8_HEADS_MAX 4       /* problems of one lgx_s8_heads_fwd launch */
+#define LGX_S8_HEADS_MAXA 12
+struct lgx_ppo_head_args;
+struct lgx_heads_s8_args;
+struct lgx_heads_tail_args;
+typedef struct lgx_s8_heads_args {
+  const struct lgx_ppo_head_args* head;
+  const struct lgx_heads_s8_args* s8;
+  const struct lgx_heads_tail_args* tail;
+  uint8_t* decisions_critic;
+} lgx_s8_heads_args;
+int32_t lgx_s8_heads_fwd(const lgx_s8_gemm_args* args, int32_t n, const lgx_s8_heads_args* heads, void* stream);
+/* lgx_s8_gemm_group(args, n, LGX_S8_DX) whose launch also runs the aux head of lgx_loss_heads_fused
+ * / lgx_loss_heads_tail (lgx_mlp.h: the ROA regulariser and the estimator loss with their input
+ * gradients; the same kernel body, so the same out, dp, de / de_s8 / de_cs bit for bit) as its
+ * first ceil(B / 256) blocks. The GEMMs must not read what the aux head writes. n = 0: the aux
+ * head alone. Only the de fields of s8 are read. */
+struct lgx_aux_loss_args;
+int32_t lgx_s8_dx_group_aux(const lgx_s8_gemm_args* args, int32_t n, const struct lgx_aux_loss_args* aux,
+                            const struct lgx_heads_s8_args* s8, void* stream);
 
 /* ---- ABI v2: the rollout's act networks in ONE launch (PPO.act, ppo.py:129-153): the
  * estimator, scan encoder and privileged encoder, the actor on [obs | priv latent | scan latent

@@ -15,9 +15,10 @@ LIBS = {
     "liblgx.so": (["lgx_env.hip"], ["lgx_device.h", "lgx_env_common.h", "lgx_host.h", "lgx_env_host.cpp", "lgx_knobs.h"],
                   ["lgx.h"]),
     # lgx_mlp.hip and lgx_act.hip take the env's Philox from lgx_device.h -> lgx_env_common.h (-> lgx.h)
-    "liblgx_mlp.so": (["lgx_mlp.hip"], ["lgx_knobs.h", "lgx_device.h", "lgx_env_common.h"], ["lgx_mlp.h", "lgx.h"]),
-    "liblgx_s8.so": (["lgx_s8.hip", "lgx_act.hip", "lgx_s8chain.hip"], ["lgx_knobs.h", "lgx_device.h", "lgx_env_common.h"],
-                     ["lgx_s8.h", "lgx.h"]),
+    "liblgx_mlp.so": (["lgx_mlp.hip"], ["lgx_knobs.h", "lgx_device.h", "lgx_env_common.h", "lgx_heads_row.h"],
+                      ["lgx_mlp.h", "lgx.h"]),
+    "liblgx_s8.so": (["lgx_s8.hip", "lgx_act.hip", "lgx_s8chain.hip"], ["lgx_knobs.h", "lgx_device.h", "lgx_env_common.h", "lgx_heads_row.h"],
+                     ["lgx_s8.h", "lgx_mlp.h", "lgx.h"]),  # lgx_heads_row.h: the loss head's row arithmetic (-> lgx_mlp.h)
 }
 OUT = os.path.join(HERE, "lib", "liblgx.so")
 OUT_MLP = os.path.join(HERE, "lib", "liblgx_mlp.so")

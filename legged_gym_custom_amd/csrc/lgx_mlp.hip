@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "../../include/lgx_mlp.h"
+#include "lgx_heads_row.h"  // the PPO head's row arithmetic, shared with lgx_s8.hip
 #include "lgx_device.h"  // philox4x32_10 / u01: the env's counter RNG (the act head's noise)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1402,81 +1403,19 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 }
 
 // ---------------------------------------------------------------- PPO loss head
-#ifndef LGX_HT
-#define LGX_HT 256
-#endif
-constexpr int HT = LGX_HT;  // threads per block (rows per block and grid-stride pass)
-// the loss heads' cross-wave scratch (red[4 * ...]) holds at most 4 waves
-static_assert(HT % 64 == 0 && HT >= 64 && HT <= 256, "LGX_HT: 64..256 threads, whole waves");
+using lgxh::HT;  // threads per block of the loss heads (rows per block and grid-stride pass)
+using lgxh::block_sum;
+using lgxh::last_block;
+using lgxh::final_sum;
 // one row per thread (grid-stride loops, so any grid is correct; fewer blocks measured slower)
 __host__ __device__ inline unsigned head_grid(int B) { return (unsigned)((B + HT - 1) / HT); }
-constexpr int HMAXA = 16;   // max actions
-
-// block-wide sum of NV values per thread into red[NV] (thread 0 holds the result)
-template <int NV>
-__device__ void block_sum(float (&v)[NV], float* red) {
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    float x = v[k];
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    v[k] = x;
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) red[wv * NV + k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      float t = red[k];
-      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t += red[w * NV + k];  // waves in order
-      v[k] = t;
-    }
-}
-
-// The last block to finish reduces the per-block partials. Thread 0 wrote this block's
-// partials: it alone releases them (agent scope) before the counter — an agent-scope fence
-// by every thread of every block costs microseconds per block — and the last block's
-// threads acquire before they read the other blocks' partials.
-__device__ bool last_block(uint32_t* counter, unsigned nblk = 0) {
-  __shared__ bool last;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    last = atomicAdd(counter, 1u) == (nblk ? nblk : gridDim.x) - 1;
-  }
-  __syncthreads();
-  if (last) __threadfence();
-  return last;
-}
-
-// Sum of the NV-wide partial rows ws[b * stride + k] over b < nblk, by the whole block: a
-// fixed assignment (thread t takes rows t, t + 256, ...) and the fixed block_sum tree, so
-// the result is deterministic for a given grid. Thread 0 holds the totals.
-template <int NV>
-__device__ void final_sum(const float* ws, int stride, int nblk, float (&v)[NV], float* red) {
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = 0.f;
-  for (int b = threadIdx.x; b < nblk; b += blockDim.x)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] += ws[b * stride + k];
-  __syncthreads();  // red is reused
-  block_sum<NV>(v, red);
-}
+using lgxh::HMAXA;  // max actions
 
 struct HeadRow {
   float logp, ratio;
 };
 
-// One row's action-wide inputs, loaded up front at clamped columns (columns past A repeat the
-// last one and are discarded by selects): no branch around a load, so all of a row's loads
-// are in flight together (a guarded or late load is a round trip of its own, ~0.3 us).
-template <int NA>
-__device__ __forceinline__ void load_cols(const float* __restrict__ x, int i, int A, float (&v)[NA]) {
-#pragma unroll
-  for (int j = 0; j < NA; ++j) v[j] = x[(int64_t)i * A + min(j, A - 1)];
-}
+using lgxh::load_cols;
 
 template <int NA>
 __device__ __forceinline__ HeadRow head_row(const lgx_ppo_head_args& p, int i, const float* stdv, const float* lstd,
@@ -1620,77 +1559,13 @@ __device__ __forceinline__ void ppo_head_bwd_body(const lgx_ppo_head_args& p) {
 }
 
 // ---------------------------------------------------------------- ROA + estimator losses
-// p rows i0 .. i0 + HT - 1, columns [j0, j0 + w) (w <= AUX_CW) staged into st[row][AUX_CW + 1]
-// with coalesced loads: p is usually a column span of the actor-input buffer (row stride
-// ld_p), where one row per thread would touch a separate cache line per lane and load.
-constexpr int AUX_CW = 16;
-constexpr int AUX_EU = 8;  // estimator columns per unrolled group
-// Every load below is unconditional (row and column clamped into range, the extra values
-// discarded by selects or by guarded stores): a load under a branch is a round trip of its
-// own, and these kernels are a few dependent round trips long.
-__device__ __forceinline__ void aux_stage_p(const lgx_aux_loss_args& p, int64_t ldp, int i0, int j0, int w,
-                                            float* st) {
-  __syncthreads();
-  const int n = HT * w;
-  // k / w through a float reciprocal (k < 4096, w <= 16: the product is within 1e-3 of the
-  // quotient and 1/32 of the next integer, so floor is exact) — an integer division by a
-  // run-time w is ~40 instructions, and one wave per SIMD pays every one of them
-  const float rw = 1.f / (float)w;
-  float x[AUX_CW];
-#pragma unroll
-  for (int u = 0; u < AUX_CW; ++u) {
-    const int k = min((int)threadIdx.x + HT * u, n - 1);
-    const int r = (int)(((float)k + 0.5f) * rw), j = k - r * w;
-    x[u] = p.p[(int64_t)min(i0 + r, p.B - 1) * ldp + j0 + j];
-  }
-#pragma unroll
-  for (int u = 0; u < AUX_CW; ++u) {
-    const int k = (int)threadIdx.x + HT * u;
-    const int r = (int)(((float)k + 0.5f) * rw), j = k - r * w;
-    if (k < n) st[r * (AUX_CW + 1) + j] = x[u];
-  }
-  __syncthreads();
-}
-
-// sum_j (p[i, j] - a[i, j])^2 in column order for row i = i0 + threadIdx.x (block-uniform call;
-// rows past B return a value of a clamped row, unused)
-__device__ __forceinline__ float aux_row_sq(const lgx_aux_loss_args& p, int64_t ldp, int i0, float* st) {
-  const int64_t ic = min(i0 + (int)threadIdx.x, p.B - 1);
-  float s = 0.f;
-  for (int j0 = 0; j0 < p.L; j0 += AUX_CW) {
-    const int w = min(AUX_CW, p.L - j0);
-    float a[AUX_CW];
-#pragma unroll
-    for (int j = 0; j < AUX_CW; ++j) a[j] = p.a[ic * p.L + j0 + min(j, w - 1)];
-    aux_stage_p(p, ldp, i0, j0, w, st);
-#pragma unroll
-    for (int j = 0; j < AUX_CW; ++j) {
-      const float d = st[threadIdx.x * (AUX_CW + 1) + j] - a[j];
-      s = j < w ? s + d * d : s;
-    }
-  }
-  return s;
-}
-
-// sum_j (e[i, j] - t[i, j])^2 in column order
-__device__ __forceinline__ float aux_est_sq(const lgx_aux_loss_args& p, int64_t i) {
-  float q = 0.f;
-  for (int j0 = 0; j0 < p.E; j0 += AUX_EU) {
-    float e[AUX_EU], t[AUX_EU];
-#pragma unroll
-    for (int u = 0; u < AUX_EU; ++u) {
-      const int64_t c = i * p.E + min(j0 + u, p.E - 1);
-      e[u] = p.e[c];
-      t[u] = p.t[c];
-    }
-#pragma unroll
-    for (int u = 0; u < AUX_EU; ++u) {
-      const float d = e[u] - t[u];
-      q = j0 + u < p.E ? q + d * d : q;
-    }
-  }
-  return q;
-}
+// (the staging, the row sums and the fused forward + backward body: lgx_heads_row.h)
+using lgxh::AUX_CW;
+using lgxh::AUX_EU;
+using lgxh::aux_stage_p;
+using lgxh::aux_row_sq;
+using lgxh::aux_est_sq;
+using lgxh::aux_loss_fused_core;
 
 __device__ __forceinline__ void aux_loss_fwd_body(const lgx_aux_loss_args& p) {
   __shared__ float red[4 * 2];
@@ -1772,140 +1647,10 @@ __global__ __launch_bounds__(HT) void loss_heads_bwd(lgx_ppo_head_args h, lgx_au
 // narrow output gradients (dmu, dvalue, de) are also written in S8 (bf16 hi / lo interleaved
 // per 8 columns, lgx_s8.h) with one column-sum partial per block of HT = 256 rows — the
 // operands and bias-gradient partials of the update's GEMMs (replaces an lgx_s8_split launch).
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-  const __bf16 x = (__bf16)a, y = (__bf16)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
-// 8 fp32 -> one S8 group (32 B: the 8 bf16 hi values, then the 8 bf16 lo = bf16(x - hi))
-__device__ __forceinline__ void store_s8_group(char* dst, const float (&v)[8]) {
-  float lo[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) lo[e] = v[e] - (float)(__bf16)v[e];
-  typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-  const u32x4_ H = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-  const u32x4_ L = {pack_bf16x2(lo[0], lo[1]), pack_bf16x2(lo[2], lo[3]), pack_bf16x2(lo[4], lo[5]),
-                    pack_bf16x2(lo[6], lo[7])};
-  reinterpret_cast<u32x4_*>(dst)[0] = H;
-  reinterpret_cast<u32x4_*>(dst)[1] = L;
-}
-
-// One row of the fused PPO head (forward sums into v, input gradients dmu / dv, the S8 / fp32
-// gradient rows and the decisions): mu and the value come from the caller (global rows, or the
-// fused last layers of lgx_loss_heads_tail).
-// A row's inputs of the PPO head besides mu and the value (columns past A repeat the last one)
-template <int NA>
-struct HeadIn {
-  float act[NA], os[NA], om[NA];
-  float old_logp, adv, tv, R;
-  __device__ __forceinline__ void load(const lgx_ppo_head_args& p, int i) {
-    load_cols(p.actions, i, p.A, act);
-    load_cols(p.old_sigma, i, p.A, os);
-    load_cols(p.old_mu, i, p.A, om);
-    old_logp = p.old_logp[i];
-    adv = p.adv[i];
-    tv = p.clipped_value ? p.target_values[i] : 0.f;
-    R = p.returns[i];
-  }
-};
-
-template <int NA>
-__device__ __forceinline__ void head_fused_row(const lgx_ppo_head_args& p, const lgx_heads_s8_args& s, int i,
-                                               const float* stdv, const float* lstd, const float (&mu)[NA], float val,
-                                               const HeadIn<NA>& x, float gs, float gv, float (&v)[3 + 2 * NA + 1],
-                                               float (&dmu)[NA], float& dv) {
-  const float(&act)[NA] = x.act;
-  const float(&os)[NA] = x.os;
-  const float(&om)[NA] = x.om;
-  HeadRow h;
-  {
-    const float l2pi = 0.9189385332046727f;  // log(sqrt(2 pi)); head_row's arithmetic
-    float lp = 0.f;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) {
-      const float d = act[j] - mu[j];
-      const float t = -(d * d) / (2.f * stdv[j] * stdv[j]) - lstd[j] - l2pi;
-      lp = j < p.A ? lp + t : lp;
-    }
-    h.logp = lp;
-    h.ratio = expf(lp - x.old_logp);
-  }
-  const float a = x.adv;
-  const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-  // forward (ppo_head_fwd_body)
-  const float s1 = -a * h.ratio, s2 = -a * fminf(fmaxf(h.ratio, lo), hi);
-  const float R = x.R;
-  const float tv = p.clipped_value ? x.tv : val;
-  const float vc = p.clipped_value ? tv + fminf(fmaxf(val - tv, -p.clip), p.clip) : 0.f;
-  const float l1 = (val - R) * (val - R), l2 = (vc - R) * (vc - R);
-  // the discrete decisions (torch's gradient rules: max splits ties, clamp passes on [lo, hi])
-  float w1 = s1 > s2 ? 1.f : (s1 == s2 ? 0.5f : 0.f);
-  float in = (h.ratio >= lo && h.ratio <= hi) ? 1.f : 0.f;
-  float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-  float inv = (val - tv >= -p.clip && val - tv <= p.clip) ? 1.f : 0.f;
-  if (s.decisions_out)
-    s.decisions_out[i] = (uint8_t)((unsigned)(2.f * w1) | ((unsigned)in << 2) | ((unsigned)(2.f * u1) << 3) |
-                                   ((unsigned)inv << 5));
-  // a decisions_in byte with bit 6 set leaves the row its own decisions (near-tie-only replays)
-  const bool forced = s.decisions_in != nullptr && !(s.decisions_in[i] & 0x40u);
-  if (forced) {
-    const unsigned d = s.decisions_in[i];
-    w1 = 0.5f * (float)(d & 3u);
-    in = (float)((d >> 2) & 1u);
-    u1 = 0.5f * (float)((d >> 3) & 3u);
-    inv = (float)((d >> 5) & 1u);
-  }
-  if (!forced) {
-    v[0] += fmaxf(s1, s2);
-    v[1] += p.clipped_value ? fmaxf(l1, l2) : (R - val) * (R - val);
-  } else {  // the forced branch's value (a tie: either)
-    v[0] += w1 > 0.75f ? s1 : (w1 < 0.25f ? s2 : fmaxf(s1, s2));
-    v[1] += p.clipped_value ? (u1 > 0.75f ? l1 : (u1 < 0.25f ? l2 : fmaxf(l1, l2))) : (R - val) * (R - val);
-  }
-  float kl = 0.f;
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    const float dm = om[j] - mu[j];
-    const float t = logf(stdv[j] / os[j] + 1.0e-5f) + (os[j] * os[j] + dm * dm) / (2.f * (stdv[j] * stdv[j])) - 0.5f;
-    kl = j < p.A ? kl + t : kl;
-  }
-  v[2] += kl;
-  // backward (ppo_head_bwd_body)
-  const float w2 = 1.f - w1;
-  const float dratio = gs * (w1 * -a + w2 * -a * in);
-  const float dlogp = dratio * h.ratio;
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    const float d = act[j] - mu[j];
-    const float var = stdv[j] * stdv[j];
-    dmu[j] = j < p.A ? dlogp * d / var : 0.f;
-    if (j < p.A) {
-      if (p.dmu) p.dmu[(int64_t)i * p.A + j] = dmu[j];
-      v[3 + j] += dlogp * (d * d / (var * stdv[j]) - 1.f / stdv[j]);
-      v[3 + NA + j] += dmu[j];
-    }
-  }
-  if (p.clipped_value) {
-    dv = gv * (u1 * 2.f * (val - R) + (1.f - u1) * 2.f * (vc - R) * inv);
-  } else {
-    dv = gv * 2.f * (val - R);
-  }
-  if (p.dvalue) p.dvalue[i] = dv;
-  v[3 + 2 * NA] += dv;
-  if (s.dmu_s8) {
-#pragma unroll
-    for (int g0 = 0; g0 < NA; g0 += 8) {
-      if (g0 >= p.A) break;
-      float q[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) q[e] = g0 + e < NA ? dmu[g0 + e] : 0.f;
-      store_s8_group(static_cast<char*>(s.dmu_s8) + ((int64_t)i * s.ld_dmu + g0) * 4, q);
-    }
-  }
-  if (s.dvalue_s8) {
-    const float q[8] = {dv, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    store_s8_group(static_cast<char*>(s.dvalue_s8) + (int64_t)i * s.ld_dvalue * 4, q);
-  }
-}
+// The row arithmetic (and head_fused_row, one row by one thread) lives in lgx_heads_row.h.
+using lgxh::HeadIn;
+using lgxh::head_fused_row;
+using lgxh::store_s8_group;
 
 // The fused PPO head's block partials (ws, the gradient column sums) and the last block's
 // totals: the losses, the KL, the entropy, dstd (one block per grid x-index)
@@ -1967,69 +1712,6 @@ __device__ __forceinline__ void ppo_head_fused_body(const lgx_ppo_head_args& p, 
   head_block_finish<NA>(p, s, v, red, stdv, lstd, ge);
 }
 
-// nblk: the blocks that take part (blockIdx.x < nblk; 0: the grid's)
-// st: the row staging ([HT][AUX_CW + 1] floats of LDS)
-__device__ __forceinline__ void aux_loss_fused_core(const lgx_aux_loss_args& p, const lgx_heads_s8_args& s,
-                                                    unsigned nblk, float* st) {
-  const unsigned nb = nblk ? nblk : gridDim.x;
-  if (blockIdx.x >= nb) return;
-  constexpr int NV = 2 + 8;  // forward sums | de column sums (E <= 8 on the S8 path)
-  __shared__ float red[4 * NV];
-  const int i0 = blockIdx.x * HT, i = i0 + threadIdx.x;
-  const int64_t ic = min(i, p.B - 1);
-  const float gr = p.g[0] / p.B, ge = p.g[1] / p.B;
-  const int64_t ldp = p.ld_p > 0 ? p.ld_p : p.L;
-  float v[NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = 0.f;
-  const float n = sqrtf(aux_row_sq(p, ldp, i0, st));
-  const float q = aux_est_sq(p, ic);
-  if (i < p.B) {
-    v[0] = n;
-    const float nq = sqrtf(q);  // torch: norm(dim=1).pow(2)
-    v[1] = nq * nq;
-  }
-  const float k = n > 0.f ? gr / n : 0.f;
-  for (int j0 = 0; j0 < p.L; j0 += AUX_CW) {
-    const int w = min(AUX_CW, p.L - j0);
-    float a[AUX_CW];
-#pragma unroll
-    for (int j = 0; j < AUX_CW; ++j) a[j] = p.a[ic * p.L + j0 + min(j, w - 1)];
-    aux_stage_p(p, ldp, i0, j0, w, st);
-#pragma unroll
-    for (int j = 0; j < AUX_CW; ++j)
-      if (i < p.B && j < w) p.dp[ic * p.L + j0 + j] = k * (st[threadIdx.x * (AUX_CW + 1) + j] - a[j]);
-  }
-  float de[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int64_t c = ic * p.E + min(u, p.E - 1);
-    de[u] = u < p.E && i < p.B ? ge * 2.f * (p.e[c] - p.t[c]) : 0.f;
-    v[2 + u] = de[u];
-  }
-  if (i < p.B) {
-    if (p.de)
-      for (int u = 0; u < p.E; ++u) p.de[ic * p.E + u] = de[u];
-    if (s.de_s8) store_s8_group(static_cast<char*>(s.de_s8) + ic * s.ld_de * 4, de);
-  }
-  block_sum<NV>(v, red);
-  if (threadIdx.x == 0) {
-    p.ws[blockIdx.x * 2] = v[0];
-    p.ws[blockIdx.x * 2 + 1] = v[1];
-    if (s.de_cs)
-      for (int u = 0; u < p.E; ++u) s.de_cs[(int64_t)blockIdx.x * p.E + u] = v[2 + u];
-  }
-  if (last_block(p.counter, nb)) {
-    float t[2];
-    final_sum<2>(p.ws, 2, nb, t, red);
-    if (threadIdx.x == 0) {
-      p.out[0] = t[0] / p.B;
-      p.out[1] = t[1] / p.B;
-      *p.counter = 0u;
-    }
-  }
-}
-
 __device__ __forceinline__ void aux_loss_fused_body(const lgx_aux_loss_args& p, const lgx_heads_s8_args& s) {
   __shared__ float st[HT * (AUX_CW + 1)];
   aux_loss_fused_core(p, s, 0, st);
@@ -2045,7 +1727,7 @@ __global__ __launch_bounds__(HT) void loss_heads_fused(lgx_ppo_head_args h, lgx_
 // block = TR rows, 256 threads. LDS (dynamic, floats): the rows' hidden activations y, y_c
 // [TR][H + 4] (then, in place, the input gradients dy, dy_c), W [NA][H + 4], W_c [H_c + 4],
 // mu [TR][NA], value [TR], dmu [TR][NA], dvalue [TR].
-constexpr int TR = LGX_HEADS_TAIL_ROWS;
+using lgxh::TR;
 // per-block phase clocks (dev builds only: -DLGX_TAIL_CLOCK, tools/tail_clock.py): thread 0 of
 // every PPO block writes clock64 deltas of its phases to g_tailclk[block][8]
 #ifdef LGX_TAIL_CLOCK
@@ -2060,20 +1742,7 @@ __host__ __device__ inline size_t tail_lds_floats(int NA, int H, int Hc) {
          2 * (size_t)TR * NA + 2 * TR;
 }
 
-// dot over k < n of two LDS rows (16-B aligned), k in order
-__device__ __forceinline__ float lds_dot(const float* x, const float* w, int n) {
-  float acc = 0.f;
-#pragma unroll 8
-  for (int k = 0; k < n; k += 4) {
-    const float4 a = *reinterpret_cast<const float4*>(x + k);
-    const float4 b = *reinterpret_cast<const float4*>(w + k);
-    acc = fmaf(a.x, b.x, acc);
-    acc = fmaf(a.y, b.y, acc);
-    acc = fmaf(a.z, b.z, acc);
-    acc = fmaf(a.w, b.w, acc);
-  }
-  return acc;
-}
+using lgxh::lds_dot;
 
 template <int NA>
 __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const lgx_heads_s8_args& s,
@@ -2212,10 +1881,8 @@ __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const 
   for (int o = tid; o < TR * NA; o += blockDim.x) {
     const int r = o / NA, j = o % NA;
     const float sd = stdv[j], mu = mus[r * NA + min(j, A - 1)];
-    const float d = hin[r][j] - mu;
-    tlp[r][j] = -(d * d) / (2.f * sd * sd) - lstd[j] - 0.9189385332046727f;
-    const float os = hin[r][NA + j], dm = hin[r][2 * NA + j] - mu;
-    tkl[r][j] = logf(sd / os + 1.0e-5f) + (os * os + dm * dm) / (2.f * (sd * sd)) - 0.5f;
+    tlp[r][j] = lgxh::lp_term(hin[r][j], mu, sd, lstd[j]);
+    tkl[r][j] = lgxh::kl_term(hin[r][2 * NA + j], hin[r][NA + j], mu, sd);
   }
   __syncthreads();
   if (tid < TR) {
@@ -2225,45 +1892,20 @@ __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const 
       float lp = 0.f;
 #pragma unroll
       for (int j = 0; j < NA; ++j) lp = j < A ? lp + tlp[tid][j] : lp;
-      const float ratio = expf(lp - hin[tid][3 * NA]);
-      const float a = hin[tid][3 * NA + 1];
-      const float lo = 1.f - p.clip, hi = 1.f + p.clip;
-      const float s1 = -a * ratio, s2 = -a * fminf(fmaxf(ratio, lo), hi);
-      const float R = hin[tid][3 * NA + 3], val = vals[tid];
-      const float tv = p.clipped_value ? hin[tid][3 * NA + 2] : val;
-      const float vc = p.clipped_value ? tv + fminf(fmaxf(val - tv, -p.clip), p.clip) : 0.f;
-      const float l1 = (val - R) * (val - R), l2 = (vc - R) * (vc - R);
-      float w1 = s1 > s2 ? 1.f : (s1 == s2 ? 0.5f : 0.f);
-      float in = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-      float u1 = l1 > l2 ? 1.f : (l1 == l2 ? 0.5f : 0.f);
-      float inv = (val - tv >= -p.clip && val - tv <= p.clip) ? 1.f : 0.f;
-      if (s.decisions_out)
-        s.decisions_out[i] = (uint8_t)((unsigned)(2.f * w1) | ((unsigned)in << 2) | ((unsigned)(2.f * u1) << 3) |
-                                       ((unsigned)inv << 5));
-      const bool forced = s.decisions_in != nullptr && !(s.decisions_in[i] & 0x40u);
-      if (forced) {
-        const unsigned dd = s.decisions_in[i];
-        w1 = 0.5f * (float)(dd & 3u);
-        in = (float)((dd >> 2) & 1u);
-        u1 = 0.5f * (float)((dd >> 3) & 3u);
-        inv = (float)((dd >> 5) & 1u);
-      }
-      if (!forced) {
-        r4[0] = 0.f + fmaxf(s1, s2);
-        r4[1] = 0.f + (p.clipped_value ? fmaxf(l1, l2) : (R - val) * (R - val));
-      } else {
-        r4[0] = 0.f + (w1 > 0.75f ? s1 : (w1 < 0.25f ? s2 : fmaxf(s1, s2)));
-        r4[1] = 0.f + (p.clipped_value ? (u1 > 0.75f ? l1 : (u1 < 0.25f ? l2 : fmaxf(l1, l2))) : (R - val) * (R - val));
-      }
       float kl = 0.f;
 #pragma unroll
       for (int j = 0; j < NA; ++j) kl = j < A ? kl + tkl[tid][j] : kl;
+      unsigned din;
+      const bool forced = lgxh::decisions_forced(s, i, din);
+      float surr, vloss;
+      const unsigned own =
+          lgxh::actor_row(lp, hin[tid][3 * NA], hin[tid][3 * NA + 1], p.clip, gs, forced, din, surr, r4[3]) |
+          lgxh::critic_row(vals[tid], hin[tid][3 * NA + 3], hin[tid][3 * NA + 2], p.clip, p.clipped_value != 0, gv,
+                           forced, din, vloss, dv);
+      if (s.decisions_out) s.decisions_out[i] = (uint8_t)own;
+      r4[0] = 0.f + surr;
+      r4[1] = 0.f + vloss;
       r4[2] = 0.f + kl;
-      const float w2 = 1.f - w1;
-      const float dratio = gs * (w1 * -a + w2 * -a * in);
-      r4[3] = dratio * ratio;  // dlogp
-      if (p.clipped_value) dv = gv * (u1 * 2.f * (val - R) + (1.f - u1) * 2.f * (vc - R) * inv);
-      else dv = gv * 2.f * (val - R);
       if (p.dvalue) p.dvalue[i] = dv;
       if (s.dvalue_s8) {
         const float q[8] = {dv, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -2279,12 +1921,10 @@ __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const 
     const int r = o / NA, j = o % NA, i = r0 + r;
     float dmu = 0.f, vs = 0.f;
     if (i < p.B && j < A) {
-      const float sd = stdv[j], dlogp = rowv[r][3];
-      const float d = hin[r][j] - mus[r * NA + j];
-      const float var = sd * sd;
-      dmu = dlogp * d / var;
+      float ds;
+      lgxh::dmu_term(rowv[r][3], hin[r][j], mus[r * NA + j], stdv[j], dmu, ds);
       if (p.dmu) p.dmu[(int64_t)i * p.A + j] = dmu;
-      vs = 0.f + dlogp * (d * d / (var * sd) - 1.f / sd);
+      vs = 0.f + ds;
     }
     dmus[r * NA + j] = dmu;
     tvs[r][j] = vs;
@@ -2312,33 +1952,10 @@ __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const 
       const int r = jt / gg, q = jt % gg;
       float* y = critic ? yc + r * PC + 8 * q : ys + r * PH + 8 * q;
       float x[8];
-      if (critic) {
-        const float d = dvs[r];
-        const float4 w0 = *reinterpret_cast<const float4*>(Wc + 8 * q);
-        const float4 w1 = *reinterpret_cast<const float4*>(Wc + 8 * q + 4);
-        x[0] = d * w0.x; x[1] = d * w0.y; x[2] = d * w0.z; x[3] = d * w0.w;
-        x[4] = d * w1.x; x[5] = d * w1.y; x[6] = d * w1.z; x[7] = d * w1.w;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = 0.f;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) {  // a in order; rows past A are zero
-          const float d = dmus[r * NA + a];
-          const float4 w0 = *reinterpret_cast<const float4*>(Ws + a * PH + 8 * q);
-          const float4 w1 = *reinterpret_cast<const float4*>(Ws + a * PH + 8 * q + 4);
-          x[0] = fmaf(d, w0.x, x[0]); x[1] = fmaf(d, w0.y, x[1]); x[2] = fmaf(d, w0.z, x[2]);
-          x[3] = fmaf(d, w0.w, x[3]); x[4] = fmaf(d, w1.x, x[4]); x[5] = fmaf(d, w1.y, x[5]);
-          x[6] = fmaf(d, w1.z, x[6]); x[7] = fmaf(d, w1.w, x[7]);
-        }
-      }
-      const float4 y0 = *reinterpret_cast<const float4*>(y);
-      const float4 y1 = *reinterpret_cast<const float4*>(y + 4);
-      const float yy[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
+      if (critic) lgxh::dv_w8(dvs[r], Wc + 8 * q, x);
+      else lgxh::dmu_w8<NA>(dmus + r * NA, Ws + 8 * q, PH, x);
       float d[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) d[e] = x[e] * (yy[e] > 0.f ? 1.f : yy[e] + 1.f);
-      *reinterpret_cast<float4*>(y) = {d[0], d[1], d[2], d[3]};
-      *reinterpret_cast<float4*>(y + 4) = {d[4], d[5], d[6], d[7]};
+      lgxh::delu8_inplace(x, y, d);
       if (r0 + r < p.B) {
         if (critic) store_s8_group(static_cast<char*>(t.dyc) + ((int64_t)(r0 + r) * t.ld_dyc + 8 * q) * 4, d);
         else store_s8_group(static_cast<char*>(t.dy) + ((int64_t)(r0 + r) * t.ld_dy + 8 * q) * 4, d);
@@ -2355,10 +1972,7 @@ __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const 
     if (!cs) continue;
     const float* y = critic ? yc : ys;
     const int P = critic ? PC : PH;
-    float sum = 0.f;
-#pragma unroll 8
-    for (int r = 0; r < TR; ++r) sum += y[r * P + k];
-    cs[(int64_t)bx * (critic ? Hc : H) + k] = sum;
+    cs[(int64_t)bx * (critic ? Hc : H) + k] = lgxh::col_sum_rows(y + k, P);
   }
   // the block's partials only — no last-block pass (an agent-scope fence per block costs the L2's
   // write-back: ~1 us each): ws[b] = {surr / B, vloss / B, kl / B, dstd partial [A]}, block 0's
@@ -2366,33 +1980,11 @@ __device__ __forceinline__ void ppo_tail_body(const lgx_ppo_head_args& p, const 
   // (lgx_s8_reduce jobs of the caller). Block 0 writes the entropy (a constant) into out[2].
   TCK(4);
   // the block's sums of the rows' values, summed in row order
-  if (tid < NV) {
-    float sum = 0.f;
-    for (int q = 0; q < TR; ++q) {
-      const float x = tid < 3 ? rowv[q][tid]
-                              : (tid < 3 + NA ? tvs[q][tid - 3]
-                                              : (tid < 3 + 2 * NA ? dmus[q * NA + tid - 3 - NA] : dvs[q]));
-      sum += x;
-    }
-    const float inv = 1.f / p.B;
-    float* w = p.ws + (int64_t)bx * (3 + HMAXA);
-    if (tid < 3) w[tid] = sum * inv;
-    else if (tid < 3 + NA) {
-      const int j = tid - 3;
-      if (j < A) w[3 + j] = sum + (bx == 0 ? ge / stdv[j] : 0.f);
-    } else if (tid < 3 + 2 * NA) {
-      const int j = tid - 3 - NA;
-      if (s.dmu_cs && j < A) s.dmu_cs[(int64_t)bx * A + j] = sum;
-    } else if (s.dvalue_cs) {
-      s.dvalue_cs[bx] = sum;
-    }
-  }
+  if (tid < NV) lgxh::partial_value<NA>(p, s, tid, bx, &rowv[0][0], &tvs[0][0], dmus, dvs, stdv, ge);
   TCK(5);
   if (tid == 0) {
     if (bx == 0) {
-      float ent = 0.f;
-      for (int j = 0; j < A; ++j) ent += 0.5f + 0.9189385332046727f + lstd[j];
-      p.out[2] = ent;
+      p.out[2] = lgxh::entropy_of(lstd, A);
     }
   }
 #ifdef LGX_TAIL_CLOCK
@@ -3289,6 +2881,7 @@ int32_t lgx_ppo_tail(const lgx_ppo_tail_args* a, void* stream) {
     };
     const int64_t segs[2][2] = {{a->main_lo, a->main_hi}, {a->est_lo, a->est_hi}};
     bool ok = true;
+    bool covered[LGX_TAIL_S8_MAX] = {};  // entry i lies in one of the two segments
     for (int o = 0; o < 2 && ok; ++o) {
       int64_t cur = segs[o][0];
       for (int i = 0; i < a->n_s8 && ok;) {
@@ -3300,6 +2893,7 @@ int32_t lgx_ppo_tail(const lgx_ppo_tail_args* a, void* stream) {
           if (w0 < cur) return fail("lgx_ppo_tail: overlapping S8 weights");
           ok = add(cur, w0, o, 0, 0) && add(w0, w1, o, i, j - i);
           cur = w1;
+          for (int q = i; q < j; ++q) covered[q] = true;
         } else if (w0 < segs[o][1] && w1 > segs[o][0]) {
           return fail("lgx_ppo_tail: an S8 weight straddles a segment boundary");
         }
@@ -3309,6 +2903,9 @@ int32_t lgx_ppo_tail(const lgx_ppo_tail_args* a, void* stream) {
     }
     ok = ok && add(a->adapt_lo, a->adapt_hi, 2, 0, 0);
     if (!ok) return fail("lgx_ppo_tail: too many ranges");
+    // a weight in neither segment would never be re-split: its S8 copy would go stale silently
+    for (int i = 0; i < a->n_s8; ++i)
+      if (!covered[i]) return fail("lgx_ppo_tail: an S8 weight lies in neither the main nor the estimator segment");
     k.nr = nr;
     k.r[nr].blk0 = blk;
     hipLaunchKernelGGL(lgxm::tail_norms, dim3(lgxm::TAIL_BLOCKS), dim3(256), 0, s, *a);

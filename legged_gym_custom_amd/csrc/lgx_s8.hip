@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "../../include/lgx_s8.h"
+#include "lgx_heads_row.h"  // the PPO head's row arithmetic, shared with lgx_mlp.hip (-> lgx_mlp.h)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -115,8 +116,13 @@ struct Group {
   int nunits;
   uint16_t ustart[9];
   uint16_t units[UMAX];
+  // DX only (lgx_s8_dx_group_aux): the launch's first naux blocks run the aux loss head
+  int naux;
+  lgx_aux_loss_args aux;
+  lgx_heads_s8_args auxs;
 };
 static_assert(sizeof(Group) <= 4096, "kernel argument segment");
+static_assert(lgxh::HT == Cfg::NT, "the aux head's 256-row blocks are the GEMM's blocks");
 
 // An operand's staging geometry (one K step).
 // T = the tile's extent along this operand (BM for A, BN for B); NW = waves of the block.
@@ -395,7 +401,19 @@ __global__ __launch_bounds__(Cfg::NT, 2) __attribute__((amdgpu_waves_per_eu(1, 2
   constexpr int STAGE = OA::IMG + OB::IMG;
   extern __shared__ __align__(16) char lds[];
 
-  const int x = blockIdx.x & 7, jb = blockIdx.x >> 3;
+  int bid = blockIdx.x;
+  if constexpr (KIND == LGX_S8_DX) {
+    // the aux loss head's blocks in front of the tiles (they are a few dependent memory round
+    // trips long and nearly idle: beside the tiles they cost little, alone a launch of ~26 us)
+    if (g.naux > 0) {
+      if (bid < g.naux) {
+        lgxh::aux_loss_fused_core(g.aux, g.auxs, (unsigned)g.naux, reinterpret_cast<float*>(lds));
+        return;
+      }
+      bid -= g.naux;
+    }
+  }
+  const int x = bid & 7, jb = bid >> 3;
   if (jb >= g.per_xcd) return;
   int pi = 0, l = -1;
   if (g.nunits > 0) {
@@ -719,6 +737,405 @@ __global__ __launch_bounds__(Cfg::NT, 2) __attribute__((amdgpu_waves_per_eu(1, 2
       }
     }
   }
+}
+
+// ---------------------------------------------------------------- FWD with the loss heads in the epilogue
+// lgx_s8_heads_fwd: the last forward level. A tile of the actor's / critic's last hidden layer
+// (N <= 128: whole rows) keeps its 128 rows in the fp32 LDS image after bias + ELU + the S8 store
+// (as the S8-rounded hi + lo, the values lgx_loss_heads_tail would read back) and runs on them the
+// last layer, the PPO head rows, the last layer's input gradient and the partials — every
+// expression from lgx_heads_row.h, every sum in lgx_loss_heads_tail's order (bit-equal outputs).
+// K loop and image as lgxs::s8_gemm_kernel<LGX_S8_FWD>. LDS past the image: the last layer's
+// weights, one 64-row pass of the head's per-action terms, the row values: 81,280 B in all, so
+// 2 blocks per CU (160 KB) as the other kinds. The rows' head inputs, the weights and std are
+// requested before the K loop (their latency runs under it); no load sits inside a store loop.
+constexpr int HPMAX = LGX_S8_HEADS_MAX, HNA = LGX_S8_HEADS_MAXA;
+constexpr int HPW = BN + 4;        // LDS pitch of the last layer's weight rows (floats)
+constexpr int HPASS = 64;          // rows per pass of the actor tile's head stages
+constexpr int HNV = 3 + 2 * HNA + 1;
+struct HLds {  // float offsets
+  static constexpr int IMG = 0, W = Cfg::BM * CP, TLP = W + HNA * HPW, TKL = TLP + HPASS * HNA,
+                       ROWV = TKL + HPASS * HNA, STD = ROWV + HPASS * 4, LSTD = STD + 16, BIAS = LSTD + 16,
+                       END = BIAS + 16;
+};
+static_assert(HLds::END * 4 <= 80 * 1024, "two blocks per CU");
+static_assert(HNA * BN == 6 * Cfg::NT && Cfg::BM * HNA == 6 * Cfg::NT && HPASS * HNA == 3 * Cfg::NT, "head thread maps");
+static_assert(Cfg::BM * 4 <= HPASS * HNA && lgxh::TR == 32, "critic row values fit the term arrays");
+struct HGroup {
+  int n, ntiles;
+  int start[HPMAX + 1];
+  Prob p[HPMAX];
+  lgx_ppo_head_args h;
+  lgx_heads_s8_args s;
+  lgx_heads_tail_args t;
+  uint8_t* dec_critic;
+};
+static_assert(sizeof(HGroup) <= 4096, "kernel argument segment");
+
+__global__ __launch_bounds__(Cfg::NT, 2) __attribute__((amdgpu_waves_per_eu(1, 2))) void s8_heads_fwd_kernel(HGroup g) {
+  constexpr int BM = Cfg::BM, NW = Cfg::NW, NT = Cfg::NT;
+  using OA = Op<false, BM, NW>;
+  using OB = Op<false, BN, NW>;
+  constexpr int STAGE = OA::IMG + OB::IMG;
+  static_assert(2 * STAGE <= HLds::W * 4, "the stages end before the head's arrays");
+  extern __shared__ __align__(16) char lds[];
+  float* const fl = reinterpret_cast<float*>(lds);
+
+  const int t = blockIdx.x;
+  if (t >= g.ntiles) return;
+  int pi = 0;
+  while (pi + 1 < g.n && t >= g.start[pi + 1]) ++pi;
+  const Prob& P = g.p[pi];
+  const int M = P.M, N = P.N;
+  const int l = t - g.start[pi];
+  const int n0 = (l % P.tiles_n) * BN, tm = l / P.tiles_n, m0 = tm * BM;
+  const int nk = (P.K + BK - 1) / BK;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave % Cfg::WR) * 64, wn = (wave / Cfg::WR) * 64;
+  const int kind = (P.epi & LGX_S8_EPI_HEAD_ACTOR) ? 1 : ((P.epi & LGX_S8_EPI_HEAD_CRITIC) ? 2 : 0);
+  const lgx_ppo_head_args& hp = g.h;
+  const int A = hp.A;
+
+  const uint32_t lds0 = (uint32_t)(uintptr_t)((LDS_AS char*)lds);
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  uint32_t offA[OA::PW], offB[OB::PW];
+  OA::offsets(offA, wave, lane, m0, M, P.lda, 0);
+  OB::offsets(offB, wave, lane, n0, N, P.ldb, 0);
+  auto issue = [&](int stage, int step) {
+    const uint32_t st = lds0 + (uint32_t)(stage * STAGE);
+    OA::issue(P.A + step * OA::step_bytes(P.lda), offA, st, wv);
+    OB::issue(P.B + step * OB::step_bytes(P.ldb), offB, st + OA::IMG, wv);
+  };
+  if (nk > 0) issue(0, 0);
+#ifdef LGX_S8_CLOCK  // thread 0's phase account (tools/heads_fwd_clock.py): g_s8clk[block][12]
+  uint64_t hkl = clock64();
+  const uint64_t hk0 = hkl;
+  uint32_t hck[6] = {0, 0, 0, 0, 0, 0};  // K loop | bias, ELU, y store | last layer | head rows | level 0 + stores | partials, column sums
+#define HCK(q) do { const uint64_t t_ = clock64(); hck[q] += (uint32_t)(t_ - hkl); hkl = t_; } while (0)
+  auto hck_out = [&]() {
+    if (threadIdx.x == 0 && g_s8clk != nullptr) {
+      uint32_t* o = g_s8clk + (size_t)blockIdx.x * 12;
+      for (int q = 0; q < 6; ++q) o[q] = hck[q];
+      o[6] = (uint32_t)(clock64() - hk0);
+      o[7] = (uint32_t)((P.epi & LGX_S8_EPI_HEAD_ACTOR) ? 1 : 2);
+      o[8] = (uint32_t)nk;
+    }
+  };
+#else
+#define HCK(q) do { } while (0)
+  auto hck_out = [] {};
+#endif
+
+  // ---- the head's inputs, requested behind step 0's DMA: thread (q) owns (row, action) pairs
+  // o = tid + 256 q -> (o / HNA, o % HNA) of the tile (actions, old sigma, old mu at clamped
+  // indices); thread r < 128 owns row r's scalars
+  float hact[6], hos[6], hom[6], hr0 = 0.f, hr1 = 0.f, wreg[6], sreg = 0.f;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) hact[q] = hos[q] = hom[q] = wreg[q] = 0.f;
+  if (kind == 1) {
+    const int H = g.t.H;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const int o = tid + NT * q, r = o / HNA, j = o % HNA;
+      const int64_t at = (int64_t)std::min(m0 + r, M - 1) * A + std::min(j, A - 1);
+      hact[q] = hp.actions[at];
+      hos[q] = hp.old_sigma[at];
+      hom[q] = hp.old_mu[at];
+      const int a = o / H;  // the last layer's weights [A][H] (rows past A zero)
+      wreg[q] = a < A ? g.t.W[std::min(o, A * H - 1)] : 0.f;
+    }
+    if (tid < BM) {
+      const int i = std::min(m0 + tid, M - 1);
+      hr0 = hp.old_logp[i];
+      hr1 = hp.adv[i];
+    }
+    if (tid < 16) sreg = hp.std[std::min(tid, A - 1)];
+    else if (tid < 32) sreg = g.t.b[std::min(tid - 16, A - 1)];
+  } else if (kind == 2) {
+    if (tid < BM) {
+      const int i = std::min(m0 + tid, M - 1);
+      hr0 = hp.returns[i];
+      hr1 = hp.clipped_value ? hp.target_values[i] : 0.f;
+    }
+    wreg[0] = g.t.Wc[std::min(tid, g.t.Hc - 1)];
+    if (tid == 16) sreg = g.t.bc[0];
+  }
+  if (kind == 1) {
+    const int H = g.t.H;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const int o = tid + NT * q, a = o / H, k = o % H;
+      if (a < HNA) fl[HLds::W + a * HPW + k] = wreg[q];
+    }
+    if (tid < 16) {
+      fl[HLds::STD + tid] = sreg;
+      fl[HLds::LSTD + tid] = logf(sreg);
+    } else if (tid < 32) {
+      fl[HLds::BIAS + tid - 16] = sreg;
+    }
+  } else if (kind == 2) {
+    if (tid < g.t.Hc) fl[HLds::W + tid] = wreg[0];
+    if (tid == 16) fl[HLds::BIAS] = sreg;
+  }
+
+  f32x4 acc[4][NJ];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto compute = [&](int stage) {
+    const char* st = lds + stage * STAGE;
+    bf16x8 ah[4], al[4], bh[NJ], bl[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) OB::frag(st + OA::IMG, wn + 16 * j, 0, lane, bh[j], bl[j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) OA::frag(st, wm + 16 * i, 0, lane, ah[i], al[i]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+        S8_MFMA_ORDER();
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+        S8_MFMA_ORDER();
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        S8_MFMA_ORDER();
+      }
+  };
+  for (int k = 0; k < nk; ++k) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_barrier" ::: "memory");
+    if (k + 1 < nk) issue((k + 1) & 1, k + 1);
+    compute(k & 1);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  HCK(0);
+
+  // ---- the fp32 tile into LDS (MFMA C/D map: col = lane & 15, row = (lane >> 4) * 4 + r)
+  float* const img = fl + HLds::IMG;
+  {
+    const int ec = lane & 15, er = (lane >> 4) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) img[(wm + 16 * i + er + r) * CP + wn + 16 * j + ec] = acc[i][j][r];
+  }
+  __syncthreads();
+  if (kind == 0) {  // a plain forward problem sharing the launch
+    epi_act<LGX_S8_FWD, NT, BM, BN, CP>(P, img, m0, n0, tm * (BM / LGX_S8_TILE_M), tid);
+    return;
+  }
+  // ---- bias + ELU, the S8 store of y (epi_act's FWD arithmetic), and y back into the image as
+  // hi + lo; rows past M as zeros (lgx_loss_heads_tail's rows past B)
+  {
+    constexpr int G = BN / 8, RS = NT / G;
+    const int gq = tid % G, r0 = tid / G, n = 8 * gq;  // n0 = 0: one column tile
+    float bias[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bias[e] = n + e < N ? P.bias[n + e] : 0.f;
+#pragma unroll
+    for (int it = 0; it < BM / RS; ++it) {
+      const int row = r0 + RS * it, m = m0 + row;
+      if (n >= N) continue;  // groups past N are never read
+      float* ip = img + row * CP + n;
+      float v[8];
+      if (m < M) {
+        const f32x4 t0 = *reinterpret_cast<const f32x4*>(ip);
+        const f32x4 t1 = *reinterpret_cast<const f32x4*>(ip + 4);
+        const float u[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = n + e < N ? elu(u[e] + bias[e]) : 0.f;  // zero pad columns
+        store_s8(P.C + (int64_t)m * P.ldc + (n >> 3) * 32, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const __bf16 h = (__bf16)v[e];
+          const __bf16 lo = (__bf16)(v[e] - (float)h);
+          v[e] = (float)h + (float)lo;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+      }
+      *reinterpret_cast<f32x4*>(ip) = f32x4{v[0], v[1], v[2], v[3]};
+      *reinterpret_cast<f32x4*>(ip + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    }
+  }
+  __syncthreads();
+  HCK(1);
+
+  const lgx_heads_s8_args& hs = g.s;
+  const lgx_heads_tail_args& ht = g.t;
+  float* const Wl = fl + HLds::W;
+  float* const tlp = fl + HLds::TLP;   // log-prob terms, then the std-gradient terms (tvs)
+  float* const tkl = fl + HLds::TKL;   // KL terms, then dmu
+  float* const rowv = fl + HLds::ROWV;
+  const float* const stdv = fl + HLds::STD;
+  const float* const lstd = fl + HLds::LSTD;
+  const float gs = hp.g[0] / hp.B, gv = hp.g[1] / hp.B, ge = hp.g[2];
+  const int bx0 = m0 / lgxh::TR;  // the tile's first partial
+
+  if (kind == 2) {
+    // ---- critic tile: all 128 rows at once. rowv [128][4] over the term arrays, dvs [128]
+    const int Hc = ht.Hc, Gc = Hc / 8;
+    float* const rv = tlp;
+    float* const dvs = tkl;
+    if (tid < BM) {
+      const int i = m0 + tid;
+      const float val = lgxh::lds_dot(img + tid * CP, Wl, Hc) + fl[HLds::BIAS];
+      float vl = 0.f, dv = 0.f;
+      if (i < M) {
+        if (ht.value_out) ht.value_out[i] = val;
+        unsigned din;
+        const bool forced = lgxh::decisions_forced(hs, i, din);
+        float vloss;
+        const unsigned own = lgxh::critic_row(val, hr0, hr1, hp.clip, hp.clipped_value != 0, gv, forced, din, vloss, dv);
+        if (g.dec_critic) g.dec_critic[i] = (uint8_t)own;
+        vl = 0.f + vloss;
+        if (hp.dvalue) hp.dvalue[i] = dv;
+        if (hs.dvalue_s8) {
+          const float q[8] = {dv, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          lgxh::store_s8_group(static_cast<char*>(hs.dvalue_s8) + (int64_t)i * hs.ld_dvalue * 4, q);
+        }
+      }
+      rv[tid * 4 + 1] = vl;
+      dvs[tid] = dv;
+    }
+    __syncthreads();
+    HCK(3);  // (the critic's last layer is one dot per row: counted with its head rows)
+    for (int it = tid; it < BM * Gc; it += NT) {
+      const int row = it / Gc, qg = it % Gc;
+      float x[8], d[8];
+      lgxh::dv_w8(dvs[row], Wl + 8 * qg, x);
+      lgxh::delu8_inplace(x, img + row * CP + 8 * qg, d);
+      if (m0 + row < M)
+        lgxh::store_s8_group(static_cast<char*>(ht.dyc) + ((int64_t)(m0 + row) * ht.ld_dyc + 8 * qg) * 4, d);
+    }
+    if (tid < 2 * (BM / lgxh::TR)) {
+      const int sb = tid >> 1, k = (tid & 1) ? HNV - 1 : 1;
+      if (m0 + lgxh::TR * sb < M)
+        lgxh::partial_value<HNA>(hp, hs, k, bx0 + sb, rv + sb * lgxh::TR * 4, rv, rv, dvs + sb * lgxh::TR, stdv,
+                                 ge);  // (its k read rowv and dvs only)
+    }
+    __syncthreads();
+    HCK(4);
+    if (ht.dyc_cs)
+      for (int o = tid; o < (BM / lgxh::TR) * Hc; o += NT) {
+        const int sb = o / Hc, k = o % Hc;
+        if (m0 + lgxh::TR * sb < M)
+          ht.dyc_cs[(int64_t)(bx0 + sb) * Hc + k] = lgxh::col_sum_rows(img + sb * lgxh::TR * CP + k, CP);
+      }
+    HCK(5);
+    hck_out();
+    return;
+  }
+
+  // ---- actor tile. The last layer for every (row, action) pair of the thread (k in order)
+  const int H = ht.H, G = H / 8;
+  float mu[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    const int o = tid + NT * q, r = o / HNA, j = o % HNA;
+    mu[q] = 0.f;
+    if (j < A) {
+      mu[q] = lgxh::lds_dot(img + r * CP, Wl + j * HPW, H) + fl[HLds::BIAS + j];
+      if (ht.mu_out && m0 + r < M) ht.mu_out[(int64_t)(m0 + r) * A + j] = mu[q];
+    }
+  }
+  float* const tvs = tlp;
+  float* const dmus = tkl;
+  HCK(2);
+#pragma unroll
+  for (int ps = 0; ps < BM / HPASS; ++ps) {
+    const int rb = HPASS * ps;  // the pass's first tile row
+    // (1) each action's log-prob and KL terms
+#pragma unroll
+    for (int qq = 0; qq < 3; ++qq) {
+      const int q = 3 * ps + qq, o = tid + NT * q, lr = o / HNA - rb, j = o % HNA;
+      tlp[lr * HNA + j] = lgxh::lp_term(hact[q], mu[q], stdv[j], lstd[j]);
+      tkl[lr * HNA + j] = lgxh::kl_term(hom[q], hos[q], mu[q], stdv[j]);
+    }
+    __syncthreads();
+    // (2) per row (thread rb + lr holds its scalars): the sums in action order, the policy half
+    if (tid >= rb && tid < rb + HPASS) {
+      const int lr = tid - rb, i = m0 + tid;
+      float r4[4] = {0.f, 0.f, 0.f, 0.f};
+      if (i < M) {
+        float lp = 0.f, kl = 0.f;
+#pragma unroll
+        for (int j = 0; j < HNA; ++j) lp = j < A ? lp + tlp[lr * HNA + j] : lp;
+#pragma unroll
+        for (int j = 0; j < HNA; ++j) kl = j < A ? kl + tkl[lr * HNA + j] : kl;
+        unsigned din;
+        const bool forced = lgxh::decisions_forced(hs, i, din);
+        float surr;
+        const unsigned own = lgxh::actor_row(lp, hr0, hr1, hp.clip, gs, forced, din, surr, r4[3]);
+        if (hs.decisions_out) hs.decisions_out[i] = (uint8_t)own;
+        r4[0] = 0.f + surr;
+        r4[2] = 0.f + kl;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) rowv[lr * 4 + k] = r4[k];
+    }
+    __syncthreads();
+    // (3) each action's dmu and std-gradient term (over the dead term arrays)
+#pragma unroll
+    for (int qq = 0; qq < 3; ++qq) {
+      const int q = 3 * ps + qq, o = tid + NT * q, lr = o / HNA - rb, j = o % HNA, i = m0 + rb + lr;
+      float dmu = 0.f, vs = 0.f;
+      if (i < M && j < A) {
+        float ds;
+        lgxh::dmu_term(rowv[lr * 4 + 3], hact[q], mu[q], stdv[j], dmu, ds);
+        if (hp.dmu) hp.dmu[(int64_t)i * A + j] = dmu;
+        vs = 0.f + ds;
+      }
+      dmus[lr * HNA + j] = dmu;
+      tvs[lr * HNA + j] = vs;
+    }
+    __syncthreads();
+    HCK(3);
+    if (hs.dmu_s8) {  // the rows' dmu as S8 groups (columns past A zero)
+      constexpr int GN = (HNA + 7) / 8;
+      for (int o = tid; o < HPASS * GN; o += NT) {
+        const int lr = o / GN, g0 = 8 * (o % GN), i = m0 + rb + lr;
+        if (i >= M || g0 >= A) continue;
+        float q[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q[e] = g0 + e < HNA ? dmus[lr * HNA + g0 + e] : 0.f;
+        lgxh::store_s8_group(static_cast<char*>(hs.dmu_s8) + ((int64_t)i * hs.ld_dmu + g0) * 4, q);
+      }
+    }
+    // the last layer's input gradient in place of y: (dmu W) * ELU'(y)
+    for (int it = tid; it < HPASS * G; it += NT) {
+      const int lr = it / G, qg = it % G, row = rb + lr;
+      float x[8], d[8];
+      lgxh::dmu_w8<HNA>(dmus + lr * HNA, Wl + 8 * qg, HPW, x);
+      lgxh::delu8_inplace(x, img + row * CP + 8 * qg, d);
+      if (m0 + row < M)
+        lgxh::store_s8_group(static_cast<char*>(ht.dy) + ((int64_t)(m0 + row) * ht.ld_dy + 8 * qg) * 4, d);
+    }
+    // the pass's two partials: every value but the critic tile's (value loss, dvalue sum)
+    if (tid < (HPASS / lgxh::TR) * HNV) {
+      const int sb = tid / HNV, k = tid % HNV;
+      if (k != 1 && k != HNV - 1 && m0 + rb + lgxh::TR * sb < M)
+        lgxh::partial_value<HNA>(hp, hs, k, bx0 + rb / lgxh::TR + sb, rowv + sb * lgxh::TR * 4,
+                                 tvs + sb * lgxh::TR * HNA, dmus + sb * lgxh::TR * HNA, rowv, stdv, ge);  // (no dvs)
+    }
+    __syncthreads();
+    HCK(4);
+  }
+  if (bx0 == 0 && tid == 0) hp.out[2] = lgxh::entropy_of(lstd, A);
+  if (ht.dy_cs)
+    for (int o = tid; o < (BM / lgxh::TR) * H; o += NT) {
+      const int sb = o / H, k = o % H;
+      if (m0 + lgxh::TR * sb < M)
+        ht.dy_cs[(int64_t)(bx0 + sb) * H + k] = lgxh::col_sum_rows(img + sb * lgxh::TR * CP + k, CP);
+    }
+  HCK(5);
+  hck_out();
 }
 
 // ---------------------------------------------------------------- fp32 -> S8 (+ column sums)
@@ -1045,7 +1462,7 @@ static void launch_gemm(const lgxs::Group& g, hipStream_t s) {
                               lds);
     attr = true;
   }
-  hipLaunchKernelGGL((lgxs::s8_gemm_kernel<KIND>), dim3(8 * g.per_xcd), dim3(lgxs::Cfg::NT), lds, s, g);
+  hipLaunchKernelGGL((lgxs::s8_gemm_kernel<KIND>), dim3(8 * g.per_xcd + g.naux), dim3(lgxs::Cfg::NT), lds, s, g);
 }
 
 extern "C" {
@@ -1077,17 +1494,27 @@ int32_t lgx_s8_pick_split(const int32_t* M, const int32_t* N, const int32_t* K, 
   return 0;
 }
 
-int32_t lgx_s8_gemm_group(const lgx_s8_gemm_args* a, int32_t n, int32_t kind, void* stream) {
+}  // extern "C"
+
+static int32_t gemm_group(const lgx_s8_gemm_args* a, int32_t n, int32_t kind, const lgx_aux_loss_args* aux,
+                          const lgx_heads_s8_args* auxs, void* stream) {
   if (n < 0 || n > LGX_S8_GROUP_MAX) return fail("lgx_s8_gemm_group: 0 <= n <= LGX_S8_GROUP_MAX");
   if (kind < LGX_S8_FWD || kind > LGX_S8_DW) return fail("lgx_s8_gemm_group: unknown kind");
   lgxs::Group g;
   memset(&g, 0, sizeof g);
+  if (aux) {
+    g.naux = (aux->B + lgxh::HT - 1) / lgxh::HT;
+    g.aux = *aux;
+    g.auxs = *auxs;
+  }
   int np = 0, acc = 0;
   for (int i = 0; i < n; ++i) {
     const lgx_s8_gemm_args& q = a[i];
     if (q.M < 0 || q.N < 0 || q.K < 0) return fail("lgx_s8_gemm_group: negative size");
     if (q.M == 0 || q.N == 0) continue;
     if (!q.A || !q.B) return fail("lgx_s8_gemm_group: null operand");
+    if (q.epilogue & (LGX_S8_EPI_HEAD_ACTOR | LGX_S8_EPI_HEAD_CRITIC))
+      return fail("lgx_s8_gemm_group: the loss-head epilogues run through lgx_s8_heads_fwd");
     if (q.lda % 8 || q.ldb % 8) return fail("lgx_s8_gemm_group: S8 pitches must be multiples of 8");
     if ((((uintptr_t)q.A) | ((uintptr_t)q.B)) & 15) return fail("lgx_s8_gemm_group: operands must be 16-B aligned");
     const bool atr = kind == LGX_S8_DW, btr = kind != LGX_S8_FWD;
@@ -1144,7 +1571,7 @@ int32_t lgx_s8_gemm_group(const lgx_s8_gemm_args* a, int32_t n, int32_t kind, vo
   }
   g.n = np;
   g.per_xcd = acc;
-  if (np == 0) return 0;
+  if (np == 0 && g.naux == 0) return 0;
   if (kind == LGX_S8_DW && dw_xcd_units()) deal_units(g);
   hipStream_t s = (hipStream_t)stream;
   if (kind == LGX_S8_FWD && fwd_register_epilogue()) launch_fwd(g, s);
@@ -1152,6 +1579,108 @@ int32_t lgx_s8_gemm_group(const lgx_s8_gemm_args* a, int32_t n, int32_t kind, vo
   else if (kind == LGX_S8_DX) launch_gemm<LGX_S8_DX>(g, s);
   else launch_gemm<LGX_S8_DW>(g, s);
   return launched("lgx_s8_gemm_group");
+}
+
+extern "C" {
+
+int32_t lgx_s8_gemm_group(const lgx_s8_gemm_args* a, int32_t n, int32_t kind, void* stream) {
+  return gemm_group(a, n, kind, nullptr, nullptr, stream);
+}
+
+int32_t lgx_s8_dx_group_aux(const lgx_s8_gemm_args* a, int32_t n, const lgx_aux_loss_args* x,
+                            const lgx_heads_s8_args* s, void* stream) {
+  if (!x || !s) return fail("lgx_s8_dx_group_aux: null arguments");
+  if (x->B < 1 || x->L < 1 || x->E < 1 || x->E > 8 || !x->p || !x->a || !x->e || !x->t || !x->out || !x->ws ||
+      !x->counter || !x->g || !x->dp)
+    return fail("lgx_s8_dx_group_aux: bad aux arguments (E <= 8)");
+  if (!x->de && !s->de_s8) return fail("lgx_s8_dx_group_aux: de needs an fp32 or an S8 destination");
+  if (s->de_s8 && (s->ld_de % 8 || (((uintptr_t)s->de_s8) & 15)))
+    return fail("lgx_s8_dx_group_aux: S8 destination pitch / alignment");
+  return gemm_group(a, n, LGX_S8_DX, x, s, stream);
+}
+
+int32_t lgx_s8_heads_fwd(const lgx_s8_gemm_args* a, int32_t n, const lgx_s8_heads_args* hd, void* stream) {
+  if (n < 1 || n > LGX_S8_HEADS_MAX || !a) return fail("lgx_s8_heads_fwd: 1 <= n <= LGX_S8_HEADS_MAX");
+  if (!hd || !hd->head || !hd->s8 || !hd->tail) return fail("lgx_s8_heads_fwd: null head arguments");
+  const lgx_ppo_head_args& h = *hd->head;
+  const lgx_heads_s8_args& s8 = *hd->s8;
+  const lgx_heads_tail_args& t = *hd->tail;
+  if (h.B < 1 || h.A < 1 || h.A > LGX_S8_HEADS_MAXA || !h.std || !h.actions || !h.old_logp || !h.adv || !h.returns ||
+      (h.clipped_value && !h.target_values) || !h.ws || !h.out || !h.old_mu || !h.old_sigma || !h.g)
+    return fail("lgx_s8_heads_fwd: bad head arguments (A <= LGX_S8_HEADS_MAXA)");
+  if ((!h.dmu && !s8.dmu_s8) || (!h.dvalue && !s8.dvalue_s8))
+    return fail("lgx_s8_heads_fwd: dmu / dvalue need an fp32 or an S8 destination");
+  if ((s8.dmu_s8 && (s8.ld_dmu % 8 || s8.ld_dmu < (h.A + 7) / 8 * 8)) || (s8.dvalue_s8 && s8.ld_dvalue % 8) ||
+      ((((uintptr_t)s8.dmu_s8) | ((uintptr_t)s8.dvalue_s8) | ((uintptr_t)t.dy) | ((uintptr_t)t.dyc)) & 15))
+    return fail("lgx_s8_heads_fwd: S8 destinations: pitches multiples of 8, 16-B aligned");
+  if ((s8.decisions_out != nullptr) != (hd->decisions_critic != nullptr))
+    return fail("lgx_s8_heads_fwd: decisions_out and decisions_critic are set together");
+  if (!t.W || !t.b || !t.dy || !t.Wc || !t.bc || !t.dyc || t.ld_dy % 8 || t.ld_dy < t.H || t.ld_dyc % 8 ||
+      t.ld_dyc < t.Hc)
+    return fail("lgx_s8_heads_fwd: bad tail arguments");
+  lgxs::HGroup g;
+  memset(&g, 0, sizeof g);
+  int seen = 0;
+  for (int i = 0; i < n; ++i) {
+    const lgx_s8_gemm_args& q = a[i];
+    const int hb = q.epilogue & (LGX_S8_EPI_HEAD_ACTOR | LGX_S8_EPI_HEAD_CRITIC);
+    if (q.M < 1 || q.N < 1 || q.K < 0 || !q.A || !q.B) return fail("lgx_s8_heads_fwd: bad problem");
+    if (q.lda % 8 || q.ldb % 8 || ((((uintptr_t)q.A) | ((uintptr_t)q.B)) & 15))
+      return fail("lgx_s8_heads_fwd: S8 operands: pitches multiples of 8, 16-B aligned");
+    const int kp = cdiv(q.K, lgxs::BK) * lgxs::BK;
+    if (q.lda < kp || q.ldb < kp) return fail("lgx_s8_heads_fwd: ROW operand pitch < round_up(K, 32)");
+    if ((int64_t)q.M * q.lda * 4 >= (1ll << 31) || (int64_t)q.N * q.ldb * 4 >= (1ll << 31))
+      return fail("lgx_s8_heads_fwd: operand spans >= 2 GB");
+    if (!q.C && !q.C32) return fail("lgx_s8_heads_fwd: no output");
+    if (q.C && (q.ldc % 8 || (((uintptr_t)q.C) & 15))) return fail("lgx_s8_heads_fwd: S8 output alignment");
+    if ((q.epilogue & LGX_S8_EPI_BIAS) && !q.bias) return fail("lgx_s8_heads_fwd: bias epilogue without bias");
+    if (q.C32 && q.ldc32 < q.N) return fail("lgx_s8_heads_fwd: ldc32 < N");
+    if (hb) {
+      const bool actor = hb == LGX_S8_EPI_HEAD_ACTOR;
+      if ((hb != LGX_S8_EPI_HEAD_ACTOR && hb != LGX_S8_EPI_HEAD_CRITIC) || (seen & hb))
+        return fail("lgx_s8_heads_fwd: at most one actor and one critic problem");
+      seen |= hb;
+      if (q.N > lgxs::BN || q.N % 8 || q.N != (actor ? t.H : t.Hc) || q.M != h.B || !q.C || q.C32 || q.colsum_ws ||
+          (q.epilogue & (LGX_S8_EPI_BIAS | LGX_S8_EPI_ELU)) != (LGX_S8_EPI_BIAS | LGX_S8_EPI_ELU) || q.ldc < q.N)
+        return fail("lgx_s8_heads_fwd: a head problem is bias + ELU into S8 with N = H <= 128, a multiple of 8, M = B");
+    }
+    lgxs::Prob& p = g.p[i];
+    p.A = (const char*)q.A;
+    p.B = (const char*)q.B;
+    p.lda = q.lda * 4;
+    p.ldb = q.ldb * 4;
+    p.M = q.M;
+    p.N = q.N;
+    p.K = q.K;
+    p.tiles_m = cdiv(q.M, lgxs::Cfg::BM);
+    p.tiles_n = cdiv(q.N, lgxs::BN);
+    p.tiles = p.tiles_m * p.tiles_n;
+    p.kchunk = kp;
+    p.epi = q.epilogue;
+    p.C = (char*)q.C;
+    p.ldc = q.ldc * 4;
+    p.C32 = q.C32;
+    p.ldc32 = q.ldc32;
+    p.bias = q.bias;
+    p.colsum_ws = q.colsum_ws;
+    g.start[i + 1] = g.start[i] + p.tiles;
+  }
+  if (seen != (LGX_S8_EPI_HEAD_ACTOR | LGX_S8_EPI_HEAD_CRITIC))
+    return fail("lgx_s8_heads_fwd: needs the actor and the critic problem");
+  g.n = n;
+  g.ntiles = g.start[n];
+  g.h = h;
+  g.s = s8;
+  g.t = t;
+  g.dec_critic = hd->decisions_critic;
+  constexpr int lds = lgxs::HLds::END * 4;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)lgxs::s8_heads_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr = true;
+  }
+  hipLaunchKernelGGL(lgxs::s8_heads_fwd_kernel, dim3(g.ntiles), dim3(lgxs::Cfg::NT), lds, (hipStream_t)stream, g);
+  return launched("lgx_s8_heads_fwd");
 }
 
 int32_t lgx_s8_split(const lgx_s8_split_args* a, int32_t n, void* stream) {

@@ -17,7 +17,10 @@ graph, no per-call allocation (the hipGraph captures exactly these launches):
     3  loss heads forward + backward in one launch (lgx_loss_heads_fused: surrogate, clipped
        value loss, entropy, KL, ROA regulariser, estimator loss; ppo.py:196-262), which also
        writes the narrow output gradients in S8 with their column sums (the last layers' bias
-       gradients)
+       gradients). When a 128-column tile holds whole rows of the actor's and the critic's last
+       hidden layers (go2), the PPO head, the last layers and the first input-gradient level run
+       in the last forward level's own tiles instead (lgx_s8_heads_fwd), and the regulariser /
+       estimator head rides in front of the next input-gradient launch (lgx_s8_dx_group_aux)
     4  input gradients, one grouped launch per level back through the chains; each epilogue
        applies ELU'(y) of the layer below (from its S8 output), writes S8, and sums its columns
        per 128-row tile (that layer's bias gradient). The actor's first layer forms the gradient
@@ -157,6 +160,13 @@ class S8Minibatch:
         self.tail = (HEADS_TAIL and self.actor.n >= 2 and self.critic.n >= 2 and Wa.shape[0] <= 16 and Wc.shape[0] == 1
                      and all(W.shape[1] % 8 == 0 and 8 <= W.shape[1] <= 256 and W.is_contiguous() for W in (Wa, Wc)))
         self.ntail = (mb + H.HEADS_TAIL_ROWS - 1) // H.HEADS_TAIL_ROWS
+        # the loss heads in the last forward level's epilogue (lgx_s8_heads_fwd) instead of their own
+        # launch: when a 128-column tile holds whole rows of the actor's and the critic's last hidden
+        # layers, so that the tile that forms them runs the last layer, the PPO head and the first
+        # input gradient on them (bit-equal to lgx_loss_heads_tail). Selected by shape, here; tests
+        # set the attribute to False to run lgx_loss_heads_tail on the same buffers.
+        self.heads_fwd = (self.tail and Wa.shape[0] <= S.HEADS_MAXA and Wa.shape[1] <= 128 and Wc.shape[1] <= 128)
+        self._dec_critic = torch.zeros(mb, dtype=torch.uint8, device=dev)  # test hook: the critic tiles' decision bits
         self.head_ws = torch.empty(19 * max(self.ntail, (mb + 63) // 64), device=dev)
         self.aux_ws = torch.empty(2 * ((mb + 63) // 64), device=dev)
         # ---- weight-gradient split-K workspace and bias-gradient partials
@@ -185,6 +195,13 @@ class S8Minibatch:
         # critic beside the privileged / scan encoders' narrow levels: 2 / 3 / 4 slices 720 / 746
         # / 739 us per minibatch against 710 unsliced — not used)
         self.l0_slices = {"critic": 1}
+        enc_depth = max(self.priv.n, self.scan.n)
+        # (one launch: the two last hidden layers must share a level, with at most HEADS_MAX problems)
+        hlev = enc_depth + self.actor.n - 2
+        others = sum(1 for p in (self.priv, self.scan, self.est) for l in range(p.n)
+                     if l + (self.fwd_shift.get(p.name, 0) if p is self.est else 0) == hlev)
+        self.heads_fwd = (self.heads_fwd and self.critic.n - 2 + self.fwd_shift["critic"] == hlev
+                          and 2 + others <= S.HEADS_MAX)
         # the privileged and scan encoders' forward as one chain launch (lgx_s8_chain)
         # instead of their own three grouped levels
         self.enc_chain = ENC_CHAIN and all(p.n <= S.CHAIN_MAXL and max(max(W.shape) for W in p.W) <= S.CHAIN_MAXW
@@ -301,9 +318,14 @@ class S8Minibatch:
                "critic": (row(self.crin), self.crin.shape[1], cr.W[0].shape[1])}
         enc_depth = max(pr.n, sc.n)
         levels = {}
+        heads = []  # heads_fwd: the actor's and the critic's last hidden layers, and their level
 
-        def put(level, args):
-            levels.setdefault(level, []).append(args)
+        def put(level, args, head=0):
+            if head and self.heads_fwd:
+                args.epilogue |= head
+                heads.append((level, args))
+            else:
+                levels.setdefault(level, []).append(args)
         chains = []
         for p in (pr, sc, es, cr):
             A_ptr, lda, K = ins[p.name]
@@ -335,7 +357,8 @@ class S8Minibatch:
                             put(l + sh - (ns - 1) + q, self._fwd(p, l, A_ptr, lda, K, C=S.group_ptr(o, n0),
                                                                  ldc=o.shape[1], n0=n0, n1=n1))
                     else:
-                        put(l + sh, self._fwd(p, l, A_ptr, lda, K, C=o.data_ptr(), ldc=o.shape[1]))
+                        put(l + sh, self._fwd(p, l, A_ptr, lda, K, C=o.data_ptr(), ldc=o.shape[1]),
+                            head=S.EPI_HEAD_CRITIC if p is cr and l == p.n - 2 else 0)
                     A_ptr, lda, K = o.data_ptr(), o.shape[1], p.W[l].shape[0]
                     continue
                 if p is pr:
@@ -353,14 +376,11 @@ class S8Minibatch:
             lev = enc_depth + l
             if l < a.n - 1:
                 o = a.out[l]
-                put(lev, self._fwd(a, l, A_ptr, lda, K, C=o.data_ptr(), ldc=o.shape[1]))
+                put(lev, self._fwd(a, l, A_ptr, lda, K, C=o.data_ptr(), ldc=o.shape[1]),
+                    head=S.EPI_HEAD_ACTOR if l == a.n - 2 else 0)
                 A_ptr, lda, K = o.data_ptr(), o.shape[1], a.W[l].shape[0]
             elif not self.tail:
                 put(lev, self._fwd(a, l, A_ptr, lda, K, C32=self.mu.data_ptr(), ldc32=self.mu.shape[1], elu=False))
-        if chains:
-            S.chain(chains)
-        for lev in sorted(levels):
-            S.gemm_group(levels[lev], S.FWD)
         # 3. loss heads: forward sums and input gradients in one launch; the narrow output
         #    gradients straight into S8 with their per-256-row column sums (the last layers'
         #    bias gradients)
@@ -393,6 +413,7 @@ class S8Minibatch:
             dec["k"] = k + 1
             s8.decisions_in = dec["in"][k].data_ptr() if dec.get("in") is not None else None
             s8.decisions_out = dec["out"][k].data_ptr() if dec.get("out") is not None else None
+        t = None
         if self.tail:
             t = H.HeadsTailArgs(y=a.out[-1].data_ptr(), ld_y=a.out[-1].shape[1], W=a.W[-1].data_ptr(),
                                 b=a.b[-1].data_ptr(), dy=a.dy[-2].data_ptr(), ld_dy=a.dy[-2].shape[1],
@@ -400,6 +421,26 @@ class S8Minibatch:
                                 Wc=cr.W[-1].data_ptr(), bc=cr.b[-1].data_ptr(), dyc=cr.dy[-2].data_ptr(),
                                 ld_dyc=cr.dy[-2].shape[1], dyc_cs=cr.cs[-2].data_ptr(), mu_out=self.mu.data_ptr(),
                                 value_out=self.value.data_ptr(), H=a.W[-1].shape[1], Hc=cr.W[-1].shape[1])
+        # the forward launches (the argument structs above only hold addresses)
+        if chains:
+            S.chain(chains)
+        hlev = heads[0][0] if heads else None
+        for lev in sorted(set(levels) | ({hlev} if heads else set())):
+            if lev != hlev:
+                S.gemm_group(levels[lev], S.FWD)
+                continue
+            # the last level with the PPO head in the actor's / critic's tiles, the level's other
+            # problems (the estimator's last layer) after them. The aux head reads the estimator's
+            # output, so it rides in the next launch: the first input-gradient level (below)
+            dec_out = s8.decisions_out
+            heads.sort(key=lambda e: not e[1].epilogue & S.EPI_HEAD_ACTOR)  # the actor's (longer) tiles first
+            S.heads_fwd([g for _lev, g in heads] + levels.get(lev, []), h, s8, t,
+                        decisions_critic=self._dec_critic.data_ptr() if dec_out else None)
+            if dec_out:  # (test hook, eager: a row's two halves come from two tiles)
+                dec["out"][dec["k"] - 1].bitwise_or_(self._dec_critic)
+        if heads:
+            pass  # (ran in the last forward level)
+        elif self.tail:
             H._check(H.lib().lgx_loss_heads_tail(H.C.byref(h), H.C.byref(x), H.C.byref(s8), H.C.byref(t),
                                                  H._stream()), "lgx_loss_heads_tail")
         else:
@@ -427,7 +468,7 @@ class S8Minibatch:
             sh = self.dx_shift.get(p.name, 0)
             for l in range(p.n - 1, 0, -1):
                 if self.tail and p is not es and l == p.n - 1:
-                    continue  # in the heads-tail launch
+                    continue  # in the heads-tail launch / the last forward level's epilogue
                 bput(p.n - 1 - l + sh, dx(p, l, p.dy[l], p.dy[l - 1], p.cs[l - 1]))
         # the actor's first layer: gradient of its latent columns (+ the regulariser's)
         lev_lat = a.n - 1
@@ -445,8 +486,17 @@ class S8Minibatch:
                 else:
                     args = dx(p, l, dy, p.dy[l - 1], p.cs[l - 1])
                 bput(lev_lat + 1 + (p.n - 1 - l), args)
-        for lev in sorted(blev):
-            S.gemm_group(blev[lev], S.DX)
+        for k, lev in enumerate(sorted(blev)):
+            if heads and k == 0:
+                # with the aux head's blocks in front (alone they are a ~26 us launch; its outputs
+                # are first read by the estimator's and the latent's levels, after this one)
+                if lev < min(self.dx_shift.get("est", 0), lev_lat):
+                    S.dx_group_aux(blev[lev], x, s8)
+                else:  # (a level that reads them: the aux head alone first)
+                    S.dx_group_aux([], x, s8)
+                    S.gemm_group(blev[lev], S.DX)
+            else:
+                S.gemm_group(blev[lev], S.DX)
         # 5. weight gradients (one launch) and the reductions into the flat gradient buffer
         g_args, red = [], []
         off = 0

@@ -17,9 +17,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("LGX_S8_LIB") or os.path.join(os.path.dirname(os.path.dirname(_HERE)), "lib", "liblgx_s8.so")  # env: A/B builds
 _lib = None
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 FWD, DX, DW = 0, 1, 2
 EPI_BIAS, EPI_ELU, EPI_DELU, EPI_ACCUM = 1, 2, 4, 8
+EPI_HEAD_ACTOR, EPI_HEAD_CRITIC = 16, 32  # lgx_s8_heads_fwd: the tile also runs its half of the PPO loss head
+HEADS_MAX, HEADS_MAXA = 4, 12
 GROUP_MAX = 20
 BATCH_MAX = 48
 TILE_M = 64  # rows of one FWD / DX column-sum partial (lgx_s8.h LGX_S8_TILE_M)
@@ -78,6 +80,11 @@ class ChainArgs(C.Structure):
     _fields_ = [("A", vp), ("lda", i64), ("rows", i32), ("nlayers", i32), ("layers", ChainLayer * 3)]
 
 
+class HeadsArgs(C.Structure):
+    """Mirror of lgx_s8_heads_args: pointers to lgx_mlp.h's head / S8 / tail argument structs."""
+    _fields_ = [("head", vp), ("s8", vp), ("tail", vp), ("decisions_critic", vp)]
+
+
 def flat_reduce(ws, stride, out, n, nsplit, accumulate=0):
     """ReduceArgs for out[i] (+)= sum_s ws[s * stride + i], i < n (raw addresses)."""
     return ReduceArgs(ws=ws, stride=stride, ld_ws=n, out=out, ld_out=n, rows=1, cols=n, nsplit=nsplit,
@@ -87,12 +94,13 @@ def flat_reduce(ws, stride, out, n, nsplit, accumulate=0):
 # the three tables of the lgx_s8.h mirror (legged_gym_custom_amd/_cbind.py; tests/test_abi.py checks them)
 STRUCTS = {"lgx_s8_gemm_args": GemmArgs, "lgx_s8_split_args": SplitArgs, "lgx_s8_reduce_args": ReduceArgs,
            "lgx_s8_act_layer": ActLayer, "lgx_s8_act_args": ActArgs, "lgx_s8_act_pack_args": ActPackArgs,
-           "lgx_s8_chain_layer": ChainLayer, "lgx_s8_chain_args": ChainArgs}
+           "lgx_s8_chain_layer": ChainLayer, "lgx_s8_chain_args": ChainArgs, "lgx_s8_heads_args": HeadsArgs}
 SIZEOF = {"lgx_s8_sizeof_" + n: "lgx_s8_" + n for n in ("gemm_args", "act_pack_args", "chain_args", "act_args")}
 CONSTANTS = {
     "LGX_S8_ABI_VERSION": ABI_VERSION, "LGX_S8_FWD": FWD, "LGX_S8_DX": DX, "LGX_S8_DW": DW,
     "LGX_S8_EPI_BIAS": EPI_BIAS, "LGX_S8_EPI_ELU": EPI_ELU, "LGX_S8_EPI_DELU": EPI_DELU,
-    "LGX_S8_EPI_ACCUM": EPI_ACCUM, "LGX_S8_GROUP_MAX": GROUP_MAX, "LGX_S8_BATCH_MAX": BATCH_MAX,
+    "LGX_S8_EPI_ACCUM": EPI_ACCUM, "LGX_S8_EPI_HEAD_ACTOR": EPI_HEAD_ACTOR, "LGX_S8_EPI_HEAD_CRITIC": EPI_HEAD_CRITIC,
+    "LGX_S8_HEADS_MAX": HEADS_MAX, "LGX_S8_HEADS_MAXA": HEADS_MAXA, "LGX_S8_GROUP_MAX": GROUP_MAX, "LGX_S8_BATCH_MAX": BATCH_MAX,
     "LGX_S8_TILE_M": TILE_M, "LGX_S8_SPLIT_ROWS": SPLIT_ROWS, "LGX_S8_CHAIN_MAX": CHAIN_MAX,
     "LGX_S8_CHAIN_MAXL": CHAIN_MAXL, "LGX_S8_CHAIN_MAXW": CHAIN_MAXW, "LGX_S8_ACT_ROWS": ACT_ROWS,
     "LGX_S8_ACT_MAXIN": ACT_MAXIN, "LGX_S8_ACT_MAXH": ACT_MAXH, "LGX_S8_ACT_MAXENC": ACT_MAXENC,
@@ -110,6 +118,8 @@ SIGNATURES = {
     "lgx_s8_act_pack": (i32, (vp, i32, vp)),
     "lgx_s8_act_last_error": (C.c_char_p, ()),
     "lgx_s8_chain": (i32, (vp, i32, vp)),
+    "lgx_s8_heads_fwd": (i32, (vp, i32, vp, vp)),
+    "lgx_s8_dx_group_aux": (i32, (vp, i32, vp, vp, vp)),
 }
 EXPORTED = list(SIGNATURES)
 
@@ -190,6 +200,26 @@ def gemm_group(args, kind, L=None):
         chunk = args[i:i + GROUP_MAX]
         arr = (GemmArgs * len(chunk))(*chunk)
         _check(L.lgx_s8_gemm_group(arr, len(chunk), kind, _stream()), "lgx_s8_gemm_group")
+
+
+def heads_fwd(args, head, s8, tail, decisions_critic=None, L=None):
+    """lgx_s8_heads_fwd: the last forward level ([GemmArgs], the actor's / critic's last hidden
+    layers marked EPI_HEAD_ACTOR / EPI_HEAD_CRITIC) with the PPO loss head in its epilogue; head,
+    s8, tail: hip_mlp's HeadArgs, HeadsS8Args, HeadsTailArgs."""
+    L = lib() if L is None else L
+    arr = (GemmArgs * len(args))(*args)
+    hd = HeadsArgs(head=C.addressof(head), s8=C.addressof(s8), tail=C.addressof(tail), decisions_critic=decisions_critic)
+    _check(L.lgx_s8_heads_fwd(arr, len(args), C.byref(hd), _stream()), "lgx_s8_heads_fwd")
+
+
+def dx_group_aux(args, aux, s8, L=None):
+    """lgx_s8_dx_group_aux: one input-gradient level ([GemmArgs], may be empty) with the aux loss
+    head (hip_mlp's AuxArgs, HeadsS8Args) as the launch's first blocks."""
+    L = lib() if L is None else L
+    if len(args) > GROUP_MAX:
+        raise S8LibError("dx_group_aux: one launch")
+    arr = (GemmArgs * max(len(args), 1))(*args)
+    _check(L.lgx_s8_dx_group_aux(arr, len(args), C.byref(aux), C.byref(s8), _stream()), "lgx_s8_dx_group_aux")
 
 
 def pick_split(shapes, L=None):
