@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 8
+#define LGX_ABI_VERSION 9
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -48,6 +48,8 @@ extern "C" {
 #define LGX_EVAL_METRICS 8        /* per-env record columns (lgx_eval_buffers.acc) */
 #define LGX_EVAL_CELL_COLS 12     /* per-cell output columns (lgx_eval_buffers.cells) */
 #define LGX_MAX_ACTION_HISTORY 4  /* control steps of actuation latency (action_history rows) */
+#define LGX_EVAL_PUSH_REC 4       /* per-env push-recovery record columns (lgx_eval_buffers.push_rec) */
+#define LGX_EVAL_PUSH_COLS 5      /* per-cell push-recovery columns (lgx_eval_buffers.push_cells) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -324,6 +326,27 @@ typedef struct lgx_buffers {
   const int32_t* action_delay; /* [N] latency of each env in physics substeps */
   float* action_history;       /* [N,H,A] state */
   const float* motor_strength; /* [N,D] */
+  /* Scheduled push (ABI v9; the reference has none: its push_robots fires for all envs on one
+     global step and sets a random world-frame velocity). Both optional; both NULL = the step of
+     ABI 8, bit for bit. lgx_bind refuses one without the other.
+     Env e is pushed once per episode, in the step whose incremented episode length ep equals
+     push_step[e] (ep counts from 1: a value <= 0 means never). With (a, b, c) = push_dvel[e]: forward
+     and left velocity change in m/s in the robot's heading frame and yaw-rate change in rad/s,
+       f = quat_apply(q, (1,0,0));  n = sqrt(fx^2 + fy^2);  (hx, hy) = n > 1e-6 ? (fx/n, fy/n) : (1, 0)
+       root_states[e][7]  += a*hx - b*hy
+       root_states[e][8]  += a*hy + b*hx
+       root_states[e][12] += c
+     in fp32 without contraction, immediately after the reference's push (legged_robot.py:535-540),
+     so after base_lin_vel / base_ang_vel / projected_gravity are formed and before the termination
+     check. It is an impulse: it adds to the velocity (the training push sets it). The step's
+     observation and tracking terms do not see it (they read the velocities formed before it, as
+     with the reference's push); what the step copies from the root velocity afterwards
+     (last_root_vel, the reward terms that read root_states[7] / [9]) does; an env that resets in
+     the same step loses it. The next step's physics starts from the pushed velocity. The same rule
+     holds in lgx_step, lgx_step_dev and lgx_post_physics on both backends. The step reads both
+     buffers at kernel time: writing them between steps needs no re-bind. */
+  const int32_t* push_step;    /* [N] episode step of env e's push; <= 0: never */
+  const float* push_dvel;      /* [N,3] forward, left (m/s, heading frame), yaw rate (rad/s) */
 } lgx_buffers;
 
 typedef struct lgx_env lgx_env;
@@ -401,12 +424,21 @@ typedef struct lgx_eval_buffers {
   uint32_t* overflow;/* [1] written by lgx_eval_reduce: envs whose terrain level / type lies outside
                         the cell grid (0: cells are valid; else cells were left untouched) */
   int32_t cell_rows, cell_cols; /* terrain levels x terrain types; 1 x 1 when none are bound */
+  /* ABI 9, all optional (NULL / unset = the behaviour of ABI 8). */
+  const int32_t* cell_ids; /* [N] free cell key: lgx_eval_reduce files env e under cell cell_ids[e]
+                              instead of level * cell_cols + type. A value outside
+                              [0, cell_rows*cell_cols) is counted in overflow and leaves the cells
+                              untouched, as an out-of-grid terrain cell does. */
+  float* push_rec;         /* [N, 4] per-env push-recovery record, columns at lgx_eval_accumulate */
+  float settle_tol;        /* m/s: a sample is "off the command" when its tracking error exceeds it */
+  double* push_cells;      /* [cell_rows*cell_cols, 5], written by lgx_eval_reduce */
 } lgx_eval_buffers;
 int64_t lgx_sizeof_eval_buffers(void);
 /* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph.
  * They need commands, base_lin_vel, base_ang_vel, torques, dof_state, contact_forces, reset and
- * time_out bound; blew_up, terrain_levels and terrain_types are optional.
- * lgx_eval_begin: zero acc, status and overflow. */
+ * time_out bound; blew_up, terrain_levels and terrain_types are optional. With push_rec set they
+ * also need projected_gravity, episode_length and push_step bound (each failure names the buffer).
+ * lgx_eval_begin: zero acc, status, overflow and push_rec. */
 int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
 /* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
  * status[e] == 0:
@@ -425,7 +457,19 @@ int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
  *     acc[7]  = max(acc[7], max_f |contact_forces[e, feet_idx[f], :]|)   peak foot force
  * Envs with status != 0 are not touched: a finished env's later episodes change nothing. */
 int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
-/* cells[terrain_levels[e] * cell_cols + terrain_types[e]] (cell 0 for an unbound one) =
+/* Push recovery (ABI 9, push_rec set): in the same call, for an env that took a sample above
+ * (status[e] == 0, not reset this step) with push_step[e] > 0 and k = episode_length[e] -
+ * push_step[e] > 0 (the sample at k = 0 still shows the velocities formed before the push and is
+ * excluded), pg = projected_gravity[e], err = sqrt((c0-v0)^2 + (c1-v1)^2), rec = push_rec[e]:
+ *     rec[0] += 1                                          post-push samples
+ *     rec[1]  = max(rec[1], atan2f(sqrt(pg0^2+pg1^2), -pg2))   peak tilt, rad
+ *     rec[2]  = max(rec[2], err)                           peak tracking error, m/s
+ *     rec[3]  = err > settle_tol ? (float)k : rec[3]       last step still off the command
+ * push_cells[cell] (lgx_eval_reduce, push_cells set; needs push_rec) over the cell's finished envs
+ * (status != 0) with rec[0] > 0 = {n, sum rec[1], sum rec[2], n_survived (status 1 among them),
+ * sum of rec[3] over those survivors}: the same fp64 fixed tree and the same no-write-on-overflow
+ * rule as cells.
+ * cells[terrain_levels[e] * cell_cols + terrain_types[e]] (cell 0 for an unbound one) =
  * {n_envs, n_timeout, n_fall, n_blowup, fp64 sums of acc[0..7] over the cell's finished envs
  * (status != 0)}. Deterministic: fixed env order per lane and a fixed combination tree, no
  * floating-point atomics; two calls on the same records give bit-identical cells. A level or type

@@ -98,14 +98,28 @@ class NativeEnv:
         self._check(self._L.lgx_episode_extras(self.handle, p(means), p(level_mean), p(time_outs), p(step_dev),
                                                C.c_void_p(stream)), "lgx_episode_extras")
 
-    def eval_buffers(self, acc, status, cells, overflow):
+    def eval_buffers(self, acc, status, cells, overflow, cell_ids=None, push_rec=None, push_cells=None,
+                     settle_tol=0.0):
         """lgx_eval_buffers over the given tensors: acc [N, 8] fp32, status [N] uint8, cells
-        [rows, cols, 12] float64, overflow [1] int32, all in the env's memory space."""
+        [rows, cols, 12] float64, overflow [1] int32, all in the env's memory space. Optional
+        (ABI 9; None = unset): cell_ids [N] int32 (the free cell key), push_rec [N, 4] fp32 with
+        settle_tol, push_cells [rows, cols, 5] float64 (needs push_rec)."""
         n = self.params.num_envs
+        rc = tuple(cells.shape[:2]) if cells.dim() == 3 else None
         want = {"acc": ((n, _abi.EVAL_METRICS), "float32"), "status": ((n,), "uint8"),
-                "cells": (None, "float64"), "overflow": ((1,), "int32")}
+                "cells": (None, "float64"), "overflow": ((1,), "int32"), "cell_ids": ((n,), "int32"),
+                "push_rec": ((n, _abi.EVAL_PUSH_REC), "float32"),
+                "push_cells": (None if rc is None else rc + (_abi.EVAL_PUSH_COLS,), "float64")}
+        if push_cells is not None and push_rec is None:
+            raise LgxError("eval buffer push_cells needs push_rec")
+        if not 0.0 <= float(settle_tol) < float("inf"):
+            raise LgxError(f"settle_tol must be finite and >= 0 (got {settle_tol})")
         ev = _abi.EvalBuffers()
-        for name, t in (("acc", acc), ("status", status), ("cells", cells), ("overflow", overflow)):
+        ev.settle_tol = float(settle_tol)
+        for name, t in (("acc", acc), ("status", status), ("cells", cells), ("overflow", overflow),
+                        ("cell_ids", cell_ids), ("push_rec", push_rec), ("push_cells", push_cells)):
+            if t is None:
+                continue  # (an optional one: the struct's member stays NULL)
             shape, dtype = want[name]
             if name == "cells" and (t.dim() != 3 or t.shape[2] != _abi.EVAL_CELL_COLS):
                 raise LgxError(f"eval buffer cells must be [rows, cols, {_abi.EVAL_CELL_COLS}]")
@@ -115,7 +129,7 @@ class NativeEnv:
                                f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
             setattr(ev, name, t.data_ptr())
         ev.cell_rows, ev.cell_cols = int(cells.shape[0]), int(cells.shape[1])
-        ev._keep = (acc, status, cells, overflow)
+        ev._keep = (acc, status, cells, overflow, cell_ids, push_rec, push_cells)
         return ev
 
     def eval_begin(self, ev, stream):

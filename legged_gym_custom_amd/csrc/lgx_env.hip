@@ -1784,6 +1784,8 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
       root[7] = rand_range(-Pm->max_push_vel_xy, Pm->max_push_vel_xy, stg_U(AR)[S_PUSH + 0]);
       root[8] = rand_range(-Pm->max_push_vel_xy, Pm->max_push_vel_xy, stg_U(AR)[S_PUSH + 1]);
     }
+    // scheduled push (include/lgx.h, ABI 9): ep >= 1, so a push_step <= 0 never fires
+    if (B.push_step && (long long)B.push_step[e] == ep) scheduled_push(root, B.push_dvel + (size_t)e * 3);
     // check_termination go2.py:186-204
     int reset = 0;
     for (int i = 0; i < Pm->n_termination; ++i) {
@@ -2163,6 +2165,8 @@ int lgx_bind(lgx_env* env, const lgx_buffers* b) {
     return fail(env, "lgx_bind: action_delay needs action_history and params.action_history_len > 0");
   if (b->action_history && env->params.action_history_len <= 0)
     return fail(env, "lgx_bind: action_history with params.action_history_len = 0");
+  if (b->push_step && !b->push_dvel) return fail(env, "lgx_bind: push_step without push_dvel");
+  if (b->push_dvel && !b->push_step) return fail(env, "lgx_bind: push_dvel without push_step");
   if (env->params.curriculum && (!b->terrain_levels || !b->terrain_types || !b->terrain_origins))
     return fail(env, "lgx_bind: terrain curriculum needs terrain_levels/terrain_types/terrain_origins");
   env->buffers = *b;
@@ -2415,6 +2419,12 @@ struct EvalArgs {
   int N, D, NB, nfeet;
   int feet[LGX_MAX_FEET];
   float dt;
+  // push recovery (ABI 9): push_rec NULL = none of these is read
+  const float* pg;
+  const int64_t* ep;
+  const int32_t* push_step;
+  float* push_rec;
+  float settle_tol;
 };
 
 // lgx_eval_accumulate: four lanes per env (16 envs per wave). Lane q of an env reads a quarter of
@@ -2422,6 +2432,9 @@ struct EvalArgs {
 // per env, whole lines per wave) and foot q; two xor shuffles combine the quarters; lane q then
 // updates record columns 2q and 2q+1 (a wave writes 512 contiguous bytes). About 60 floats per
 // env: the kernel is launch-bound. No LDS, no atomics; finished envs are read-only.
+// Push recovery (push_rec set): lane q also updates push-record column q of a pushed env (a wave
+// writes 256 contiguous bytes); the extra reads are the env's push_step, episode_length and
+// projected_gravity rows.
 __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 2, q = t & 3;
@@ -2474,6 +2487,15 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
   }
   a[0] = x0;
   a[1] = x1;
+  if (A.push_rec) {
+    const int ps = A.push_step[e];
+    const long long k = (long long)A.ep[e] - ps;
+    if (ps > 0 && k > 0) {
+      float* r = A.push_rec + (size_t)e * LGX_EVAL_PUSH_REC + q;
+      *r = push_record_col(q, *r, A.pg + (size_t)e * 3, A.commands + (size_t)e * 4, A.lin_vel + (size_t)e * 3, k,
+                           A.settle_tol);
+    }
+  }
 }
 
 // lgx_eval_reduce: one block of 256 threads per cell. Thread t scans envs t, t+256, ... in
@@ -2482,13 +2504,18 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
 // wave results in wave order by thread 0), so the result depends only on the records. Every block
 // scans every env's level / type and so knows the number of out-of-grid envs: no block writes
 // its cell when there are any, and block 0 publishes the count.
+// ABI 9: cell_ids, when set, is the env's cell instead of level * cols + type (same range rule);
+// push_cells, when set, gets the cell's push-recovery sums from push_rec by the same tree.
 __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restrict__ acc,
                                                           const uint8_t* __restrict__ status,
                                                           const int64_t* __restrict__ levels,
-                                                          const int64_t* __restrict__ types, int N, int rows,
+                                                          const int64_t* __restrict__ types,
+                                                          const int32_t* __restrict__ cell_ids,
+                                                          const float* __restrict__ push_rec, int N, int rows,
                                                           int cols, double* __restrict__ cells,
+                                                          double* __restrict__ push_cells,
                                                           uint32_t* __restrict__ overflow) {
-  constexpr int NC = LGX_EVAL_CELL_COLS;
+  constexpr int NA = LGX_EVAL_CELL_COLS, NC = NA + LGX_EVAL_PUSH_COLS;
   __shared__ double part[4][NC];
   __shared__ uint32_t bad_s[4];
   const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -2496,9 +2523,15 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
   for (int k = 0; k < NC; ++k) s[k] = 0.0;
   uint32_t bad = 0;
   for (int e = tid; e < N; e += 256) {
-    const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
-    if (lv < 0 || lv >= rows || ty < 0 || ty >= cols) { ++bad; continue; }
-    if ((int)(lv * cols + ty) != cell) continue;
+    if (cell_ids) {
+      const int id = cell_ids[e];
+      if (id < 0 || id >= rows * cols) { ++bad; continue; }
+      if (id != cell) continue;
+    } else {
+      const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
+      if (lv < 0 || lv >= rows || ty < 0 || ty >= cols) { ++bad; continue; }
+      if ((int)(lv * cols + ty) != cell) continue;
+    }
     const int st = status[e];
     s[0] += 1.0;
     if (st == 0) continue;
@@ -2507,6 +2540,16 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
     s[3] += st == 3 ? 1.0 : 0.0;  // blow-up
     const float* a = acc + (size_t)e * LGX_EVAL_METRICS;
     for (int k = 0; k < LGX_EVAL_METRICS; ++k) s[4 + k] += (double)a[k];
+    if (push_cells) {
+      const float* r = push_rec + (size_t)e * LGX_EVAL_PUSH_REC;
+      if (r[0] > 0.f) {
+        s[NA + 0] += 1.0;
+        s[NA + 1] += (double)r[1];
+        s[NA + 2] += (double)r[2];
+        s[NA + 3] += st == 1 ? 1.0 : 0.0;
+        s[NA + 4] += st == 1 ? (double)r[3] : 0.0;
+      }
+    }
   }
   for (int o = 32; o > 0; o >>= 1) {
     for (int k = 0; k < NC; ++k) s[k] += __shfl_down(s[k], o, 64);
@@ -2519,7 +2562,10 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
   __syncthreads();
   const uint32_t nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
   if (tid == 0 && cell == 0 && overflow) *overflow = nbad;
-  if (nbad == 0 && tid < NC) cells[(size_t)cell * NC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+  if (nbad != 0 || tid >= NC) return;
+  const double v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+  if (tid < NA) cells[(size_t)cell * NA + tid] = v;
+  else if (push_cells) push_cells[(size_t)cell * LGX_EVAL_PUSH_COLS + (tid - NA)] = v;
 }
 }  // namespace lgx
 
@@ -2540,6 +2586,14 @@ static int eval_check(lgx_env* env, const lgx_eval_buffers* ev, const char* what
   if (ev->cell_rows < 1 || ev->cell_cols < 1 || (int64_t)ev->cell_rows * ev->cell_cols > (1 << 20))
     return fail(env, w + ": cell_rows * cell_cols must be >= 1 (and at most 2^20)");
   if (reduce && (!ev->cells || !ev->overflow)) return fail(env, w + ": cells and overflow are required");
+  if (ev->push_rec) {
+    static const char* pnames[] = {"projected_gravity", "episode_length", "push_step", "commands", "base_lin_vel"};
+    const void* pptrs[] = {b.projected_gravity, b.episode_length, b.push_step, b.commands, b.base_lin_vel};
+    for (size_t i = 0; i < sizeof(pptrs) / sizeof(pptrs[0]); ++i)
+      if (!pptrs[i]) return fail(env, w + ": push_rec needs a buffer that is not bound: " + pnames[i]);
+    if (!(ev->settle_tol >= 0.f)) return fail(env, w + ": settle_tol must be >= 0");
+  }
+  if (ev->push_cells && !ev->push_rec) return fail(env, w + ": push_cells needs push_rec");
   for (int f = 0; f < env->params.num_feet; ++f)
     if (env->params.feet_idx[f] < 0 || env->params.feet_idx[f] >= env->params.num_bodies)
       return fail(env, w + ": feet_idx outside the bodies");
@@ -2559,6 +2613,7 @@ int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) {
   HIP_OK(hipMemsetAsync(ev->acc, 0, sizeof(float) * LGX_EVAL_METRICS * N, st));
   HIP_OK(hipMemsetAsync(ev->status, 0, N, st));
   if (ev->overflow) HIP_OK(hipMemsetAsync(ev->overflow, 0, sizeof(uint32_t), st));
+  if (ev->push_rec) HIP_OK(hipMemsetAsync(ev->push_rec, 0, sizeof(float) * LGX_EVAL_PUSH_REC * N, st));
   return 0;
 }
 
@@ -2574,6 +2629,8 @@ int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stre
   A.commands = b.commands; A.lin_vel = b.base_lin_vel; A.ang_vel = b.base_ang_vel; A.torques = b.torques;
   A.dof_state = b.dof_state; A.contact = b.contact_forces; A.reset = b.reset; A.time_out = b.time_out;
   A.blew_up = b.blew_up; A.acc = ev->acc; A.status = ev->status;
+  A.pg = b.projected_gravity; A.ep = b.episode_length; A.push_step = b.push_step; A.push_rec = ev->push_rec;
+  A.settle_tol = ev->settle_tol;
   A.N = p.num_envs; A.D = p.num_dof; A.NB = p.num_bodies; A.nfeet = p.num_feet; A.dt = p.dt;
   for (int f = 0; f < LGX_MAX_FEET; ++f) A.feet[f] = f < p.num_feet ? p.feet_idx[f] : 0;
   const int64_t threads = (int64_t)p.num_envs * 4;
@@ -2587,14 +2644,15 @@ int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) 
   if (int rc = eval_check(env, ev, "lgx_eval_reduce", true)) return rc;
   if (env->host) {
     const int bad = lgxh::eval_reduce(&env->params, &env->buffers, ev);
-    if (bad) return fail(env, "lgx_eval_reduce: " + std::to_string(bad) + " envs have a terrain level / type outside the "
-                              "cell grid (cells not written)");
+    if (bad) return fail(env, "lgx_eval_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
+                              "outside the cell grid (cells not written)");
     return 0;
   }
   const lgx_buffers& b = env->buffers;
   hipLaunchKernelGGL(lgx::eval_reduce_kernel, dim3((unsigned)(ev->cell_rows * ev->cell_cols)), dim3(256), 0,
-                     (hipStream_t)hip_stream, ev->acc, ev->status, b.terrain_levels, b.terrain_types,
-                     env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cells, ev->overflow);
+                     (hipStream_t)hip_stream, ev->acc, ev->status, b.terrain_levels, b.terrain_types, ev->cell_ids,
+                     ev->push_rec, env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cells, ev->push_cells,
+                     ev->overflow);
   HIP_OK(hipGetLastError());
   return 0;
 }

@@ -261,6 +261,35 @@ LGX_HD void action_history_push(float* h, int H, int A, int j, float last, bool 
   h[j] = last;
 }
 
+// Scheduled push (lgx_buffers.push_step / push_dvel, include/lgx.h ABI 9): the impulse dv =
+// (forward, left, yaw rate) in the robot's heading frame added to the staged root state's world
+// velocity. Called by both backends right after the reference's push, for an env whose incremented
+// episode length equals its push_step.
+LGX_HD void scheduled_push(float* root, const float* dv) {
+  const float fwd[3] = {1.f, 0.f, 0.f};
+  float f[3];
+  quat_apply(root + 3, fwd, f);
+  const float n = nrm2(f[0], f[1]);
+  const bool ok = n > 1e-6f;
+  const float hx = ok ? f[0] / n : 1.0f, hy = ok ? f[1] / n : 0.0f;
+  root[7] = root[7] + (dv[0] * hx - dv[1] * hy);
+  root[8] = root[8] + (dv[0] * hy + dv[1] * hx);
+  root[12] = root[12] + dv[2];
+}
+
+// Push recovery (lgx_eval_buffers.push_rec, include/lgx.h ABI 9): one post-push sample of an env,
+// k > 0 steps after its push. The new value of record column col (0..3) from its old value x; pg:
+// projected gravity, c / v: commands and base_lin_vel. (The kernel gives one column to each of an
+// env's four lanes, the host backend loops over them.)
+LGX_HD float push_record_col(int col, float x, const float* pg, const float* c, const float* v, long long k,
+                             float settle_tol) {
+  if (col == 0) return x + 1.0f;
+  if (col == 1) return fmaxf(x, atan2f(nrm2(pg[0], pg[1]), -pg[2]));
+  const float err = sqrtf((c[0] - v[0]) * (c[0] - v[0]) + (c[1] - v[1]) * (c[1] - v[1]));
+  if (col == 2) return fmaxf(x, err);
+  return err > settle_tol ? (float)k : x;
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];

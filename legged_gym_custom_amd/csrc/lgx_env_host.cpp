@@ -826,6 +826,8 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     root[7] = rand_range(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 0]);
     root[8] = rand_range(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 1]);
   }
+  // scheduled push (include/lgx.h, ABI 9): ep >= 1, so a push_step <= 0 never fires
+  if (B->push_step && (long long)B->push_step[e] == ep) scheduled_push(root, B->push_dvel + (size_t)e * 3);
   // check_termination go2.py:186-204
   int reset = 0;
   for (int i = 0; i < P->n_termination; ++i) reset |= fnorm(s.cf[P->termination_idx[i]]) > 1.0f;
@@ -1075,6 +1077,7 @@ void eval_begin(const lgx_task_params* P, const lgx_eval_buffers* E) {
   memset(E->acc, 0, sizeof(float) * LGX_EVAL_METRICS * N);
   memset(E->status, 0, N);
   if (E->overflow) *E->overflow = 0;
+  if (E->push_rec) memset(E->push_rec, 0, sizeof(float) * LGX_EVAL_PUSH_REC * N);
 }
 
 // lgx_eval_accumulate (include/lgx.h): the kernel's arithmetic (lgx_env.hip
@@ -1112,12 +1115,22 @@ void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_e
     a[5] += dt * en;
     a[6] += t2;
     a[7] = std::max(a[7], fm);
+    if (E->push_rec) {  // push recovery (ABI 9)
+      const int ps = B->push_step[e];
+      const long long k = (long long)B->episode_length[e] - ps;
+      if (ps > 0 && k > 0) {
+        float* r = E->push_rec + (size_t)e * LGX_EVAL_PUSH_REC;
+        for (int col = 0; col < LGX_EVAL_PUSH_REC; ++col)
+          r[col] = push_record_col(col, r[col], B->projected_gravity + (size_t)e * 3, c, v, k, E->settle_tol);
+      }
+    }
   }
 }
 
 int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E) {
   const int N = P->num_envs, rows = E->cell_rows, cols = E->cell_cols;
   auto cell_of = [&](int e) -> int64_t {
+    if (E->cell_ids) return (E->cell_ids[e] < 0 || E->cell_ids[e] >= rows * cols) ? -1 : E->cell_ids[e];
     const int64_t lv = B->terrain_levels ? B->terrain_levels[e] : 0, ty = B->terrain_types ? B->terrain_types[e] : 0;
     return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : lv * cols + ty;
   };
@@ -1127,6 +1140,8 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
   if (bad) return bad;
   const size_t nc = (size_t)rows * cols * LGX_EVAL_CELL_COLS;
   for (size_t i = 0; i < nc; ++i) E->cells[i] = 0.0;
+  if (E->push_cells)
+    for (size_t i = 0; i < (size_t)rows * cols * LGX_EVAL_PUSH_COLS; ++i) E->push_cells[i] = 0.0;
   for (int e = 0; e < N; ++e) {  // env order: deterministic
     double* cl = E->cells + (size_t)cell_of(e) * LGX_EVAL_CELL_COLS;
     const int st = E->status[e];
@@ -1135,6 +1150,14 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
     if (st >= 1 && st <= 3) cl[st] += 1.0;
     const float* a = E->acc + (size_t)e * LGX_EVAL_METRICS;
     for (int k = 0; k < LGX_EVAL_METRICS; ++k) cl[4 + k] += (double)a[k];
+    const float* r = E->push_cells ? E->push_rec + (size_t)e * LGX_EVAL_PUSH_REC : nullptr;
+    if (r && r[0] > 0.f) {
+      double* pc = E->push_cells + (size_t)cell_of(e) * LGX_EVAL_PUSH_COLS;
+      pc[0] += 1.0;
+      pc[1] += (double)r[1];
+      pc[2] += (double)r[2];
+      if (st == 1) { pc[3] += 1.0; pc[4] += (double)r[3]; }
+    }
   }
   return 0;
 }

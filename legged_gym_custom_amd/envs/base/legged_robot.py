@@ -149,14 +149,51 @@ class LeggedRobot(BaseTask):
                                                    self._eval_overflow)
         return self._eval
 
-    def eval_begin(self):
-        """lgx_eval_begin: start recording every env's next (first) episode."""
-        self._native.eval_begin(self._eval_buffers(), self._stream())
+    def push_eval_buffers(self, rows, cols, settle_tol):
+        """A second set of evaluation tensors for the push test (lgx_eval_buffers with cell_ids,
+        push_rec and push_cells, ABI 9), allocated once per (rows, cols, settle_tol) so a captured
+        loop replays on fixed addresses: push_cell_ids [N] int32 (the caller writes each env's bin
+        in place), push_rec [N, 4] and, after eval_push_cells, cells [rows, cols, 12] and push cells
+        [rows, cols, 5]. Pass the result as `ev` to eval_begin / eval_accumulate."""
+        key = (int(rows), int(cols), float(settle_tol))
+        if getattr(self, "_push_eval_key", None) != key:
+            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
+            n = self.num_envs
+            self.push_eval_acc = z(n, _abi.EVAL_METRICS, dtype=torch.float32)
+            self.push_eval_status = z(n, dtype=torch.uint8)
+            self.push_cell_ids = z(n, dtype=torch.int32)
+            self.push_rec = z(n, _abi.EVAL_PUSH_REC, dtype=torch.float32)
+            self._push_eval_cells = z(key[0], key[1], _abi.EVAL_CELL_COLS, dtype=torch.float64)
+            self._push_cells = z(key[0], key[1], _abi.EVAL_PUSH_COLS, dtype=torch.float64)
+            self._push_eval_overflow = z(1, dtype=torch.int32)
+            self._push_eval = self._native.eval_buffers(
+                self.push_eval_acc, self.push_eval_status, self._push_eval_cells, self._push_eval_overflow,
+                cell_ids=self.push_cell_ids, push_rec=self.push_rec, push_cells=self._push_cells, settle_tol=key[2])
+            self._push_eval_key = key
+        return self._push_eval
 
-    def eval_accumulate(self):
+    def eval_begin(self, ev=None):
+        """lgx_eval_begin: start recording every env's next (first) episode (ev: another set of
+        eval buffers, push_eval_buffers(...); default: the plain evaluation's)."""
+        self._native.eval_begin(self._eval_buffers() if ev is None else ev, self._stream())
+
+    def eval_accumulate(self, ev=None):
         """lgx_eval_accumulate for the step just run (call after every step(); stream-ordered,
         no host sync, capturable)."""
-        self._native.eval_accumulate(self._eval_buffers(), self._stream())
+        self._native.eval_accumulate(self._eval_buffers() if ev is None else ev, self._stream())
+
+    def eval_push_cells(self):
+        """lgx_eval_reduce on the push test's buffers, then (cells [rows, cols, 12], push cells
+        [rows, cols, 5]: n, sum of peak tilt, sum of peak tracking error, survivors, sum of the
+        survivors' settle steps) float64 on the host. Synchronises. A cell id outside the grid is
+        an error."""
+        ev = self._push_eval
+        self._native.eval_reduce(ev, self._stream())
+        bad = int(self._push_eval_overflow.item())
+        if bad:
+            raise _native.LgxError(f"lgx_eval_reduce: {bad} envs have a cell id outside the "
+                                   f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
+        return self._push_eval_cells.cpu().clone(), self._push_cells.cpu().clone()
 
     def eval_cells(self):
         """lgx_eval_reduce, then the cells [rows, cols, 12] float64 on the host: n_envs, n_timeout,
@@ -382,6 +419,9 @@ class LeggedRobot(BaseTask):
         if not getattr(dr, "randomize_kp_kd", False):
             self.kp_kd_multipliers.fill_(1.0)
         self._init_actuator_randomisation()  # after every existing setup draw: those keep their values
+        self.push_step = self.push_dvel = None  # scheduled pushes (ABI 9): no draw, off unless allocated
+        if prm.scheduled_pushes(self.cfg):
+            self._alloc_push_schedule()
         self.default_dof_pos = torch.tensor([self.cfg.init_state.default_joint_angles[nm] for nm in self.dof_names],
                                             device=dev).unsqueeze(0)
         self._dof_state3[..., 0] = self.default_dof_pos
@@ -461,6 +501,7 @@ class LeggedRobot(BaseTask):
             "command_range_log": self._command_range_log if self._cmd_curriculum else None,
             "action_delay": self.action_delay_substeps, "action_history": self.action_history,
             "motor_strength": self.motor_strengths,
+            "push_step": self.push_step, "push_dvel": self.push_dvel,
             **self._sea_buffers,
         })
 
@@ -531,6 +572,46 @@ class LeggedRobot(BaseTask):
             self.motor_strengths = torch.ones(self.num_envs, self.num_dof, device=self.device)
             self._bind()
         self.motor_strengths.copy_(v.expand(self.num_envs, self.num_dof))
+
+    # ------------------------------------------------------------------ scheduled pushes
+    def _alloc_push_schedule(self):
+        self.push_step = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        self.push_dvel = torch.zeros(self.num_envs, 3, device=self.device)
+
+    def set_push_schedule(self, step, dvel):
+        """Scheduled pushes (include/lgx.h ABI 9): env e gets the velocity impulse dvel[e] = (forward,
+        left in m/s in its heading frame, yaw rate in rad/s) in the step in which its episode length
+        becomes step[e]; a step <= 0 means never. step: an int or an int tensor [num_envs]; dvel: [3]
+        or [num_envs, 3]. Written in place once the buffers exist; the first call on an env built
+        without domain_rand.scheduled_pushes allocates them and re-binds, which a captured graph of
+        this env's step would not see: RuntimeError once a step of this env has been captured.
+        ValueError for wrong shapes, a non-finite dvel or a step beyond max_episode_length."""
+        n = self.num_envs
+        st = torch.as_tensor(step, device=self.device)
+        if st.dtype.is_floating_point or st.dtype == torch.bool or st.dim() not in (0, 1) or \
+                (st.dim() == 1 and st.shape[0] != n):
+            raise ValueError(f"push step: an int or an int tensor [{n}], got {st.dtype} of shape {list(st.shape)}")
+        dv = torch.as_tensor(dvel, dtype=torch.float32, device=self.device)
+        if tuple(dv.shape) not in ((3,), (n, 3)):
+            raise ValueError(f"push dvel: a tensor [3] or [{n}, 3], got shape {list(dv.shape)}")
+        if not bool(torch.isfinite(dv).all()):
+            raise ValueError("push dvel must be finite")
+        if int(st.max()) > int(self.max_episode_length):
+            raise ValueError(f"push step {int(st.max())} is beyond max_episode_length = {int(self.max_episode_length)}")
+        if self.push_step is None:
+            if self._captured:
+                raise RuntimeError("set_push_schedule: this env has no push buffers and its step has been captured in "
+                                   "a graph, which would go on replaying the old binding; build the env with "
+                                   "domain_rand.scheduled_pushes or set a schedule before the capture")
+            self._alloc_push_schedule()
+            self._bind()
+        self.push_step.copy_(st.to(torch.int32).expand(n))
+        self.push_dvel.copy_(dv.expand(n, 3))
+
+    def clear_push_schedule(self):
+        """No env is pushed: push_step zeroed in place (a no-op on an env without the buffers)."""
+        if self.push_step is not None:
+            self.push_step.zero_()
 
     @property
     def physics_blowups(self):

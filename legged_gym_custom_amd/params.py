@@ -118,6 +118,14 @@ def actuator_randomisation(cfg, sim_dt):
                 strength_on=strength_on, strength_range=[slo, shi])
 
 
+def scheduled_pushes(cfg):
+    """cfg.domain_rand.scheduled_pushes (optional, read with getattr: the shipped config classes do
+    not carry it; set it on a config instance): allocate and bind the scheduled-push buffers
+    (lgx_buffers.push_step / push_dvel, include/lgx.h ABI 9) when the env is built, so that
+    env.set_push_schedule never has to re-bind (which a captured graph would not see)."""
+    return bool(getattr(cfg.domain_rand, "scheduled_pushes", False))
+
+
 def build_task_params(cfg, model, num_envs, num_envs_total=None, env_id_offset=0, sim_dt=None, go2=True,
                       terrain_shape=None):
     P = _abi.TaskParams()

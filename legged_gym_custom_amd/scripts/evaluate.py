@@ -7,14 +7,21 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
 
   python legged_gym/scripts/evaluate.py --task=go2_parkour --num_envs=4096 [--policy student|teacher]
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
+         [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
 history the largest one needs); several values give one report each under "sweep", on one captured
 loop. --motor_strength: a constant motor strength factor. Without them the config's own actuator
 randomisation applies, as trained.
 
+--push_vel: the push-recovery test (PolicyEvaluator.run_push_test): every env is shoved once, --push_at_s
+seconds into its episode, by a velocity impulse of one of the given speeds (m/s; 0 gives the control row)
+from one of --push_dirs directions in the robot's heading frame; one run fills the speeds x directions
+table. The config's own random pushes (domain_rand.push_robots) are switched off for this mode, so the
+scheduled push is the only disturbance.
+
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
-eval_<policy>_latency.json)."""
+eval_<policy>_latency.json; the push test: eval_<policy>_push.json)."""
 import argparse
 import json
 import os
@@ -33,7 +40,8 @@ from legged_gym.utils import get_args, get_load_path, task_registry  # noqa: E40
 from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 
-def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None):
+def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
+             push_vel=None, push_dirs=8, push_at_s=2.0):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -42,6 +50,11 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         dr = env_cfg.domain_rand
         own = getattr(dr, "max_action_delay_s", getattr(dr, "action_delay_range_s", [0.0, 0.0])[1])
         dr.max_action_delay_s = max(float(own), max(delays_s))
+    if push_vel:
+        if delays_s or motor_strength is not None:
+            raise ValueError("--push_vel is a mode of its own: not with --action_delay_ms / --motor_strength")
+        env_cfg.domain_rand.scheduled_pushes = True  # the push buffers exist before any capture
+        env_cfg.domain_rand.push_robots = False      # the scheduled push is the only disturbance
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
 
     train_cfg.runner.resume = True
@@ -52,7 +65,11 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
     checkpoint = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
     ev = PolicyEvaluator(env, runner, policy=policy)
     head = dict(task=args.task, checkpoint=checkpoint, iteration=int(runner.current_learning_iteration))
-    if len(delays_s) > 1:
+    if push_vel:
+        report = dict(**head, **ev.run_push_test(push_vel, directions=push_dirs, at_s=push_at_s, num_steps=eval_steps,
+                                                 graph=graph))
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_push.json")
+    elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength)
         report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_latency.json")
@@ -71,10 +88,14 @@ def main(argv=None):
     p.add_argument("--eval_steps", type=int, default=None)
     p.add_argument("--action_delay_ms", type=lambda s: [float(v) for v in s.split(",")], default=None)
     p.add_argument("--motor_strength", type=float, default=None)
+    p.add_argument("--push_vel", type=lambda s: [float(v) for v in s.split(",")], default=None)
+    p.add_argument("--push_dirs", type=int, default=8)
+    p.add_argument("--push_at_s", type=float, default=2.0)
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
     report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
-                         action_delay_ms=own.action_delay_ms, motor_strength=own.motor_strength)
+                         action_delay_ms=own.action_delay_ms, motor_strength=own.motor_strength,
+                         push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s)
     print(json.dumps(report))
     return report
 

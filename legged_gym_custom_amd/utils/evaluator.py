@@ -19,6 +19,11 @@ mean straight into env.actions_in (the weights are packed once, at construction 
 refresh_weights()), and the loop body {act, env.step, eval_accumulate} is captured once as a
 hipGraph and replayed. Otherwise (CPU, ANYmal) the torch modules run eagerly.
 
+Push recovery (run_push_test): every env is shoved once, at the same episode step, by the step
+kernel's scheduled push (lgx_buffers.push_step / push_dvel, ABI 9); the envs are spread over
+speed x direction bins through the evaluation's free cell key (lgx_eval_buffers.cell_ids) and a
+per-env recovery record (push_rec) is reduced per bin: one run gives the whole polar table.
+
 Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
@@ -46,6 +51,15 @@ def cell_report(cell, dt, weight):
             "cost_of_transport": div(s[5], weight * s[4]), "mean_peak_foot_force": div(s[7], ep)}
 
 
+def push_cell_report(pcell, dt):
+    """The recovery entries of one push cell row [5] (n, sum of peak tilt, sum of peak tracking
+    error, survivors, sum of the survivors' settle steps). Means without data are None."""
+    n, surv = int(round(float(pcell[0]))), int(round(float(pcell[3])))
+    div = lambda a, b: a / b if b > 0 else None  # noqa: E731
+    return {"pushed": n, "mean_peak_tilt_rad": div(float(pcell[1]), n), "mean_peak_lin_vel_err": div(float(pcell[2]), n),
+            "survivors": surv, "mean_settle_s": div(float(pcell[4]) * dt, surv)}
+
+
 def _min_max(t, kind):
     return None if t is None else [kind(t.min()), kind(t.max())]
 
@@ -64,8 +78,10 @@ class PolicyEvaluator:
             raise RuntimeError(f"the evaluator runs the policy on the env's device ({env.device}), not {self.device}")
         self.on_gpu = self.device.startswith("cuda")
         self._graph = None
+        self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._fused = None
         self.last_cells = None
+        self.last_push_cells = self.last_push_bins = None
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -86,7 +102,7 @@ class PolicyEvaluator:
         """Re-pack the fused act kernel's weights (after the runner loaded or trained them)."""
         if self._fused is not None:
             self._fused.refresh_weights()
-            self._graph = None
+            self._graph = self._push_graph = None
 
     # ------------------------------------------------------------------ one iteration
     def act(self):
@@ -99,13 +115,14 @@ class PolicyEvaluator:
             return mu
         return ac.act_inference(obs, priv, self.alg.estimator(obs), scan, adaptation_mode=self.adaptation_mode)
 
-    def step(self):
-        """One eager iteration: act, env.step, eval_accumulate."""
+    def step(self, ev=None):
+        """One eager iteration: act, env.step, eval_accumulate (ev: the eval buffers to record
+        into; default: the plain evaluation's)."""
         with torch.no_grad():
             self.env.step(self.act())
-            self.env.eval_accumulate()
+            self.env.eval_accumulate(ev)
 
-    def begin(self):
+    def begin(self, ev=None):
         """Reset every env and start recording. The env's step and reset-call counters (the keys
         of its random streams) are rewound, so an evaluation depends only on the weights, the
         seed and the config, and repeats exactly; do not interleave it with training on the same
@@ -118,22 +135,23 @@ class PolicyEvaluator:
         with torch.no_grad():
             env.reset()
             env.episode_length_buf = torch.zeros_like(env.episode_length_buf)
-            env.eval_begin()
+            env.eval_begin(ev)
 
-    def _capture(self):
+    def _capture(self, ev=None):
         """The loop body as one hipGraph (the runner's _capture_rollout is the model): one eager
-        iteration warms every kernel, then the capture records without executing."""
+        iteration warms every kernel, then the capture records without executing. Returns the
+        graph (it records into ev; default: the plain evaluation's buffers)."""
         env = self.env
-        self.step()
+        self.step(ev)
         torch.cuda.synchronize(self.device)
         csc = env.common_step_counter
         g = torch.cuda.CUDAGraph()
         with torch.inference_mode(False), torch.no_grad(), \
                 torch.cuda.graph(g, capture_error_mode=self.alg.capture_mode()):
             env.step(self.act())
-            env.eval_accumulate()
+            env.eval_accumulate(ev)
         env.common_step_counter = csc  # host mirror (capture advanced it, the device did not)
-        self._graph = g
+        return g
 
     # ------------------------------------------------------------------ run
     def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None):
@@ -178,22 +196,95 @@ class PolicyEvaluator:
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         if use_graph and self._graph is None:
-            self._capture()
+            self._graph = self._capture()
         self.begin()
-        if self.on_gpu:
-            torch.cuda.synchronize(self.device)
-        t0 = time.perf_counter()
-        if use_graph:
-            for _ in range(steps):
-                self._graph.replay()
-                env.advance_step_counter(1)
-        else:
-            for _ in range(steps):
-                self.step()
+        t0 = self._loop(steps, self._graph if use_graph else None, None)
         cells = env.eval_cells()  # reduce + the host read (synchronises)
         wall = time.perf_counter() - t0
         self.last_cells = cells  # [rows, cols, 12] float64, as lgx_eval_reduce wrote them
         return self.report(cells, steps, wall, use_graph)
+
+    def _loop(self, steps, g, ev):
+        """steps x the loop body (g: its captured graph, or None for the eager loop) recording
+        into ev; returns the start time."""
+        env = self.env
+        if self.on_gpu:
+            torch.cuda.synchronize(self.device)
+        t0 = time.perf_counter()
+        if g is not None:
+            for _ in range(steps):
+                g.replay()
+                env.advance_step_counter(1)
+        else:
+            for _ in range(steps):
+                self.step(ev)
+        return t0
+
+    # ------------------------------------------------------------------ push recovery
+    def run_push_test(self, speeds, directions=8, at_s=2.0, settle_tol=0.3, num_steps=None, graph=True):
+        """How hard a shove does the policy survive, from which side, and how quickly does it
+        settle: one run in which every env is pushed once, at episode step round(at_s / dt), by a
+        velocity impulse of its bin (speed index s, direction index d): dvel = speeds[s] *
+        (cos t, sin t, 0) with t = 2 pi d / directions measured from the robot's forward axis
+        towards its left. Envs get bins by randperm(num_envs, seeded with env.seed) % (S * D): bin
+        sizes differ by at most one and do not follow the terrain columns. Speed 0 gives the
+        control row.
+
+        The records go to a second set of eval buffers (env.push_eval_buffers: the bin is the cell
+        key, plus the per-env recovery record of include/lgx.h), and this mode's captured loop is a
+        graph of its own, never the plain run's. The env needs the push buffers before any of its
+        steps is captured (domain_rand.scheduled_pushes = True, or call this before run()).
+        The schedule is cleared in place when the run ends, so a following run() is the plain one.
+
+        Returns the report: "bins"[s][d] with the REPORT_KEYS entries and pushed (finished envs
+        with post-push samples), mean_peak_tilt_rad, mean_peak_lin_vel_err (m/s), survivors (timed
+        out among them) and mean_settle_s (the survivors' mean time from the push to the last step
+        whose tracking error exceeded settle_tol); "total" likewise; speeds, directions_deg,
+        push_step, settle_tol. None where there is no data, never NaN.
+        ValueError: no speeds or directions, a negative or non-finite speed, a push step outside
+        0 < step < max_episode_length."""
+        env = self.env
+        speeds = [float(v) for v in speeds]
+        S, D = len(speeds), int(directions)
+        if S < 1 or D < 1 or not all(math.isfinite(v) and v >= 0.0 for v in speeds):
+            raise ValueError(f"push test: need at least one finite speed >= 0 and one direction (got {speeds}, {directions})")
+        if not (math.isfinite(float(settle_tol)) and float(settle_tol) >= 0.0):
+            raise ValueError(f"push test: settle_tol must be finite and >= 0 (got {settle_tol})")
+        at = float(at_s)
+        step = int(round(at / float(env.dt))) if math.isfinite(at) else -1
+        if not 0 < step < int(env.max_episode_length):
+            raise ValueError(f"push test: at_s = {at_s} s is step {step}, outside 0 < step < max_episode_length = "
+                             f"{int(env.max_episode_length)}")
+        n = env.num_envs
+        bins = torch.randperm(n, generator=torch.Generator().manual_seed(int(env.seed))) % (S * D)
+        theta = 2.0 * math.pi * (bins % D).double() / D
+        v = torch.tensor(speeds, dtype=torch.float64)[bins // D]
+        dvel = torch.stack([v * torch.cos(theta), v * torch.sin(theta), torch.zeros_like(v)], 1).float()
+        steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
+        use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
+        key = (S, D, float(settle_tol))
+        try:
+            env.set_push_schedule(0, dvel)  # (the first one allocates: refused once a loop is captured)
+            ev = env.push_eval_buffers(*key)
+            env.push_cell_ids.copy_(bins.to(torch.int32))
+            if use_graph and (self._push_graph is None or self._push_graph_key != key):
+                self._push_graph, self._push_graph_key = self._capture(ev), key
+            self.begin(ev)
+            env.set_push_schedule(step, dvel)  # after begin: its reset ends with an env step of its own
+            t0 = self._loop(steps, self._push_graph if use_graph else None, ev)
+            cells, pcells = env.eval_push_cells()  # reduce + the host read (synchronises)
+            wall = time.perf_counter() - t0
+        finally:
+            env.clear_push_schedule()
+        self.last_cells, self.last_push_cells, self.last_push_bins = cells, pcells, bins
+        dt, w = float(env.dt), self.mass * self.gravity
+        both = lambda c, p: {**cell_report(c, dt, w), **push_cell_report(p, dt)}  # noqa: E731
+        return {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
+                "graph": use_graph, "speeds": speeds, "directions_deg": [360.0 * d / D for d in range(D)],
+                "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
+                "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
+                "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)],
+                "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
 
     def sweep_action_delay(self, delays_s, **run_kwargs):
         """One report per actuation latency (seconds) of delays_s, each a full run() with that

@@ -2,6 +2,7 @@
 networks (the timing does not depend on the weights), graph replay and the eager loop alternated.
 
   python tools/eval_bench.py [--task go2] [--num_envs 4096] [--steps N] [--repeats 3] [--out FILE]
+  python tools/eval_bench.py --push_vel 0,0.5,1.0,1.5 [--push_dirs 8] ...   # + the push test (run_push_test)
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/eval_bench.py --profile
   python tools/eval_bench.py --stats DIR/..._kernel_stats.csv --merge FILE   # kernel times into FILE
 
@@ -40,6 +41,9 @@ def main():
     p.add_argument("--steps", type=int, default=None)
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--device", default="cuda:0", help="cpu: a rehearsal of the tool, not a measurement")
+    p.add_argument("--push_vel", type=lambda s: [float(v) for v in s.split(",")], default=None,
+                   help="also time run_push_test with these speeds (the env is built with scheduled_pushes)")
+    p.add_argument("--push_dirs", type=int, default=8)
     p.add_argument("--profile", action="store_true")
     p.add_argument("--stats")
     p.add_argument("--merge")
@@ -55,6 +59,8 @@ def main():
     cfg, tcfg = task_registry_configs(a.task)
     cfg.seed = tcfg.seed = 1
     cfg.terrain.curriculum = cfg.commands.curriculum = False
+    if a.push_vel:
+        cfg.domain_rand.scheduled_pushes = True  # buffers bound with no env scheduled: the plain run's step is unchanged
     args = get_args([f"--task={a.task}", "--headless", f"--num_envs={a.num_envs}", "--seed=1",
                      f"--sim_device={a.device}", f"--rl_device={a.device}"])
     env, _ = task_registry.make_env(a.task, args, env_cfg=cfg)
@@ -67,15 +73,28 @@ def main():
     ev.run(20)  # warm both paths (the capture included)
     ev.run(20, graph=False)
     rates = {"graph": [], "eager": []}
+    push = (lambda steps, graph: ev.run_push_test(a.push_vel, directions=a.push_dirs, num_steps=steps, graph=graph))
+    if a.push_vel:
+        rates.update(push_graph=[], push_eager=[])
+        push(20, True)
+        push(20, False)
     for _ in range(a.repeats):
-        for mode in ("graph", "eager"):
-            r = ev.run(a.steps, graph=mode == "graph")
-            assert a.device == "cpu" or r["graph"] == (mode == "graph")
+        for mode in rates:
+            graph = mode.endswith("graph")
+            r = push(a.steps, graph) if mode.startswith("push") else ev.run(a.steps, graph=graph)
+            assert a.device == "cpu" or r["graph"] == graph
             rates[mode].append(r["env_steps_per_s"])
+    pr = r if a.push_vel else None
+    r = ev.run(a.steps) if a.push_vel else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
                                for m, v in rates.items()},
            "total": r["total"]}
+    if pr:
+        doc["push_test"] = {k: pr[k] for k in ("speeds", "directions_deg", "push_step", "settle_tol", "total")}
+        doc["push_test"]["per_speed"] = [
+            {"speed": v, "episodes": sum(c["episodes"] for c in row), "survivors": sum(c["survivors"] for c in row),
+             "pushed": sum(c["pushed"] for c in row)} for v, row in zip(pr["speeds"], pr["bins"])]
     print(json.dumps(doc))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
