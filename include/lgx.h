@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 9
+#define LGX_ABI_VERSION 10
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -50,6 +50,9 @@ extern "C" {
 #define LGX_MAX_ACTION_HISTORY 4  /* control steps of actuation latency (action_history rows) */
 #define LGX_EVAL_PUSH_REC 4       /* per-env push-recovery record columns (lgx_eval_buffers.push_rec) */
 #define LGX_EVAL_PUSH_COLS 5      /* per-cell push-recovery columns (lgx_eval_buffers.push_cells) */
+#define LGX_CMD_SEGMENTS 4        /* segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val) */
+#define LGX_EVAL_CMD_REC 8        /* per-env step-response record columns (lgx_eval_buffers.cmd_rec) */
+#define LGX_EVAL_CMD_COLS 9       /* per-cell step-response columns (lgx_eval_buffers.cmd_cells) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -347,6 +350,31 @@ typedef struct lgx_buffers {
      buffers at kernel time: writing them between steps needs no re-bind. */
   const int32_t* push_step;    /* [N] episode step of env e's push; <= 0: never */
   const float* push_dvel;      /* [N,3] forward, left (m/s, heading frame), yaw rate (rad/s) */
+  /* Command schedule (ABI v10; the reference draws commands from the training ranges, or holds one
+     user_command for all envs). Both optional; both NULL = the step of ABI 9, bit for bit, and so
+     is a bound schedule whose entries are all < 0. lgx_bind refuses one without the other.
+     Env e's schedule is up to LGX_CMD_SEGMENTS segments (cmd_step[e][k], cmd_val[e][k][0..3]); an
+     entry with cmd_step < 0 is unused, and the start steps of the used entries are non-decreasing
+     (the caller's duty). With ep the env's episode length, the active segment is the largest k with
+     0 <= cmd_step[e][k] <= ep. If there is one, commands[e][0..3] = cmd_val[e][k] exactly: a
+     schedule is literal, the small-command zeroing and the zero-command draw do not apply to it.
+     If there is none, nothing is written. The rule is applied at three sites, each after the
+     unchanged code it follows, so every random draw still happens (and is overwritten; the
+     uniforms are slot-keyed, no other stream moves):
+       * post-physics, after the command resample and after the heading rule, with ep the
+         incremented episode length: cmd_val[..][2] is therefore a yaw rate, and the heading
+         controller is bypassed for an env with an active segment;
+       * in reset_idx (in-step resets and lgx_reset_envs), after its resample, with ep = 0: a reset
+         env returns to the segment that starts at step 0 and switches again in its new episode;
+       * in lgx_command_curriculum's redraw of the reset envs' commands, after the redraw, with
+         ep = 0: the rewritten observation, critic and history command slots carry the schedule.
+     params.has_user_command and a schedule together: the schedule wins (it is applied later).
+     What the step does to commands after these sites still happens: with params.heading_command the
+     heading reward wraps commands[e][3] into (-pi, pi] in place (the reference's side effect), in
+     fp32 the identity on [0, pi] and within an ulp of 2 pi elsewhere in that interval.
+     The step reads both buffers at kernel time: writing them between steps needs no re-bind. */
+  const int32_t* cmd_step;     /* [N,LGX_CMD_SEGMENTS] first episode step of each segment; < 0: unused */
+  const float* cmd_val;        /* [N,LGX_CMD_SEGMENTS,4] the segment's commands (vx, vy, yaw rate, heading) */
 } lgx_buffers;
 
 typedef struct lgx_env lgx_env;
@@ -432,13 +460,21 @@ typedef struct lgx_eval_buffers {
   float* push_rec;         /* [N, 4] per-env push-recovery record, columns at lgx_eval_accumulate */
   float settle_tol;        /* m/s: a sample is "off the command" when its tracking error exceeds it */
   double* push_cells;      /* [cell_rows*cell_cols, 5], written by lgx_eval_reduce */
+  /* ABI 10, all optional (NULL / unset = the behaviour of ABI 9). */
+  const int32_t* cmd_switch_step; /* [N] the episode step env e's step-response record counts from;
+                                     <= 0: no record */
+  float* cmd_rec;          /* [N, 8] per-env step-response record, columns at lgx_eval_accumulate */
+  double* cmd_cells;       /* [cell_rows*cell_cols, 9], written by lgx_eval_reduce */
+  float yaw_tol;           /* rad/s: a sample is "off the yaw command" when |c2 - w2| exceeds it */
+  int32_t steady_after;    /* steps after the switch from which the achieved velocities are summed */
 } lgx_eval_buffers;
 int64_t lgx_sizeof_eval_buffers(void);
 /* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph.
  * They need commands, base_lin_vel, base_ang_vel, torques, dof_state, contact_forces, reset and
  * time_out bound; blew_up, terrain_levels and terrain_types are optional. With push_rec set they
- * also need projected_gravity, episode_length and push_step bound (each failure names the buffer).
- * lgx_eval_begin: zero acc, status, overflow and push_rec. */
+ * also need projected_gravity, episode_length and push_step bound, with cmd_rec set
+ * projected_gravity, episode_length and cmd_switch_step (each failure names the buffer).
+ * lgx_eval_begin: zero acc, status, overflow, push_rec and cmd_rec. */
 int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
 /* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
  * status[e] == 0:
@@ -469,6 +505,22 @@ int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stre
  * (status != 0) with rec[0] > 0 = {n, sum rec[1], sum rec[2], n_survived (status 1 among them),
  * sum of rec[3] over those survivors}: the same fp64 fixed tree and the same no-write-on-overflow
  * rule as cells.
+ * Step response (ABI 10, cmd_rec set): in the same call, for an env that took a sample above with
+ * cmd_switch_step[e] > 0 and k = episode_length[e] - cmd_switch_step[e] >= 0 (the command
+ * schedule switches in the step whose incremented episode length reaches its start step, so the
+ * sample at k = 0 is the first under the new command), yerr = |c2 - w2|, rec = cmd_rec[e]:
+ *     rec[0] += 1                                          post-switch samples
+ *     rec[1]  = err > settle_tol ? (float)(k+1) : rec[1]   steps until the linear velocity is on the
+ *                                                          command for good; 0: it was never off
+ *     rec[2]  = yerr > yaw_tol ? (float)(k+1) : rec[2]     the same for the yaw rate
+ *     rec[3]  = max(rec[3], atan2f(sqrt(pg0^2+pg1^2), -pg2))   peak tilt, rad
+ *     and, when k >= steady_after:
+ *     rec[4] += 1                                          steady samples
+ *     rec[5] += v0;  rec[6] += v1;  rec[7] += w2           achieved velocities, summed
+ * cmd_cells[cell] (lgx_eval_reduce, cmd_cells set; needs cmd_rec) over the cell's finished envs
+ * (status != 0) with rec[0] > 0 = {n, n_survived (status 1 among them), sum of rec[1] and of rec[2]
+ * over those survivors, sum of rec[3], sums of rec[4..7] over the survivors}: the same fp64 fixed
+ * tree (a second launch of the same kernel shape) and the same no-write-on-overflow rule as cells.
  * cells[terrain_levels[e] * cell_cols + terrain_types[e]] (cell 0 for an unbound one) =
  * {n_envs, n_timeout, n_fall, n_blowup, fp64 sums of acc[0..7] over the cell's finished envs
  * (status != 0)}. Deterministic: fixed env order per lane and a fixed combination tree, no

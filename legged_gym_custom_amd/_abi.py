@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -24,6 +24,9 @@ EVAL_CELL_COLS = 12  # per-cell output columns (lgx_eval_buffers.cells)
 MAX_ACTION_HISTORY = 4  # control steps of actuation latency (rows of lgx_buffers.action_history)
 EVAL_PUSH_REC = 4    # per-env push-recovery record columns (lgx_eval_buffers.push_rec)
 EVAL_PUSH_COLS = 5   # per-cell push-recovery columns (lgx_eval_buffers.push_cells)
+CMD_SEGMENTS = 4     # segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val)
+EVAL_CMD_REC = 8     # per-env step-response record columns (lgx_eval_buffers.cmd_rec)
+EVAL_CMD_COLS = 9    # per-cell step-response columns (lgx_eval_buffers.cmd_cells)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -138,7 +141,7 @@ class Buffers(C.Structure):
         "friction", "mass_params", "kp_kd", "env_origins", "terrain_levels", "terrain_types",
         "terrain_origins", "height_samples", "terrain_mesh", "sea_hidden", "sea_cell", "episode_stats",
         "blew_up", "blowup_count", "command_ranges", "curriculum_vals", "command_range_log",
-        "action_delay", "action_history", "motor_strength", "push_step", "push_dvel",
+        "action_delay", "action_history", "motor_strength", "push_step", "push_dvel", "cmd_step", "cmd_val",
     ]]
 
 
@@ -146,10 +149,11 @@ BUFFER_FIELDS = [f[0] for f in Buffers._fields_]
 
 
 class EvalBuffers(C.Structure):
-    """lgx_eval_buffers (ABI 7; cell_ids and the push-recovery members: ABI 9): the policy
-    evaluation's records and cells."""
+    """lgx_eval_buffers (ABI 7; cell_ids and the push-recovery members: ABI 9; the step-response
+    members: ABI 10): the policy evaluation's records and cells."""
     _fields_ = [("acc", P), ("status", P), ("cells", P), ("overflow", P), ("cell_rows", i32), ("cell_cols", i32),
-                ("cell_ids", P), ("push_rec", P), ("settle_tol", f32), ("push_cells", P)]
+                ("cell_ids", P), ("push_rec", P), ("settle_tol", f32), ("push_cells", P),
+                ("cmd_switch_step", P), ("cmd_rec", P), ("cmd_cells", P), ("yaw_tol", f32), ("steady_after", i32)]
 
 
 STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buffers,
@@ -164,6 +168,7 @@ CONSTANTS = {
     "LGX_MAX_TERMINATION": MAX_TERMINATION, "LGX_EVAL_METRICS": EVAL_METRICS, "LGX_EVAL_CELL_COLS": EVAL_CELL_COLS,
     "LGX_MAX_ACTION_HISTORY": MAX_ACTION_HISTORY,
     "LGX_EVAL_PUSH_REC": EVAL_PUSH_REC, "LGX_EVAL_PUSH_COLS": EVAL_PUSH_COLS,
+    "LGX_CMD_SEGMENTS": CMD_SEGMENTS, "LGX_EVAL_CMD_REC": EVAL_CMD_REC, "LGX_EVAL_CMD_COLS": EVAL_CMD_COLS,
     "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
     "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
     **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},

@@ -99,25 +99,37 @@ class NativeEnv:
                                                C.c_void_p(stream)), "lgx_episode_extras")
 
     def eval_buffers(self, acc, status, cells, overflow, cell_ids=None, push_rec=None, push_cells=None,
-                     settle_tol=0.0):
+                     settle_tol=0.0, cmd_switch_step=None, cmd_rec=None, cmd_cells=None, yaw_tol=0.0, steady_after=0):
         """lgx_eval_buffers over the given tensors: acc [N, 8] fp32, status [N] uint8, cells
         [rows, cols, 12] float64, overflow [1] int32, all in the env's memory space. Optional
         (ABI 9; None = unset): cell_ids [N] int32 (the free cell key), push_rec [N, 4] fp32 with
-        settle_tol, push_cells [rows, cols, 5] float64 (needs push_rec)."""
+        settle_tol, push_cells [rows, cols, 5] float64 (needs push_rec). ABI 10: cmd_switch_step [N]
+        int32, cmd_rec [N, 8] fp32 with settle_tol, yaw_tol and steady_after (steps), cmd_cells
+        [rows, cols, 9] float64 (needs cmd_rec; cmd_rec without cmd_switch_step is refused by the
+        lgx_eval_* calls)."""
         n = self.params.num_envs
         rc = tuple(cells.shape[:2]) if cells.dim() == 3 else None
         want = {"acc": ((n, _abi.EVAL_METRICS), "float32"), "status": ((n,), "uint8"),
                 "cells": (None, "float64"), "overflow": ((1,), "int32"), "cell_ids": ((n,), "int32"),
                 "push_rec": ((n, _abi.EVAL_PUSH_REC), "float32"),
-                "push_cells": (None if rc is None else rc + (_abi.EVAL_PUSH_COLS,), "float64")}
+                "push_cells": (None if rc is None else rc + (_abi.EVAL_PUSH_COLS,), "float64"),
+                "cmd_switch_step": ((n,), "int32"), "cmd_rec": ((n, _abi.EVAL_CMD_REC), "float32"),
+                "cmd_cells": (None if rc is None else rc + (_abi.EVAL_CMD_COLS,), "float64")}
         if push_cells is not None and push_rec is None:
             raise LgxError("eval buffer push_cells needs push_rec")
         if not 0.0 <= float(settle_tol) < float("inf"):
             raise LgxError(f"settle_tol must be finite and >= 0 (got {settle_tol})")
+        if cmd_cells is not None and cmd_rec is None:
+            raise LgxError("eval buffer cmd_cells needs cmd_rec")
+        if not 0.0 <= float(yaw_tol) < float("inf"):
+            raise LgxError(f"yaw_tol must be finite and >= 0 (got {yaw_tol})")
+        if not 0 <= int(steady_after) < 2 ** 31:
+            raise LgxError(f"steady_after must be a step count >= 0 (got {steady_after})")
         ev = _abi.EvalBuffers()
-        ev.settle_tol = float(settle_tol)
+        ev.settle_tol, ev.yaw_tol, ev.steady_after = float(settle_tol), float(yaw_tol), int(steady_after)
         for name, t in (("acc", acc), ("status", status), ("cells", cells), ("overflow", overflow),
-                        ("cell_ids", cell_ids), ("push_rec", push_rec), ("push_cells", push_cells)):
+                        ("cell_ids", cell_ids), ("push_rec", push_rec), ("push_cells", push_cells),
+                        ("cmd_switch_step", cmd_switch_step), ("cmd_rec", cmd_rec), ("cmd_cells", cmd_cells)):
             if t is None:
                 continue  # (an optional one: the struct's member stays NULL)
             shape, dtype = want[name]
@@ -129,7 +141,7 @@ class NativeEnv:
                                f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
             setattr(ev, name, t.data_ptr())
         ev.cell_rows, ev.cell_cols = int(cells.shape[0]), int(cells.shape[1])
-        ev._keep = (acc, status, cells, overflow, cell_ids, push_rec, push_cells)
+        ev._keep = (acc, status, cells, overflow, cell_ids, push_rec, push_cells, cmd_switch_step, cmd_rec, cmd_cells)
         return ev
 
     def eval_begin(self, ev, stream):

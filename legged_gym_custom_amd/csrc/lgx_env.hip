@@ -1780,6 +1780,11 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
       float gain = go2 ? Pm->heading_error_gain : 0.5f;
       cmd[2] = clipf(wrap_to_pi(cmd[3] - heading) * gain, -1.0f, 1.0f);
     }
+    // command schedule (include/lgx.h, ABI 10): after the resample and the heading rule, so an
+    // active segment's yaw rate stands; the env's row is read from global memory (Sh does not grow)
+    if (B.cmd_step)
+      scheduled_command(cmd, B.cmd_step + (size_t)e * LGX_CMD_SEGMENTS,
+                        B.cmd_val + (size_t)e * LGX_CMD_SEGMENTS * 4, ep);
     if (Pm->push_robots && (step % (uint64_t)Pm->push_interval == 0)) {
       root[7] = rand_range(-Pm->max_push_vel_xy, Pm->max_push_vel_xy, stg_U(AR)[S_PUSH + 0]);
       root[8] = rand_range(-Pm->max_push_vel_xy, Pm->max_push_vel_xy, stg_U(AR)[S_PUSH + 1]);
@@ -2167,6 +2172,8 @@ int lgx_bind(lgx_env* env, const lgx_buffers* b) {
     return fail(env, "lgx_bind: action_history with params.action_history_len = 0");
   if (b->push_step && !b->push_dvel) return fail(env, "lgx_bind: push_step without push_dvel");
   if (b->push_dvel && !b->push_step) return fail(env, "lgx_bind: push_dvel without push_step");
+  if (b->cmd_step && !b->cmd_val) return fail(env, "lgx_bind: cmd_step without cmd_val");
+  if (b->cmd_val && !b->cmd_step) return fail(env, "lgx_bind: cmd_val without cmd_step");
   if (env->params.curriculum && (!b->terrain_levels || !b->terrain_types || !b->terrain_origins))
     return fail(env, "lgx_bind: terrain curriculum needs terrain_levels/terrain_types/terrain_origins");
   env->buffers = *b;
@@ -2425,6 +2432,11 @@ struct EvalArgs {
   const int32_t* push_step;
   float* push_rec;
   float settle_tol;
+  // step response (ABI 10): cmd_rec NULL = none of these is read (pg, ep and settle_tol are shared)
+  const int32_t* cmd_switch_step;
+  float* cmd_rec;
+  float yaw_tol;
+  int steady_after;
 };
 
 // lgx_eval_accumulate: four lanes per env (16 envs per wave). Lane q of an env reads a quarter of
@@ -2435,6 +2447,9 @@ struct EvalArgs {
 // Push recovery (push_rec set): lane q also updates push-record column q of a pushed env (a wave
 // writes 256 contiguous bytes); the extra reads are the env's push_step, episode_length and
 // projected_gravity rows.
+// Step response (cmd_rec set): lane q also updates step-response columns 2q and 2q+1 of an env at
+// or past its command switch (a wave writes 512 contiguous bytes); the extra reads are the env's
+// cmd_switch_step, episode_length and projected_gravity rows.
 __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 2, q = t & 3;
@@ -2496,6 +2511,31 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
                            A.settle_tol);
     }
   }
+  if (A.cmd_rec) {
+    const int sw = A.cmd_switch_step[e];
+    const long long k = (long long)A.ep[e] - sw;
+    if (sw > 0 && k >= 0) {
+      float* r = A.cmd_rec + (size_t)e * LGX_EVAL_CMD_REC + 2 * q;
+      const float *pg = A.pg + (size_t)e * 3, *c = A.commands + (size_t)e * 4;
+      const float *v = A.lin_vel + (size_t)e * 3, *w = A.ang_vel + (size_t)e * 3;
+      const float y0 = command_record_col(2 * q, r[0], pg, c, v, w, k, A.settle_tol, A.yaw_tol, A.steady_after);
+      const float y1 = command_record_col(2 * q + 1, r[1], pg, c, v, w, k, A.settle_tol, A.yaw_tol, A.steady_after);
+      r[0] = y0;
+      r[1] = y1;
+    }
+  }
+}
+
+// The cell of env e for lgx_eval_reduce: cell_ids[e] when set, else level * cols + type; -1 when
+// it lies outside the rows x cols grid (never used as an index).
+__device__ inline int eval_cell_of(const int64_t* __restrict__ levels, const int64_t* __restrict__ types,
+                                   const int32_t* __restrict__ cell_ids, int e, int rows, int cols) {
+  if (cell_ids) {
+    const int id = cell_ids[e];
+    return (id < 0 || id >= rows * cols) ? -1 : id;
+  }
+  const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
+  return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : (int)(lv * cols + ty);
 }
 
 // lgx_eval_reduce: one block of 256 threads per cell. Thread t scans envs t, t+256, ... in
@@ -2523,15 +2563,9 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
   for (int k = 0; k < NC; ++k) s[k] = 0.0;
   uint32_t bad = 0;
   for (int e = tid; e < N; e += 256) {
-    if (cell_ids) {
-      const int id = cell_ids[e];
-      if (id < 0 || id >= rows * cols) { ++bad; continue; }
-      if (id != cell) continue;
-    } else {
-      const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
-      if (lv < 0 || lv >= rows || ty < 0 || ty >= cols) { ++bad; continue; }
-      if ((int)(lv * cols + ty) != cell) continue;
-    }
+    const int id = eval_cell_of(levels, types, cell_ids, e, rows, cols);
+    if (id < 0) { ++bad; continue; }
+    if (id != cell) continue;
     const int st = status[e];
     s[0] += 1.0;
     if (st == 0) continue;
@@ -2567,6 +2601,52 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
   if (tid < NA) cells[(size_t)cell * NA + tid] = v;
   else if (push_cells) push_cells[(size_t)cell * LGX_EVAL_PUSH_COLS + (tid - NA)] = v;
 }
+
+// lgx_eval_reduce's step-response cells (ABI 10, cmd_cells set): a second launch of the same
+// shape as eval_reduce_kernel (one block per cell, the same env order per thread and the same
+// fixed tree) over cmd_rec. It counts the out-of-grid envs itself, so it too writes nothing when
+// there are any; eval_reduce_kernel publishes the count.
+__global__ __launch_bounds__(256) void eval_cmd_reduce_kernel(const float* __restrict__ cmd_rec,
+                                                              const uint8_t* __restrict__ status,
+                                                              const int64_t* __restrict__ levels,
+                                                              const int64_t* __restrict__ types,
+                                                              const int32_t* __restrict__ cell_ids, int N, int rows,
+                                                              int cols, double* __restrict__ cmd_cells) {
+  constexpr int NC = LGX_EVAL_CMD_COLS;
+  __shared__ double part[4][NC];
+  __shared__ uint32_t bad_s[4];
+  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double s[NC];
+  for (int k = 0; k < NC; ++k) s[k] = 0.0;
+  uint32_t bad = 0;
+  for (int e = tid; e < N; e += 256) {
+    const int id = eval_cell_of(levels, types, cell_ids, e, rows, cols);
+    if (id < 0) { ++bad; continue; }
+    if (id != cell) continue;
+    const int st = status[e];
+    const float* r = cmd_rec + (size_t)e * LGX_EVAL_CMD_REC;
+    if (st == 0 || !(r[0] > 0.f)) continue;
+    const bool surv = st == 1;
+    s[0] += 1.0;
+    s[1] += surv ? 1.0 : 0.0;
+    s[2] += surv ? (double)r[1] : 0.0;
+    s[3] += surv ? (double)r[2] : 0.0;
+    s[4] += (double)r[3];
+    for (int k = 4; k < LGX_EVAL_CMD_REC; ++k) s[1 + k] += surv ? (double)r[k] : 0.0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int k = 0; k < NC; ++k) s[k] += __shfl_down(s[k], o, 64);
+    bad += __shfl_down(bad, o, 64);
+  }
+  if (lane == 0) {
+    for (int k = 0; k < NC; ++k) part[wv][k] = s[k];
+    bad_s[wv] = bad;
+  }
+  __syncthreads();
+  const uint32_t nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
+  if (nbad != 0 || tid >= NC) return;
+  cmd_cells[(size_t)cell * NC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
 }  // namespace lgx
 
 // shared checks of the three lgx_eval_* calls
@@ -2594,6 +2674,17 @@ static int eval_check(lgx_env* env, const lgx_eval_buffers* ev, const char* what
     if (!(ev->settle_tol >= 0.f)) return fail(env, w + ": settle_tol must be >= 0");
   }
   if (ev->push_cells && !ev->push_rec) return fail(env, w + ": push_cells needs push_rec");
+  if (ev->cmd_rec) {
+    if (!ev->cmd_switch_step) return fail(env, w + ": cmd_rec needs cmd_switch_step");
+    static const char* cnames[] = {"projected_gravity", "episode_length"};
+    const void* cptrs[] = {b.projected_gravity, b.episode_length};
+    for (size_t i = 0; i < sizeof(cptrs) / sizeof(cptrs[0]); ++i)
+      if (!cptrs[i]) return fail(env, w + ": cmd_rec needs a buffer that is not bound: " + cnames[i]);
+    if (!(ev->settle_tol >= 0.f)) return fail(env, w + ": settle_tol must be >= 0");
+    if (!(ev->yaw_tol >= 0.f)) return fail(env, w + ": yaw_tol must be >= 0");
+    if (ev->steady_after < 0) return fail(env, w + ": steady_after must be >= 0");
+  }
+  if (ev->cmd_cells && !ev->cmd_rec) return fail(env, w + ": cmd_cells needs cmd_rec");
   for (int f = 0; f < env->params.num_feet; ++f)
     if (env->params.feet_idx[f] < 0 || env->params.feet_idx[f] >= env->params.num_bodies)
       return fail(env, w + ": feet_idx outside the bodies");
@@ -2614,6 +2705,7 @@ int lgx_eval_begin(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) {
   HIP_OK(hipMemsetAsync(ev->status, 0, N, st));
   if (ev->overflow) HIP_OK(hipMemsetAsync(ev->overflow, 0, sizeof(uint32_t), st));
   if (ev->push_rec) HIP_OK(hipMemsetAsync(ev->push_rec, 0, sizeof(float) * LGX_EVAL_PUSH_REC * N, st));
+  if (ev->cmd_rec) HIP_OK(hipMemsetAsync(ev->cmd_rec, 0, sizeof(float) * LGX_EVAL_CMD_REC * N, st));
   return 0;
 }
 
@@ -2631,6 +2723,8 @@ int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stre
   A.blew_up = b.blew_up; A.acc = ev->acc; A.status = ev->status;
   A.pg = b.projected_gravity; A.ep = b.episode_length; A.push_step = b.push_step; A.push_rec = ev->push_rec;
   A.settle_tol = ev->settle_tol;
+  A.cmd_switch_step = ev->cmd_switch_step; A.cmd_rec = ev->cmd_rec; A.yaw_tol = ev->yaw_tol;
+  A.steady_after = ev->steady_after;
   A.N = p.num_envs; A.D = p.num_dof; A.NB = p.num_bodies; A.nfeet = p.num_feet; A.dt = p.dt;
   for (int f = 0; f < LGX_MAX_FEET; ++f) A.feet[f] = f < p.num_feet ? p.feet_idx[f] : 0;
   const int64_t threads = (int64_t)p.num_envs * 4;
@@ -2654,6 +2748,12 @@ int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) 
                      ev->push_rec, env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cells, ev->push_cells,
                      ev->overflow);
   HIP_OK(hipGetLastError());
+  if (ev->cmd_cells) {
+    hipLaunchKernelGGL(lgx::eval_cmd_reduce_kernel, dim3((unsigned)(ev->cell_rows * ev->cell_cols)), dim3(256), 0,
+                       (hipStream_t)hip_stream, ev->cmd_rec, ev->status, b.terrain_levels, b.terrain_types,
+                       ev->cell_ids, env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cmd_cells);
+    HIP_OK(hipGetLastError());
+  }
   return 0;
 }
 

@@ -290,6 +290,41 @@ LGX_HD float push_record_col(int col, float x, const float* pg, const float* c, 
   return err > settle_tol ? (float)k : x;
 }
 
+// Command schedule (lgx_buffers.cmd_step / cmd_val, include/lgx.h ABI 10): the active segment of
+// an env at episode length ep is the largest k with 0 <= steps_row[k] <= ep (start steps are
+// non-decreasing over the used entries; an entry < 0 is unused). If there is one, cmd takes its
+// four values exactly; if not, cmd is left alone. Called by both backends after every command
+// resample (post-physics: also after the heading rule), for an env whose buffers are bound.
+LGX_HD void scheduled_command(float* cmd, const int32_t* steps_row, const float* vals_row, long long ep) {
+  int k = -1;
+  for (int i = 0; i < LGX_CMD_SEGMENTS; ++i) {
+    const int st = steps_row[i];
+    if (st >= 0 && (long long)st <= ep) k = i;
+  }
+  if (k < 0) return;
+  for (int i = 0; i < 4; ++i) cmd[i] = vals_row[k * 4 + i];
+}
+
+// Step response (lgx_eval_buffers.cmd_rec, include/lgx.h ABI 10): one sample of an env, k >= 0
+// steps after its command switch. The new value of record column col (0..7) from its old value x;
+// pg: projected gravity, c: commands, v / w: base_lin_vel / base_ang_vel. (The kernel gives columns
+// 2q and 2q+1 to lane q of an env's four lanes, the host backend loops over them.)
+LGX_HD float command_record_col(int col, float x, const float* pg, const float* c, const float* v, const float* w,
+                                long long k, float settle_tol, float yaw_tol, int steady_after) {
+  if (col == 0) return x + 1.0f;
+  if (col == 1) {
+    const float err = sqrtf((c[0] - v[0]) * (c[0] - v[0]) + (c[1] - v[1]) * (c[1] - v[1]));
+    return err > settle_tol ? (float)(k + 1) : x;
+  }
+  if (col == 2) return fabsf(c[2] - w[2]) > yaw_tol ? (float)(k + 1) : x;
+  if (col == 3) return fmaxf(x, atan2f(nrm2(pg[0], pg[1]), -pg[2]));
+  if (k < (long long)steady_after) return x;
+  if (col == 4) return x + 1.0f;
+  if (col == 5) return x + v[0];
+  if (col == 6) return x + v[1];
+  return x + w[2];
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];
@@ -374,6 +409,9 @@ LGX_HD void reset_env_head(const lgx_task_params* Pm, const lgx_buffers& B, S& s
   }
   for (int i = 0; i < 6; ++i) root[7 + i] = rand_range(-0.5f, 0.5f, U[S_ROOT_VEL + i]);
   resample_commands(Pm, B.command_ranges, cmd, U, S_RCMD, root + 3);
+  // command schedule (include/lgx.h, ABI 10): the new episode starts in the segment of step 0
+  if (B.cmd_step)
+    scheduled_command(cmd, B.cmd_step + (size_t)e * LGX_CMD_SEGMENTS, B.cmd_val + (size_t)e * LGX_CMD_SEGMENTS * 4, 0);
   s.ep = 0;
 }
 
@@ -562,6 +600,8 @@ LGX_HD void curriculum_rewrite_env(const lgx_task_params* Pm, const lgx_buffers&
   for (int k = 0; k < 4; ++k) cmd[k] = B.commands[e * 4 + k];
   const float* quat = B.root_states + (size_t)e * 13 + 3;
   resample_commands(Pm, B.command_ranges, cmd, U, 0, quat);
+  if (B.cmd_step)  // command schedule (ABI 10): a reset env is in the segment of step 0
+    scheduled_command(cmd, B.cmd_step + (size_t)e * LGX_CMD_SEGMENTS, B.cmd_val + (size_t)e * LGX_CMD_SEGMENTS * 4, 0);
   for (int k = 0; k < 4; ++k) B.commands[e * 4 + k] = cmd[k];
   float* obs = B.obs + (size_t)e * Pm->num_obs;
   float* cr = (go2 && B.critic) ? B.critic + (size_t)e * Pm->num_critic : nullptr;

@@ -822,6 +822,10 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     quat_apply(root + 3, fwd, f);
     cmd[2] = clipf(wrap_to_pi(cmd[3] - atan2f(f[1], f[0])) * (go2 ? P->heading_error_gain : 0.5f), -1.0f, 1.0f);
   }
+  // command schedule (include/lgx.h, ABI 10): after the resample and the heading rule
+  if (B->cmd_step)
+    scheduled_command(cmd, B->cmd_step + (size_t)e * LGX_CMD_SEGMENTS,
+                      B->cmd_val + (size_t)e * LGX_CMD_SEGMENTS * 4, ep);
   if (P->push_robots && (step % (uint64_t)P->push_interval == 0)) {
     root[7] = rand_range(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 0]);
     root[8] = rand_range(-P->max_push_vel_xy, P->max_push_vel_xy, s.U[S_PUSH + 1]);
@@ -1078,6 +1082,7 @@ void eval_begin(const lgx_task_params* P, const lgx_eval_buffers* E) {
   memset(E->status, 0, N);
   if (E->overflow) *E->overflow = 0;
   if (E->push_rec) memset(E->push_rec, 0, sizeof(float) * LGX_EVAL_PUSH_REC * N);
+  if (E->cmd_rec) memset(E->cmd_rec, 0, sizeof(float) * LGX_EVAL_CMD_REC * N);
 }
 
 // lgx_eval_accumulate (include/lgx.h): the kernel's arithmetic (lgx_env.hip
@@ -1124,6 +1129,16 @@ void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_e
           r[col] = push_record_col(col, r[col], B->projected_gravity + (size_t)e * 3, c, v, k, E->settle_tol);
       }
     }
+    if (E->cmd_rec) {  // step response (ABI 10)
+      const int sw = E->cmd_switch_step[e];
+      const long long k = (long long)B->episode_length[e] - sw;
+      if (sw > 0 && k >= 0) {
+        float* r = E->cmd_rec + (size_t)e * LGX_EVAL_CMD_REC;
+        for (int col = 0; col < LGX_EVAL_CMD_REC; ++col)
+          r[col] = command_record_col(col, r[col], B->projected_gravity + (size_t)e * 3, c, v, w, k, E->settle_tol,
+                                      E->yaw_tol, E->steady_after);
+      }
+    }
   }
 }
 
@@ -1142,6 +1157,8 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
   for (size_t i = 0; i < nc; ++i) E->cells[i] = 0.0;
   if (E->push_cells)
     for (size_t i = 0; i < (size_t)rows * cols * LGX_EVAL_PUSH_COLS; ++i) E->push_cells[i] = 0.0;
+  if (E->cmd_cells)
+    for (size_t i = 0; i < (size_t)rows * cols * LGX_EVAL_CMD_COLS; ++i) E->cmd_cells[i] = 0.0;
   for (int e = 0; e < N; ++e) {  // env order: deterministic
     double* cl = E->cells + (size_t)cell_of(e) * LGX_EVAL_CELL_COLS;
     const int st = E->status[e];
@@ -1157,6 +1174,18 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
       pc[1] += (double)r[1];
       pc[2] += (double)r[2];
       if (st == 1) { pc[3] += 1.0; pc[4] += (double)r[3]; }
+    }
+    const float* cr = E->cmd_cells ? E->cmd_rec + (size_t)e * LGX_EVAL_CMD_REC : nullptr;
+    if (cr && cr[0] > 0.f) {
+      double* cc = E->cmd_cells + (size_t)cell_of(e) * LGX_EVAL_CMD_COLS;
+      cc[0] += 1.0;
+      cc[4] += (double)cr[3];
+      if (st == 1) {
+        cc[1] += 1.0;
+        cc[2] += (double)cr[1];
+        cc[3] += (double)cr[2];
+        for (int k = 4; k < LGX_EVAL_CMD_REC; ++k) cc[1 + k] += (double)cr[k];
+      }
     }
   }
   return 0;

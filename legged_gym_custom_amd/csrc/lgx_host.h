@@ -20,14 +20,16 @@ void episode_extras(const lgx_task_params* P, const lgx_buffers* B, float* means
 // lgx_command_curriculum on host buffers
 void command_curriculum(const lgx_task_params* P, const lgx_buffers* B, uint64_t seed, uint64_t step,
                         const double* global_sum_count);
-// lgx_eval_begin on host buffers: zero the records (push_rec too, when set) and the out-of-grid count
+// lgx_eval_begin on host buffers: zero the records (push_rec and cmd_rec too, when set) and the
+// out-of-grid count
 void eval_begin(const lgx_task_params* P, const lgx_eval_buffers* E);
 // lgx_eval_accumulate on host buffers (OpenMP over envs; each env's joints summed in order; the
-// push-recovery record of a pushed env when push_rec is set)
+// push-recovery record of a pushed env when push_rec is set, the step-response record of an env at
+// or past its command switch when cmd_rec is set)
 void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E);
 // lgx_eval_reduce on host buffers, envs in order. Returns the number of envs whose level / type
-// (or cell_ids entry) lies outside the cell grid; cells and push_cells are written only when it
-// is 0 (overflow always is).
+// (or cell_ids entry) lies outside the cell grid; cells, push_cells and cmd_cells are written only
+// when it is 0 (overflow always is).
 int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E);
 // the worker threads the host backend uses (OpenMP)
 int threads();

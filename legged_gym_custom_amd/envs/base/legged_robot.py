@@ -195,6 +195,46 @@ class LeggedRobot(BaseTask):
                                    f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
         return self._push_eval_cells.cpu().clone(), self._push_cells.cpu().clone()
 
+    def cmd_eval_buffers(self, rows, cols, settle_tol, yaw_tol, steady_after):
+        """A set of evaluation tensors of its own for the command test (lgx_eval_buffers with
+        cell_ids, cmd_switch_step, cmd_rec and cmd_cells, ABI 10), allocated once per (rows, cols,
+        settle_tol, yaw_tol, steady_after) so a captured loop replays on fixed addresses:
+        cmd_cell_ids [N] int32 and cmd_switch_step [N] int32 (the caller writes each env's bin and
+        the episode step its record counts from in place; <= 0: no record), cmd_rec [N, 8] and,
+        after eval_command_cells, cells [rows, cols, 12] and command cells [rows, cols, 9]. Pass
+        the result as `ev` to eval_begin / eval_accumulate."""
+        key = (int(rows), int(cols), float(settle_tol), float(yaw_tol), int(steady_after))
+        if getattr(self, "_cmd_eval_key", None) != key:
+            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
+            n = self.num_envs
+            self.cmd_eval_acc = z(n, _abi.EVAL_METRICS, dtype=torch.float32)
+            self.cmd_eval_status = z(n, dtype=torch.uint8)
+            self.cmd_cell_ids = z(n, dtype=torch.int32)
+            self.cmd_switch_step = z(n, dtype=torch.int32)
+            self.cmd_rec = z(n, _abi.EVAL_CMD_REC, dtype=torch.float32)
+            self._cmd_eval_cells = z(key[0], key[1], _abi.EVAL_CELL_COLS, dtype=torch.float64)
+            self._cmd_cells = z(key[0], key[1], _abi.EVAL_CMD_COLS, dtype=torch.float64)
+            self._cmd_eval_overflow = z(1, dtype=torch.int32)
+            self._cmd_eval = self._native.eval_buffers(
+                self.cmd_eval_acc, self.cmd_eval_status, self._cmd_eval_cells, self._cmd_eval_overflow,
+                cell_ids=self.cmd_cell_ids, cmd_switch_step=self.cmd_switch_step, cmd_rec=self.cmd_rec,
+                cmd_cells=self._cmd_cells, settle_tol=key[2], yaw_tol=key[3], steady_after=key[4])
+            self._cmd_eval_key = key
+        return self._cmd_eval
+
+    def eval_command_cells(self):
+        """lgx_eval_reduce on the command test's buffers, then (cells [rows, cols, 12], command
+        cells [rows, cols, 9]: n, survivors, the survivors' sums of linear and yaw settle steps, sum
+        of peak tilt, the survivors' sums of steady samples and of achieved vx, vy, yaw rate) float64
+        on the host. Synchronises. A cell id outside the grid is an error."""
+        ev = self._cmd_eval
+        self._native.eval_reduce(ev, self._stream())
+        bad = int(self._cmd_eval_overflow.item())
+        if bad:
+            raise _native.LgxError(f"lgx_eval_reduce: {bad} envs have a cell id outside the "
+                                   f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
+        return self._cmd_eval_cells.cpu().clone(), self._cmd_cells.cpu().clone()
+
     def eval_cells(self):
         """lgx_eval_reduce, then the cells [rows, cols, 12] float64 on the host: n_envs, n_timeout,
         n_fall, n_blowup and the sums of the 8 record columns over each cell's finished envs.
@@ -422,6 +462,9 @@ class LeggedRobot(BaseTask):
         self.push_step = self.push_dvel = None  # scheduled pushes (ABI 9): no draw, off unless allocated
         if prm.scheduled_pushes(self.cfg):
             self._alloc_push_schedule()
+        self.cmd_step = self.cmd_val = None  # command schedule (ABI 10): no draw, off unless allocated
+        if prm.scheduled_commands(self.cfg):
+            self._alloc_command_schedule()
         self.default_dof_pos = torch.tensor([self.cfg.init_state.default_joint_angles[nm] for nm in self.dof_names],
                                             device=dev).unsqueeze(0)
         self._dof_state3[..., 0] = self.default_dof_pos
@@ -502,6 +545,7 @@ class LeggedRobot(BaseTask):
             "action_delay": self.action_delay_substeps, "action_history": self.action_history,
             "motor_strength": self.motor_strengths,
             "push_step": self.push_step, "push_dvel": self.push_dvel,
+            "cmd_step": self.cmd_step, "cmd_val": self.cmd_val,
             **self._sea_buffers,
         })
 
@@ -612,6 +656,56 @@ class LeggedRobot(BaseTask):
         """No env is pushed: push_step zeroed in place (a no-op on an env without the buffers)."""
         if self.push_step is not None:
             self.push_step.zero_()
+
+    # ------------------------------------------------------------------ command schedule
+    def _alloc_command_schedule(self):
+        self.cmd_step = torch.full((self.num_envs, _abi.CMD_SEGMENTS), -1, dtype=torch.int32, device=self.device)
+        self.cmd_val = torch.zeros(self.num_envs, _abi.CMD_SEGMENTS, 4, device=self.device)
+
+    def set_command_schedule(self, steps, values):
+        """Command schedule (include/lgx.h ABI 10): from the step in which its episode length
+        reaches steps[e][k], and after every reset for a segment that starts at step 0, env e holds
+        the command values[e][k] = (vx, vy, yaw rate, heading) exactly, until its next segment
+        starts; no resample, heading rule or curriculum redraw changes it. steps: int [K'] or
+        [num_envs, K'], non-decreasing along K', each in 0 <= step < max_episode_length; values:
+        [K', 4] or [num_envs, K', 4]; K' <= 4, the unused entries are padded with -1. Written in
+        place once the buffers exist; the first call on an env built without
+        commands.scheduled_commands allocates them and re-binds, which a captured graph of this
+        env's step would not see: RuntimeError once a step of this env has been captured.
+        ValueError for wrong shapes, non-finite values, decreasing steps or a step out of range."""
+        n, K = self.num_envs, _abi.CMD_SEGMENTS
+        st = torch.as_tensor(steps, device=self.device)
+        if st.dtype.is_floating_point or st.dtype == torch.bool or st.dim() not in (1, 2) or \
+                not 1 <= st.shape[-1] <= K or (st.dim() == 2 and st.shape[0] != n):
+            raise ValueError(f"command schedule steps: an int tensor [K'] or [{n}, K'] with 1 <= K' <= {K}, got "
+                             f"{st.dtype} of shape {list(st.shape)}")
+        kk = int(st.shape[-1])
+        val = torch.as_tensor(values, dtype=torch.float32, device=self.device)
+        if tuple(val.shape) not in ((kk, 4), (n, kk, 4)):
+            raise ValueError(f"command schedule values: a tensor [{kk}, 4] or [{n}, {kk}, 4], got shape {list(val.shape)}")
+        if not bool(torch.isfinite(val).all()):
+            raise ValueError("command schedule values must be finite")
+        if int(st.min()) < 0 or int(st.max()) >= int(self.max_episode_length):
+            raise ValueError(f"command schedule steps must lie in 0 <= step < max_episode_length = "
+                             f"{int(self.max_episode_length)} (got {int(st.min())}..{int(st.max())})")
+        if kk > 1 and bool((st[..., 1:] < st[..., :-1]).any()):
+            raise ValueError("command schedule steps must not decrease")
+        if self.cmd_step is None:
+            if self._captured:
+                raise RuntimeError("set_command_schedule: this env has no command schedule buffers and its step has "
+                                   "been captured in a graph, which would go on replaying the old binding; build the "
+                                   "env with commands.scheduled_commands or set a schedule before the capture")
+            self._alloc_command_schedule()
+            self._bind()
+        self.cmd_step[:, :kk].copy_(st.to(torch.int32).expand(n, kk))
+        self.cmd_step[:, kk:].fill_(-1)
+        self.cmd_val[:, :kk].copy_(val.expand(n, kk, 4))
+
+    def clear_command_schedule(self):
+        """No env is scheduled: cmd_step filled with -1 in place (a no-op on an env without the
+        buffers). The commands an env holds stay until its next resample or reset."""
+        if self.cmd_step is not None:
+            self.cmd_step.fill_(-1)
 
     @property
     def physics_blowups(self):

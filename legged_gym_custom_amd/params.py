@@ -126,6 +126,13 @@ def scheduled_pushes(cfg):
     return bool(getattr(cfg.domain_rand, "scheduled_pushes", False))
 
 
+def scheduled_commands(cfg):
+    """cfg.commands.scheduled_commands (optional, read with getattr as scheduled_pushes is): allocate
+    and bind the command schedule buffers (lgx_buffers.cmd_step / cmd_val, include/lgx.h ABI 10) when
+    the env is built, so that env.set_command_schedule never has to re-bind."""
+    return bool(getattr(cfg.commands, "scheduled_commands", False))
+
+
 def build_task_params(cfg, model, num_envs, num_envs_total=None, env_id_offset=0, sim_dt=None, go2=True,
                       terrain_shape=None):
     P = _abi.TaskParams()

@@ -8,6 +8,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
   python legged_gym/scripts/evaluate.py --task=go2_parkour --num_envs=4096 [--policy student|teacher]
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
+         [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
 history the largest one needs); several values give one report each under "sweep", on one captured
@@ -20,8 +21,14 @@ from one of --push_dirs directions in the robot's heading frame; one run fills t
 table. The config's own random pushes (domain_rand.push_robots) are switched off for this mode, so the
 scheduled push is the only disturbance.
 
+--cmd_vx: the command-response test (PolicyEvaluator.run_command_test): every env holds --cmd_start, switches
+--cmd_at_s seconds into its episode to one command of the --cmd_vx x --cmd_vy x --cmd_yaw grid (m/s, m/s, rad/s;
+literal commands, the yaw entry is a yaw rate) and is recorded from the switch on: settle times, peak tilt,
+achieved velocities and gain per bin. The config's random pushes are switched off for this mode; not with --push_vel.
+
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
-eval_<policy>_latency.json; the push test: eval_<policy>_push.json)."""
+eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
+eval_<policy>_command.json)."""
 import argparse
 import json
 import os
@@ -41,7 +48,8 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
-             push_vel=None, push_dirs=8, push_at_s=2.0):
+             push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
+             cmd_start=None):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -55,6 +63,11 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
             raise ValueError("--push_vel is a mode of its own: not with --action_delay_ms / --motor_strength")
         env_cfg.domain_rand.scheduled_pushes = True  # the push buffers exist before any capture
         env_cfg.domain_rand.push_robots = False      # the scheduled push is the only disturbance
+    if cmd_vx:
+        if push_vel or delays_s or motor_strength is not None:
+            raise ValueError("--cmd_vx is a mode of its own: not with --push_vel / --action_delay_ms / --motor_strength")
+        env_cfg.commands.scheduled_commands = True  # the schedule buffers exist before any capture
+        env_cfg.domain_rand.push_robots = False     # the command switch is the only disturbance
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
 
     train_cfg.runner.resume = True
@@ -69,6 +82,11 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         report = dict(**head, **ev.run_push_test(push_vel, directions=push_dirs, at_s=push_at_s, num_steps=eval_steps,
                                                  graph=graph))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_push.json")
+    elif cmd_vx:
+        report = dict(**head, **ev.run_command_test(cmd_vx, vy=cmd_vy or (0.0,), yaw=cmd_yaw or (0.0,), at_s=cmd_at_s,
+                                                    start=cmd_start or (0.0, 0.0, 0.0), num_steps=eval_steps,
+                                                    graph=graph))
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_command.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength)
         report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
@@ -91,11 +109,19 @@ def main(argv=None):
     p.add_argument("--push_vel", type=lambda s: [float(v) for v in s.split(",")], default=None)
     p.add_argument("--push_dirs", type=int, default=8)
     p.add_argument("--push_at_s", type=float, default=2.0)
+    floats = lambda s: [float(v) for v in s.split(",")]  # noqa: E731
+    p.add_argument("--cmd_vx", type=floats, default=None)
+    p.add_argument("--cmd_vy", type=floats, default=None)
+    p.add_argument("--cmd_yaw", type=floats, default=None)
+    p.add_argument("--cmd_at_s", type=float, default=2.0)
+    p.add_argument("--cmd_start", type=floats, default=None)
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
     report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
                          action_delay_ms=own.action_delay_ms, motor_strength=own.motor_strength,
-                         push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s)
+                         push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s,
+                         cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
+                         cmd_start=own.cmd_start)
     print(json.dumps(report))
     return report
 

@@ -24,6 +24,11 @@ kernel's scheduled push (lgx_buffers.push_step / push_dvel, ABI 9); the envs are
 speed x direction bins through the evaluation's free cell key (lgx_eval_buffers.cell_ids) and a
 per-env recovery record (push_rec) is reduced per bin: one run gives the whole polar table.
 
+Command response (run_command_test): every env holds a start command, switches once, at the same
+episode step, to the command of its bin of a commanded vx x vy x yaw-rate grid through the step
+kernel's command schedule (lgx_buffers.cmd_step / cmd_val, ABI 10), and a per-env step-response
+record (cmd_rec) is reduced per bin: one run gives the tracking envelope and the step response.
+
 Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
@@ -60,6 +65,21 @@ def push_cell_report(pcell, dt):
             "survivors": surv, "mean_settle_s": div(float(pcell[4]) * dt, surv)}
 
 
+def command_cell_report(ccell, dt, command):
+    """The step-response entries of one command cell row [9] (n, survivors, the survivors' sums of
+    linear and yaw settle steps, sum of peak tilt, the survivors' sums of steady samples and of
+    achieved vx, vy, yaw rate) for the bin's command (vx, vy, yaw). Means without data are None."""
+    c = [float(v) for v in ccell]
+    n, surv = int(round(c[0])), int(round(c[1]))
+    div = lambda a, b: a / b if b > 0 else None  # noqa: E731
+    achieved = [c[6] / c[5], c[7] / c[5], c[8] / c[5]] if c[5] > 0 else None
+    norm2 = command[0] * command[0] + command[1] * command[1]
+    gain = (achieved[0] * command[0] + achieved[1] * command[1]) / norm2 if achieved is not None and norm2 > 0 else None
+    return {"switched": n, "survivors": surv, "mean_settle_s": div(c[2] * dt, surv),
+            "mean_yaw_settle_s": div(c[3] * dt, surv), "mean_peak_tilt_rad": div(c[4], n), "achieved": achieved,
+            "gain": gain}
+
+
 def _min_max(t, kind):
     return None if t is None else [kind(t.min()), kind(t.max())]
 
@@ -79,9 +99,11 @@ class PolicyEvaluator:
         self.on_gpu = self.device.startswith("cuda")
         self._graph = None
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
+        self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
         self._fused = None
         self.last_cells = None
         self.last_push_cells = self.last_push_bins = None
+        self.last_cmd_cells = self.last_cmd_bins = None
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -102,7 +124,7 @@ class PolicyEvaluator:
         """Re-pack the fused act kernel's weights (after the runner loaded or trained them)."""
         if self._fused is not None:
             self._fused.refresh_weights()
-            self._graph = self._push_graph = None
+            self._graph = self._push_graph = self._cmd_graph = None
 
     # ------------------------------------------------------------------ one iteration
     def act(self):
@@ -284,6 +306,83 @@ class PolicyEvaluator:
                 "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
                 "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
                 "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)],
+                "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
+
+    # ------------------------------------------------------------------ command response
+    def run_command_test(self, vx, vy=(0.0,), yaw=(0.0,), at_s=2.0, start=(0.0, 0.0, 0.0), steady_after_s=1.0,
+                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True):
+        """What does the robot do when commanded, how fast does it get there, and does it stay up:
+        one run in which every env holds the command `start` = (vx, vy, yaw rate), switches at
+        episode step round(at_s / dt) to the command of its bin (vx[ix], vy[iy], yaw[iw]) and is
+        recorded from the switch on. Bin index (ix * |vy| + iy) * |yaw| + iw; envs get bins by
+        randperm(num_envs, seeded with env.seed) % bins. The commands are literal (no small-command
+        zeroing, no heading controller: yaw is a yaw rate) and come back after a reset: a reset env
+        holds `start` again and switches again, but only an env's first episode is recorded.
+
+        The records go to eval buffers of their own (env.cmd_eval_buffers: the bin is the cell key,
+        plus the per-env step-response record of include/lgx.h), and this mode's captured loop is a
+        graph of its own. The env needs the schedule buffers before any of its steps is captured
+        (commands.scheduled_commands = True, or call this before run()). The schedule is written
+        before the run's reset and cleared in place when the run ends, so a following run() is the
+        plain one.
+
+        Returns the report: "bins"[ix][iy][iw] with the REPORT_KEYS entries and switched (finished
+        envs with post-switch samples), survivors (timed out among them), mean_settle_s /
+        mean_yaw_settle_s (the survivors' mean time from the switch until the linear velocity / yaw
+        rate error stays within settle_tol / yaw_tol; 0: never off), mean_peak_tilt_rad, achieved
+        [vx, vy, yaw] (the survivors' mean velocities over the samples from steady_after_s after the
+        switch on) and gain (achieved velocity projected on the commanded (vx, vy) direction over its
+        norm; None for a zero linear command); "total" likewise without achieved / gain; vx, vy,
+        yaw, start, switch_step, steady_after, the tolerances. None where there is no data, never NaN.
+        ValueError: an empty list, a non-finite entry, a switch step outside 0 < step <
+        max_episode_length, a negative or non-finite tolerance or steady_after_s."""
+        env = self.env
+        vx, vy, yaw, start = ([float(v) for v in lst] for lst in (vx, vy, yaw, start))
+        if min(len(vx), len(vy), len(yaw)) < 1 or len(start) != 3 or \
+                not all(math.isfinite(v) for v in vx + vy + yaw + start):
+            raise ValueError(f"command test: vx, vy and yaw need at least one finite entry each and start three "
+                             f"(got {vx}, {vy}, {yaw}, {start})")
+        for name, tol in (("settle_tol", settle_tol), ("yaw_tol", yaw_tol), ("steady_after_s", steady_after_s)):
+            if not (math.isfinite(float(tol)) and float(tol) >= 0.0):
+                raise ValueError(f"command test: {name} must be finite and >= 0 (got {tol})")
+        dt, at = float(env.dt), float(at_s)
+        step = int(round(at / dt)) if math.isfinite(at) else -1
+        if not 0 < step < int(env.max_episode_length):
+            raise ValueError(f"command test: at_s = {at_s} s is step {step}, outside 0 < step < max_episode_length = "
+                             f"{int(env.max_episode_length)}")
+        steady = int(round(float(steady_after_s) / dt))
+        n, nx, ny, nw = env.num_envs, len(vx), len(vy), len(yaw)
+        bins = torch.randperm(n, generator=torch.Generator().manual_seed(int(env.seed))) % (nx * ny * nw)
+        grid = torch.tensor([[a, b, c, 0.0] for a in vx for b in vy for c in yaw], dtype=torch.float32)
+        values = torch.stack([torch.tensor(start + [0.0], dtype=torch.float32).expand(n, 4), grid[bins]], 1)
+        steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
+        use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
+        key = (nx, ny * nw, float(settle_tol), float(yaw_tol), steady)
+        try:
+            # before begin: its reset sees segment 0 (the first call allocates: refused once a loop is captured)
+            env.set_command_schedule([0, step], values)
+            ev = env.cmd_eval_buffers(*key)
+            env.cmd_cell_ids.copy_(bins.to(torch.int32))
+            env.cmd_switch_step.fill_(step)
+            if use_graph and (self._cmd_graph is None or self._cmd_graph_key != key):
+                self._cmd_graph, self._cmd_graph_key = self._capture(ev), key
+            self.begin(ev)
+            t0 = self._loop(steps, self._cmd_graph if use_graph else None, ev)
+            cells, ccells = env.eval_command_cells()  # reduce + the host read (synchronises)
+            wall = time.perf_counter() - t0
+        finally:
+            env.clear_command_schedule()
+        self.last_cells, self.last_cmd_cells, self.last_cmd_bins = cells, ccells, bins
+        w = self.mass * self.gravity
+        both = lambda c, p, cmd: {**cell_report(c, dt, w), **command_cell_report(p, dt, cmd)}  # noqa: E731
+        total = both(cells.reshape(-1, cells.shape[2]).sum(0), ccells.reshape(-1, ccells.shape[2]).sum(0), (0.0, 0.0, 0.0))
+        del total["achieved"], total["gain"]  # (means over different commands say nothing)
+        return {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
+                "graph": use_graph, "vx": vx, "vy": vy, "yaw": yaw, "start": start, "switch_step": step,
+                "switch_at_s": step * dt, "steady_after": steady, "settle_tol": float(settle_tol),
+                "yaw_tol": float(yaw_tol), "total": total,
+                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
+                           for iw in range(nw)] for iy in range(ny)] for ix in range(nx)],
                 "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
 
     def sweep_action_delay(self, delays_s, **run_kwargs):

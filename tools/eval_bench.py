@@ -44,11 +44,17 @@ def main():
     p.add_argument("--push_vel", type=lambda s: [float(v) for v in s.split(",")], default=None,
                    help="also time run_push_test with these speeds (the env is built with scheduled_pushes)")
     p.add_argument("--push_dirs", type=int, default=8)
+    p.add_argument("--cmd_vx", type=lambda s: [float(v) for v in s.split(",")], default=None,
+                   help="also time run_command_test with these forward commands (the env is built with "
+                        "scheduled_commands; not with --push_vel)")
+    p.add_argument("--cmd_vy", type=lambda s: [float(v) for v in s.split(",")], default=[0.0])
+    p.add_argument("--cmd_yaw", type=lambda s: [float(v) for v in s.split(",")], default=[0.0])
     p.add_argument("--profile", action="store_true")
     p.add_argument("--stats")
     p.add_argument("--merge")
     p.add_argument("--out")
     a = p.parse_args()
+    assert not (a.push_vel and a.cmd_vx), "--push_vel or --cmd_vx, one at a time"
     if a.stats:
         return merge_stats(a.stats, a.merge)
     import torch
@@ -61,6 +67,8 @@ def main():
     cfg.terrain.curriculum = cfg.commands.curriculum = False
     if a.push_vel:
         cfg.domain_rand.scheduled_pushes = True  # buffers bound with no env scheduled: the plain run's step is unchanged
+    if a.cmd_vx:
+        cfg.commands.scheduled_commands = True  # likewise: bound, every entry unused
     args = get_args([f"--task={a.task}", "--headless", f"--num_envs={a.num_envs}", "--seed=1",
                      f"--sim_device={a.device}", f"--rl_device={a.device}"])
     env, _ = task_registry.make_env(a.task, args, env_cfg=cfg)
@@ -74,18 +82,23 @@ def main():
     ev.run(20, graph=False)
     rates = {"graph": [], "eager": []}
     push = (lambda steps, graph: ev.run_push_test(a.push_vel, directions=a.push_dirs, num_steps=steps, graph=graph))
+    cmd = (lambda steps, graph: ev.run_command_test(a.cmd_vx, vy=a.cmd_vy, yaw=a.cmd_yaw, num_steps=steps, graph=graph))
     if a.push_vel:
         rates.update(push_graph=[], push_eager=[])
         push(20, True)
         push(20, False)
+    if a.cmd_vx:
+        rates.update(cmd_graph=[], cmd_eager=[])
+        cmd(20, True)
+        cmd(20, False)
     for _ in range(a.repeats):
         for mode in rates:
             graph = mode.endswith("graph")
-            r = push(a.steps, graph) if mode.startswith("push") else ev.run(a.steps, graph=graph)
+            r = (push if mode.startswith("push") else cmd if mode.startswith("cmd") else ev.run)(a.steps, graph)
             assert a.device == "cpu" or r["graph"] == graph
             rates[mode].append(r["env_steps_per_s"])
-    pr = r if a.push_vel else None
-    r = ev.run(a.steps) if a.push_vel else r
+    pr, cr = r if a.push_vel else None, r if a.cmd_vx else None
+    r = ev.run(a.steps) if pr or cr else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
                                for m, v in rates.items()},
@@ -95,6 +108,14 @@ def main():
         doc["push_test"]["per_speed"] = [
             {"speed": v, "episodes": sum(c["episodes"] for c in row), "survivors": sum(c["survivors"] for c in row),
              "pushed": sum(c["pushed"] for c in row)} for v, row in zip(pr["speeds"], pr["bins"])]
+    if cr:
+        doc["command_test"] = {k: cr[k] for k in ("vx", "vy", "yaw", "start", "switch_step", "steady_after", "settle_tol",
+                                                  "yaw_tol", "total")}
+        doc["command_test"]["per_vx"] = [
+            {"vx": v, "episodes": sum(c["episodes"] for r_ in row for c in r_),
+             "survivors": sum(c["survivors"] for r_ in row for c in r_),
+             "switched": sum(c["switched"] for r_ in row for c in r_),
+             "gain": [[c["gain"] for c in r_] for r_ in row]} for v, row in zip(cr["vx"], cr["bins"])]
     print(json.dumps(doc))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
