@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 10
+#define LGX_ABI_VERSION 11
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -53,6 +53,7 @@ extern "C" {
 #define LGX_CMD_SEGMENTS 4        /* segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val) */
 #define LGX_EVAL_CMD_REC 8        /* per-env step-response record columns (lgx_eval_buffers.cmd_rec) */
 #define LGX_EVAL_CMD_COLS 9       /* per-cell step-response columns (lgx_eval_buffers.cmd_cells) */
+#define LGX_TRACE_COLS 76         /* columns of a flight-recorder row (lgx_trace_buffers.ring) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -528,6 +529,50 @@ int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stre
  * outside the grid is never used as an index: such envs are counted in *overflow, and cells are
  * then left unwritten (the host backend fails the call instead). */
 int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream);
+
+/* ABI 11. Flight recorder: a ring buffer per env that holds the last `depth` control steps of the
+ * env's FIRST episode since lgx_trace_begin and freezes when that episode ends (the rule of
+ * lgx_eval_buffers.status), so that after an evaluation the time series of chosen envs (the falls,
+ * say) can be unrolled on the device and read. The reference has no counterpart (its play.py logs
+ * one robot). Buffers are the caller's, in the env's memory space (device, or host for device < 0).
+ * The ring takes N * depth * 304 bytes. */
+typedef struct lgx_trace_buffers {
+  float* ring;     /* [N, depth, LGX_TRACE_COLS] */
+  int32_t* count;  /* [N] rows written in the env's first episode (may exceed depth); row i lives in
+                      slot i % depth */
+  uint8_t* status; /* [N] 0 recording, 1 timed out, 2 fell, 3 blew up: the lgx_eval_buffers.status rule */
+  int32_t depth;   /* K >= 1 */
+} lgx_trace_buffers;
+int64_t lgx_sizeof_trace_buffers(void);
+/* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph; each
+ * refuses depth < 1 or a NULL member. lgx_trace_begin: zero ring, count and status. */
+int lgx_trace_begin(lgx_env* env, const lgx_trace_buffers* tb, void* hip_stream);
+/* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
+ * status[e] == 0:
+ *   reset[e]: status[e] = 3 if blew_up is bound and set, else 1 if time_out[e], else 2; no row (the
+ *             step has already reset that env's state, as for lgx_eval_accumulate).
+ *   else one row into slot count[e] % depth, then count[e] += 1. Row columns (a joint slot
+ *             j >= num_dof or a foot slot f >= num_feet is 0):
+ *     0             (float)episode_length[e]
+ *     1-3, 4-7      root_states[e][0..2] (position), [3..6] (quaternion xyzw)
+ *     8-10, 11-13, 14-16   base_lin_vel[e], base_ang_vel[e], projected_gravity[e]
+ *     17-20         commands[e][0..3]
+ *     21-32, 33-44  dof_state[e][j][0], dof_state[e][j][1]
+ *     45-56, 57-68  torques[e][j], actions[e][j] (the clipped actions)
+ *     69-72         sqrtf(x^2 + y^2 + z^2) of contact_forces[e][feet_idx[f]]
+ *     73            rew[e]
+ *     74, 75        the largest such norm over the bodies NOT in feet_idx (0 if none) and (float) that
+ *                   body's index (the lowest index wins a tie; -1 when the norm is 0)
+ * Envs with status != 0 are never written again. Every source buffer above must be bound, and
+ * reset and time_out; blew_up is optional (a failure names the missing buffer). */
+int lgx_trace_record(lgx_env* env, const lgx_trace_buffers* tb, void* hip_stream);
+/* Unroll the rings of the m envs ids[i] (ids: device memory on the GPU; duplicates allowed), oldest
+ * row first, newest last: with e = ids[i] and L = min(count[e], depth),
+ *   out[i][depth - L + j] = ring[e][(count[e] - L + j) % depth]  for j < L,
+ * the rows before them zero, out_len[i] = L. An id outside [0, N) is never used as an index: its
+ * rows are zero and its out_len is -1. out: [m, depth, LGX_TRACE_COLS], out_len: [m]. */
+int lgx_trace_gather(lgx_env* env, const lgx_trace_buffers* tb, const int32_t* ids, int32_t m, float* out,
+                     int32_t* out_len, void* hip_stream);
 const char* lgx_last_error(const lgx_env* env);
 void lgx_destroy(lgx_env* env);
 

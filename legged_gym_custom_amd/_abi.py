@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -27,6 +27,7 @@ EVAL_PUSH_COLS = 5   # per-cell push-recovery columns (lgx_eval_buffers.push_cel
 CMD_SEGMENTS = 4     # segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val)
 EVAL_CMD_REC = 8     # per-env step-response record columns (lgx_eval_buffers.cmd_rec)
 EVAL_CMD_COLS = 9    # per-cell step-response columns (lgx_eval_buffers.cmd_cells)
+TRACE_COLS = 76      # columns of a flight-recorder row (lgx_trace_buffers.ring)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -156,8 +157,13 @@ class EvalBuffers(C.Structure):
                 ("cmd_switch_step", P), ("cmd_rec", P), ("cmd_cells", P), ("yaw_tol", f32), ("steady_after", i32)]
 
 
+class TraceBuffers(C.Structure):
+    """lgx_trace_buffers (ABI 11): the flight recorder's per-env rings."""
+    _fields_ = [("ring", P), ("count", P), ("status", P), ("depth", i32)]
+
+
 STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buffers,
-           "lgx_eval_buffers": EvalBuffers}
+           "lgx_eval_buffers": EvalBuffers, "lgx_trace_buffers": TraceBuffers}
 SIZEOF = {"lgx_sizeof_" + name[len("lgx_"):]: name for name in STRUCTS}  # sizeof export -> typedef
 
 CONSTANTS = {
@@ -169,6 +175,7 @@ CONSTANTS = {
     "LGX_MAX_ACTION_HISTORY": MAX_ACTION_HISTORY,
     "LGX_EVAL_PUSH_REC": EVAL_PUSH_REC, "LGX_EVAL_PUSH_COLS": EVAL_PUSH_COLS,
     "LGX_CMD_SEGMENTS": CMD_SEGMENTS, "LGX_EVAL_CMD_REC": EVAL_CMD_REC, "LGX_EVAL_CMD_COLS": EVAL_CMD_COLS,
+    "LGX_TRACE_COLS": TRACE_COLS,
     "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
     "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
     **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},
@@ -193,6 +200,9 @@ SIGNATURES = {
     "lgx_eval_begin": (cint, (P, P, P)),
     "lgx_eval_accumulate": (cint, (P, P, P)),
     "lgx_eval_reduce": (cint, (P, P, P)),
+    "lgx_trace_begin": (cint, (P, P, P)),
+    "lgx_trace_record": (cint, (P, P, P)),
+    "lgx_trace_gather": (cint, (P, P, P, i32, P, P, P)),
     "lgx_last_error": (C.c_char_p, (P,)),
     "lgx_destroy": (None, (P,)),
 }

@@ -156,6 +156,53 @@ class NativeEnv:
         """lgx_eval_reduce: records -> cells (and the out-of-grid count in ev.overflow)."""
         self._check(self._L.lgx_eval_reduce(self.handle, C.byref(ev), C.c_void_p(stream)), "lgx_eval_reduce")
 
+    def trace_buffers(self, ring, count, status):
+        """lgx_trace_buffers (ABI 11) over the given tensors: ring [N, depth, 76] fp32, count [N]
+        int32, status [N] uint8, all in the env's memory space; depth is the ring's second dimension
+        (>= 1). The ring takes N * depth * 304 bytes."""
+        n = self.params.num_envs
+        if ring is not None and (ring.dim() != 3 or ring.shape[1] < 1):
+            raise LgxError(f"trace buffer ring must be [N, depth >= 1, {_abi.TRACE_COLS}] (depth = 0 holds no row)")
+        want = {"ring": (None if ring is None else (n, ring.shape[1], _abi.TRACE_COLS), "float32"),
+                "count": ((n,), "int32"), "status": ((n,), "uint8")}
+        tb = _abi.TraceBuffers()
+        for name, t in (("ring", ring), ("count", count), ("status", status)):
+            if t is None:
+                raise LgxError(f"trace buffer {name} is required")
+            shape, dtype = want[name]
+            if tuple(t.shape) != shape or str(t.dtype) != "torch." + dtype or not t.is_contiguous() \
+                    or t.device.type != self._dev_type:
+                raise LgxError(f"trace buffer {name} must be a contiguous {dtype} tensor {list(shape)} "
+                               f"in the env's memory space")
+            setattr(tb, name, t.data_ptr())
+        tb.depth = int(ring.shape[1])
+        tb._keep = (ring, count, status)
+        return tb
+
+    def trace_begin(self, tb, stream):
+        """lgx_trace_begin: zero the rings, counts and statuses (tb: trace_buffers(...))."""
+        self._check(self._L.lgx_trace_begin(self.handle, C.byref(tb), C.c_void_p(stream)), "lgx_trace_begin")
+
+    def trace_record(self, tb, stream):
+        """lgx_trace_record: one row per recording env from the step just run."""
+        self._check(self._L.lgx_trace_record(self.handle, C.byref(tb), C.c_void_p(stream)), "lgx_trace_record")
+
+    def trace_gather(self, tb, ids, out, out_len, stream):
+        """lgx_trace_gather: unroll the rings of the envs ids [m] int32 into out [m, depth, 76] fp32 and
+        out_len [m] int32 (all in the env's memory space). An id outside [0, N) gives zero rows and
+        out_len -1."""
+        m = int(ids.shape[0])
+        want = (("ids", ids, (m,), "int32"), ("out", out, (m, tb.depth, _abi.TRACE_COLS), "float32"),
+                ("out_len", out_len, (m,), "int32"))
+        for name, t, shape, dtype in want:
+            if tuple(t.shape) != shape or str(t.dtype) != "torch." + dtype or not t.is_contiguous() \
+                    or t.device.type != self._dev_type:
+                raise LgxError(f"trace gather {name} must be a contiguous {dtype} tensor {list(shape)} "
+                               f"in the env's memory space")
+        self._check(self._L.lgx_trace_gather(self.handle, C.byref(tb), C.c_void_p(ids.data_ptr()), m,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(out_len.data_ptr()),
+                                             C.c_void_p(stream)), "lgx_trace_gather")
+
     def __del__(self):
         try:
             if self.handle:

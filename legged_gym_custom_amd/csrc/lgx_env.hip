@@ -2757,6 +2757,161 @@ int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) 
   return 0;
 }
 
+// ------------------------------------------------------------------ flight recorder (ABI 11)
+namespace lgx {
+// lgx_trace_record: sixteen lanes per env (4 envs per wave, a group never straddles a wave), five
+// column passes: lane l writes columns l, l + 16, ..., so a pass stores 64 contiguous bytes per env
+// and a row is 304 contiguous bytes. count[e], status[e] and reset[e] are read by every lane of the
+// group before the first store of the kernel, and only lane 0 of the group writes count / status,
+// after the row: no lane can see this launch's update (one thread per (env, column) spread over
+// waves could). Lane l also forms the force norm of bodies l and l + 16; four xor shuffles fold the
+// non-foot peak of columns 74 / 75 (trace_peak_merge is order-free). About 130 floats in and 76
+// out per env (8.5 us at 4096 envs: latency, a twentieth of the HBM rate). No LDS, no atomics;
+// frozen envs store nothing.
+__global__ __launch_bounds__(256) void trace_record_kernel(const lgx_task_params* __restrict__ Pm,
+                                                           const lgx_buffers* __restrict__ Bd, float* __restrict__ ring,
+                                                           int32_t* __restrict__ count, uint8_t* __restrict__ status,
+                                                           int depth) {
+  const lgx_buffers& B = *Bd;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, l = t & 15;
+  // no early return: the shuffles below need every lane of a group; tail lanes load nothing
+  const bool live = e < Pm->num_envs;
+  const int st = live ? status[e] : 1;
+  const int rs = live ? B.reset[e] : 0;
+  const int cnt = live ? count[e] : 0;
+  const bool row = st == 0 && !rs;
+  float pn = 0.f;
+  int pb = -1;
+  if (row) {
+    const int NB = Pm->num_bodies;
+    for (int b = l; b < NB; b += 16) {
+      if (trace_is_foot(Pm, b)) continue;
+      const float* c = B.contact_forces + ((size_t)e * NB + b) * 3;
+      trace_peak_merge(pn, pb, nrm3(c[0], c[1], c[2]), b);
+    }
+  }
+  for (int o = 1; o <= 8; o <<= 1) {
+    const float on = __shfl_xor(pn, o, 64);
+    const int ob = __shfl_xor(pb, o, 64);
+    trace_peak_merge(pn, pb, on, ob);
+  }
+  if (!live || st != 0) return;
+  if (rs) {
+    if (l == 0) status[e] = (B.blew_up && B.blew_up[e]) ? 3 : (B.time_out[e] ? 1 : 2);
+    return;
+  }
+  float* dst = ring + ((size_t)e * depth + (size_t)(cnt % depth)) * LGX_TRACE_COLS;
+  LGX_UNROLL
+  for (int p = 0; p < 5; ++p) {
+    const int col = l + 16 * p;
+    if (col >= LGX_TRACE_COLS) break;
+    dst[col] = col == 74 ? pn : (col == 75 ? (float)pb : trace_col(col, Pm, B, e));
+  }
+  if (l == 0) count[e] = cnt + 1;
+}
+
+// lgx_trace_gather: one thread per output float, grid-stride; consecutive lanes read consecutive
+// addresses of a ring row and write consecutive addresses of the output (256 contiguous bytes per
+// wave instruction on both sides). An id outside [0, N) is never used as an index.
+__global__ __launch_bounds__(256) void trace_gather_kernel(const float* __restrict__ ring,
+                                                           const int32_t* __restrict__ count,
+                                                           const int32_t* __restrict__ ids, int N, int m, int depth,
+                                                           float* __restrict__ out, int32_t* __restrict__ out_len) {
+  const int64_t per = (int64_t)depth * LGX_TRACE_COLS, total = (int64_t)m * per;
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(x / per);
+    const int64_t rem = x - (int64_t)i * per;
+    const int r = (int)(rem / LGX_TRACE_COLS), c = (int)(rem % LGX_TRACE_COLS);
+    const int e = ids[i];
+    const bool ok = e >= 0 && e < N;
+    const int cn = ok ? count[e] : 0;
+    const int L = max(0, min(cn, depth));
+    float v = 0.f;
+    if (r >= depth - L) {
+      const int slot = (cn - L + (r - (depth - L))) % depth;
+      v = ring[((size_t)e * depth + slot) * LGX_TRACE_COLS + c];
+    }
+    out[x] = v;
+    if (rem == 0) out_len[i] = ok ? L : -1;
+  }
+}
+}  // namespace lgx
+
+// shared checks of the three lgx_trace_* calls
+static int trace_check(lgx_env* env, const lgx_trace_buffers* tb, const char* what, bool record) {
+  if (!env) return -2;
+  const std::string w(what);
+  if (!env->bound) return fail(env, w + " before lgx_bind");
+  if (!tb) return fail(env, w + ": trace buffers are NULL");
+  if (tb->depth < 1) return fail(env, w + ": depth must be >= 1");
+  if (!tb->ring) return fail(env, w + ": ring is NULL");
+  if (!tb->count) return fail(env, w + ": count is NULL");
+  if (!tb->status) return fail(env, w + ": status is NULL");
+  if (!record) return 0;
+  const lgx_buffers& b = env->buffers;
+  static const char* names[] = {"episode_length", "root_states", "base_lin_vel", "base_ang_vel", "projected_gravity",
+                                "commands", "dof_state", "torques", "actions", "contact_forces", "rew", "reset",
+                                "time_out"};
+  const void* ptrs[] = {b.episode_length, b.root_states, b.base_lin_vel, b.base_ang_vel, b.projected_gravity,
+                        b.commands, b.dof_state, b.torques, b.actions, b.contact_forces, b.rew, b.reset, b.time_out};
+  for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
+    if (!ptrs[i]) return fail(env, w + ": required buffer not bound: " + names[i]);
+  const lgx_task_params& p = env->params;
+  if (p.num_dof > LGX_MAX_DOF || p.num_actions > LGX_MAX_DOF) return fail(env, w + ": more joints than a row holds");
+  for (int f = 0; f < p.num_feet; ++f)
+    if (p.feet_idx[f] < 0 || p.feet_idx[f] >= p.num_bodies) return fail(env, w + ": feet_idx outside the bodies");
+  return 0;
+}
+
+int64_t lgx_sizeof_trace_buffers(void) { return (int64_t)sizeof(lgx_trace_buffers); }
+
+int lgx_trace_begin(lgx_env* env, const lgx_trace_buffers* tb, void* hip_stream) {
+  if (int rc = trace_check(env, tb, "lgx_trace_begin", false)) return rc;
+  if (env->host) {
+    lgxh::trace_begin(&env->params, tb);
+    return 0;
+  }
+  const size_t N = (size_t)env->params.num_envs;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_OK(hipMemsetAsync(tb->ring, 0, sizeof(float) * LGX_TRACE_COLS * N * (size_t)tb->depth, st));
+  HIP_OK(hipMemsetAsync(tb->count, 0, sizeof(int32_t) * N, st));
+  HIP_OK(hipMemsetAsync(tb->status, 0, N, st));
+  return 0;
+}
+
+int lgx_trace_record(lgx_env* env, const lgx_trace_buffers* tb, void* hip_stream) {
+  if (int rc = trace_check(env, tb, "lgx_trace_record", true)) return rc;
+  if (env->host) {
+    lgxh::trace_record(&env->params, &env->buffers, tb);
+    return 0;
+  }
+  const int64_t threads = (int64_t)env->params.num_envs * 16;
+  hipLaunchKernelGGL(lgx::trace_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, env->d_params, env->d_buffers, tb->ring, tb->count, tb->status, tb->depth);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int lgx_trace_gather(lgx_env* env, const lgx_trace_buffers* tb, const int32_t* ids, int32_t m, float* out,
+                     int32_t* out_len, void* hip_stream) {
+  if (int rc = trace_check(env, tb, "lgx_trace_gather", false)) return rc;
+  if (m < 0) return fail(env, "lgx_trace_gather: m must be >= 0");
+  if (m == 0) return 0;
+  if (!ids) return fail(env, "lgx_trace_gather: ids is NULL");
+  if (!out || !out_len) return fail(env, "lgx_trace_gather: out and out_len are required");
+  if (env->host) {
+    lgxh::trace_gather(&env->params, tb, ids, m, out, out_len);
+    return 0;
+  }
+  const int64_t total = (int64_t)m * tb->depth * LGX_TRACE_COLS;
+  const int64_t want = (total + 255) / 256, blocks = want < 2048 ? want : 2048;  // grid-stride beyond
+  hipLaunchKernelGGL(lgx::trace_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, tb->ring,
+                     tb->count, ids, env->params.num_envs, m, tb->depth, out, out_len);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 #ifdef LGX_PHASE_CLOCK
 // dev builds only: per-env phase cycle counters ([num_envs][16] uint32, device memory)
 int lgx_debug_phase_buffer(uint32_t* dev_ptr) {

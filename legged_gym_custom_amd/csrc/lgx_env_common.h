@@ -325,6 +325,49 @@ LGX_HD float command_record_col(int col, float x, const float* pg, const float* 
   return x + w[2];
 }
 
+// Flight recorder (lgx_trace_buffers, include/lgx.h ABI 11): column col < 74 of env e's row, from the
+// buffers as the step left them: the copied columns (0-68, 73) and the foot force norms (69-72).
+// (The kernel gives column l + 16 p to lane l of an env's sixteen lanes in pass p, the host backend
+// loops over the columns. Columns 74 and 75 come from trace_peak_merge below.)
+LGX_HD float trace_col(int col, const lgx_task_params* Pm, const lgx_buffers& B, int e) {
+  const int D = Pm->num_dof;
+  const size_t se = (size_t)e;
+  if (col == 0) return (float)B.episode_length[se];
+  if (col < 8) return B.root_states[se * 13 + (col - 1)];
+  if (col < 11) return B.base_lin_vel[se * 3 + (col - 8)];
+  if (col < 14) return B.base_ang_vel[se * 3 + (col - 11)];
+  if (col < 17) return B.projected_gravity[se * 3 + (col - 14)];
+  if (col < 21) return B.commands[se * 4 + (col - 17)];
+  if (col < 69) {
+    const int k = (col - 21) / LGX_MAX_DOF, j = (col - 21) % LGX_MAX_DOF;
+    if (j >= D) return 0.f;
+    if (k < 2) return B.dof_state[(se * D + j) * 2 + k];
+    return k == 2 ? B.torques[se * D + j] : B.actions[se * Pm->num_actions + j];
+  }
+  if (col < 73) {
+    const int f = col - 69;
+    if (f >= Pm->num_feet) return 0.f;
+    const float* c = B.contact_forces + (se * Pm->num_bodies + Pm->feet_idx[f]) * 3;
+    return nrm3(c[0], c[1], c[2]);
+  }
+  return B.rew[se];
+}
+// Whether reported body b is one of the feet (the peak of columns 74 / 75 runs over the others).
+LGX_HD bool trace_is_foot(const lgx_task_params* Pm, int b) {
+  bool foot = false;
+  for (int f = 0; f < Pm->num_feet; ++f) foot = foot || Pm->feet_idx[f] == b;
+  return foot;
+}
+// Columns 74 / 75: fold the candidate (norm n of body b) into the running peak (pn, pb), which
+// starts at (0, -1). The larger norm wins, the lower body index wins a tie, a zero norm never wins:
+// associative and commutative, so the kernel's lane tree and the host's loop agree.
+LGX_HD void trace_peak_merge(float& pn, int& pb, float n, int b) {
+  if (n > pn || (n == pn && n > 0.f && b < pb)) {
+    pn = n;
+    pb = b;
+  }
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];

@@ -1191,6 +1191,62 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
   return 0;
 }
 
+void trace_begin(const lgx_task_params* P, const lgx_trace_buffers* T) {
+  const size_t N = (size_t)P->num_envs;
+  memset(T->ring, 0, sizeof(float) * LGX_TRACE_COLS * N * (size_t)T->depth);
+  memset(T->count, 0, sizeof(int32_t) * N);
+  memset(T->status, 0, N);
+}
+
+// lgx_trace_record (include/lgx.h): the kernel's arithmetic (lgx_env.hip trace_record_kernel), the
+// columns and the bodies in order
+void trace_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_trace_buffers* T) {
+  const int N = P->num_envs, NB = P->num_bodies, depth = T->depth;
+#pragma omp parallel for schedule(static)
+  for (int e = 0; e < N; ++e) {
+    if (T->status[e] != 0) continue;
+    if (B->reset[e]) {
+      T->status[e] = (B->blew_up && B->blew_up[e]) ? 3 : (B->time_out[e] ? 1 : 2);
+      continue;
+    }
+    const int cnt = T->count[e];
+    float* dst = T->ring + ((size_t)e * depth + (size_t)(cnt % depth)) * LGX_TRACE_COLS;
+    for (int col = 0; col < 74; ++col) dst[col] = trace_col(col, P, *B, e);
+    float pn = 0.f;
+    int pb = -1;
+    for (int b = 0; b < NB; ++b) {
+      if (trace_is_foot(P, b)) continue;
+      const float* c = B->contact_forces + ((size_t)e * NB + b) * 3;
+      trace_peak_merge(pn, pb, nrm3(c[0], c[1], c[2]), b);
+    }
+    dst[74] = pn;
+    dst[75] = (float)pb;
+    T->count[e] = cnt + 1;
+  }
+}
+
+void trace_gather(const lgx_task_params* P, const lgx_trace_buffers* T, const int32_t* ids, int32_t m, float* out,
+                  int32_t* out_len) {
+  const int N = P->num_envs, depth = T->depth;
+  const size_t per = (size_t)depth * LGX_TRACE_COLS;
+#pragma omp parallel for schedule(static)
+  for (int i = 0; i < m; ++i) {
+    float* o = out + (size_t)i * per;
+    memset(o, 0, sizeof(float) * per);
+    const int e = ids[i];
+    if (e < 0 || e >= N) {
+      out_len[i] = -1;
+      continue;
+    }
+    const int cn = T->count[e], L = std::max(0, std::min(cn, depth));
+    for (int j = 0; j < L; ++j)
+      memcpy(o + (size_t)(depth - L + j) * LGX_TRACE_COLS,
+             T->ring + ((size_t)e * depth + (size_t)((cn - L + j) % depth)) * LGX_TRACE_COLS,
+             sizeof(float) * LGX_TRACE_COLS);
+    out_len[i] = L;
+  }
+}
+
 int threads() { return omp_get_max_threads(); }
 
 }  // namespace lgxh

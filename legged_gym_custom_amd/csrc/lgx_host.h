@@ -31,6 +31,12 @@ void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_e
 // (or cell_ids entry) lies outside the cell grid; cells, push_cells and cmd_cells are written only
 // when it is 0 (overflow always is).
 int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E);
+// lgx_trace_begin / lgx_trace_record / lgx_trace_gather on host buffers (OpenMP over envs, over
+// the gathered ids): the flight recorder's rings, include/lgx.h ABI 11
+void trace_begin(const lgx_task_params* P, const lgx_trace_buffers* T);
+void trace_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_trace_buffers* T);
+void trace_gather(const lgx_task_params* P, const lgx_trace_buffers* T, const int32_t* ids, int32_t m, float* out,
+                  int32_t* out_len);
 // the worker threads the host backend uses (OpenMP)
 int threads();
 

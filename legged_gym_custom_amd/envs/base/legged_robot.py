@@ -247,6 +247,62 @@ class LeggedRobot(BaseTask):
                                    f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
         return self._eval_cells.cpu().clone()
 
+    # ------------------------------------------------------------------ flight recorder
+    def trace_buffers(self, depth):
+        """The flight recorder's tensors (include/lgx.h lgx_trace_buffers, ABI 11), allocated once
+        per depth so a captured loop replays on fixed addresses: trace_ring [N, depth, 76] (the last
+        `depth` control steps of each env's first episode since trace_begin; row i of an env lives in
+        slot i % depth), trace_count [N] int32 (rows written, may exceed depth) and trace_status [N]
+        (the eval_status rule). Each depth asked for keeps its tensors; the call makes that depth's
+        recorder the current one, which trace_begin / trace_record / trace_gather and the three
+        attributes refer to. Memory: the ring takes N x depth x 304 B, 124 MB at 4096 envs and
+        depth 100 (2 s of go2)."""
+        depth = int(depth)
+        if depth < 1:
+            raise ValueError(f"trace depth must be >= 1 (got {depth})")
+        if not hasattr(self, "_traces"):
+            self._traces = {}  # depth -> lgx_trace_buffers: a loop captured at a depth keeps its rings
+        if depth not in self._traces:
+            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
+            self._traces[depth] = self._native.trace_buffers(
+                z(self.num_envs, depth, _abi.TRACE_COLS, dtype=torch.float32), z(self.num_envs, dtype=torch.int32),
+                z(self.num_envs, dtype=torch.uint8))
+        self._trace = self._traces[depth]  # the current recorder: trace_begin / _record / _gather use it
+        self.trace_ring, self.trace_count, self.trace_status = self._trace._keep
+        return self._trace
+
+    def _trace_buffers(self):
+        if getattr(self, "_trace", None) is None:
+            raise RuntimeError("no flight recorder: call trace_buffers(depth) first")
+        return self._trace
+
+    def trace_begin(self):
+        """lgx_trace_begin: empty the rings and record every env's next (first) episode."""
+        self._native.trace_begin(self._trace_buffers(), self._stream())
+
+    def trace_record(self):
+        """lgx_trace_record for the step just run (call after every step(); stream-ordered, no host
+        sync, capturable)."""
+        self._native.trace_record(self._trace_buffers(), self._stream())
+
+    def trace_gather(self, ids):
+        """lgx_trace_gather: the unrolled traces of the envs `ids` (a list or an integer tensor;
+        duplicates allowed), oldest row first and newest last, zero rows in front of a trace shorter
+        than the depth. Returns (out [m, depth, 76] fp32, out_len [m] int32) in the env's memory
+        space: only the selection is unrolled. ValueError: an id outside [0, num_envs)."""
+        tb = self._trace_buffers()
+        ids = torch.as_tensor(ids).reshape(-1)
+        if ids.numel() and (ids.dtype.is_floating_point or ids.dtype == torch.bool):
+            raise ValueError(f"trace_gather: env ids must be integers (got {ids.dtype})")
+        bad = ids[(ids < 0) | (ids >= self.num_envs)]
+        if bad.numel():
+            raise ValueError(f"trace_gather: env id {int(bad[0])} is outside [0, {self.num_envs})")
+        ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        out = torch.empty(ids.shape[0], tb.depth, _abi.TRACE_COLS, device=self.device, dtype=torch.float32)
+        out_len = torch.empty(ids.shape[0], device=self.device, dtype=torch.int32)
+        self._native.trace_gather(tb, ids, out, out_len, self._stream())
+        return out, out_len
+
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""
         return torch.cuda.current_stream(self.device).cuda_stream if self.sim_device_id >= 0 else 0

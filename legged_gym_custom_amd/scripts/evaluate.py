@@ -9,6 +9,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
+         [--trace_falls M [--trace_s 2.0]]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
 history the largest one needs); several values give one report each under "sweep", on one captured
@@ -25,6 +26,13 @@ scheduled push is the only disturbance.
 --cmd_at_s seconds into its episode to one command of the --cmd_vx x --cmd_vy x --cmd_yaw grid (m/s, m/s, rad/s;
 literal commands, the yaw entry is a yaw rate) and is recorded from the switch on: settle times, peak tilt,
 achieved velocities and gain per bin. The config's random pushes are switched off for this mode; not with --push_vel.
+
+--trace_falls M: the flight recorder (PolicyEvaluator.traces), valid in every mode: the last --trace_s seconds
+of every env's episode are kept in a ring buffer on the device (depth = round(trace_s / dt) steps, clipped to
+[1, max_episode_length]; the rings take num_envs x depth x 304 B), and the traces of the M shortest falls are
+written to <the JSON's name without .json>_traces.npz (trace [M, depth, 76], length, env_id, status,
+terrain_level, terrain_type, columns, dt); the JSON gains "traces": {"file", "envs", "depth"}. With a latency
+sweep the traces are those of its last entry.
 
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
@@ -49,7 +57,7 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
-             cmd_start=None):
+             cmd_start=None, trace_falls=None, trace_s=2.0):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -78,23 +86,35 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
     checkpoint = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
     ev = PolicyEvaluator(env, runner, policy=policy)
     head = dict(task=args.task, checkpoint=checkpoint, iteration=int(runner.current_learning_iteration))
+    depth = None
+    if trace_falls is not None:
+        if int(trace_falls) < 1 or not float(trace_s) > 0.0:
+            raise ValueError(f"--trace_falls needs M >= 1 and --trace_s > 0 (got {trace_falls}, {trace_s})")
+        depth = min(max(int(round(float(trace_s) / float(env.dt))), 1), int(env.max_episode_length))
     if push_vel:
         report = dict(**head, **ev.run_push_test(push_vel, directions=push_dirs, at_s=push_at_s, num_steps=eval_steps,
-                                                 graph=graph))
+                                                 graph=graph, trace_depth=depth))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_push.json")
     elif cmd_vx:
         report = dict(**head, **ev.run_command_test(cmd_vx, vy=cmd_vy or (0.0,), yaw=cmd_yaw or (0.0,), at_s=cmd_at_s,
                                                     start=cmd_start or (0.0, 0.0, 0.0), num_steps=eval_steps,
-                                                    graph=graph))
+                                                    graph=graph, trace_depth=depth))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_command.json")
     elif len(delays_s) > 1:
-        sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength)
+        sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
+                                      trace_depth=depth)
         report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_latency.json")
     else:
         report = dict(**head, **ev.run(eval_steps, graph=graph, action_delay_s=delays_s[0] if delays_s else None,
-                                       motor_strength=motor_strength))
+                                       motor_strength=motor_strength, trace_depth=depth))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}.json")
+    if depth is not None:
+        import numpy as np
+        tr = ev.traces("falls", max_envs=int(trace_falls))
+        npz = out[:-len(".json")] + "_traces.npz"
+        np.savez(npz, **tr)
+        report["traces"] = {"file": npz, "envs": int(tr["env_id"].shape[0]), "depth": depth}
     with open(out, "w") as f:
         json.dump(report, f, indent=1)
     return report, out
@@ -115,13 +135,15 @@ def main(argv=None):
     p.add_argument("--cmd_yaw", type=floats, default=None)
     p.add_argument("--cmd_at_s", type=float, default=2.0)
     p.add_argument("--cmd_start", type=floats, default=None)
+    p.add_argument("--trace_falls", type=int, default=None)
+    p.add_argument("--trace_s", type=float, default=2.0)
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
     report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
                          action_delay_ms=own.action_delay_ms, motor_strength=own.motor_strength,
                          push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s,
                          cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
-                         cmd_start=own.cmd_start)
+                         cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s)
     print(json.dumps(report))
     return report
 

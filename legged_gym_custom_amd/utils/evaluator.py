@@ -29,17 +29,35 @@ episode step, to the command of its bin of a commanded vx x vy x yaw-rate grid t
 kernel's command schedule (lgx_buffers.cmd_step / cmd_val, ABI 10), and a per-env step-response
 record (cmd_rec) is reduced per bin: one run gives the tracking envelope and the step response.
 
+Flight recorder (trace_depth= of the three runs, then traces()): a ring buffer on the device for every
+env holds the last trace_depth control steps of the env's recorded episode (lgx_trace_record after
+each step, include/lgx.h ABI 11: state, commands, joints, torques, actions, foot forces, reward and
+the hardest-hit other body, TRACE_COLUMNS) and freezes when the episode ends; afterwards only the
+chosen envs' traces (the falls, say) are unrolled on the device and copied to the host. Memory: the
+ring takes num_envs x trace_depth x 304 B, 124 MB at 4096 envs and 100 steps.
+
 Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
 import time
 
+import numpy as np
 import torch
 
 from legged_gym_custom_amd import _abi
 
 REPORT_KEYS = ("episodes", "running", "survival_rate", "fall_rate", "blowups", "mean_episode_s", "rms_lin_vel_err",
                "rms_yaw_err", "mean_forward_speed", "cost_of_transport", "mean_peak_foot_force")
+
+# the 76 columns of a flight-recorder row (include/lgx.h lgx_trace_record)
+TRACE_COLUMNS = tuple(
+    ["episode_length", "pos_x", "pos_y", "pos_z", "quat_x", "quat_y", "quat_z", "quat_w"]
+    + [f"{k}_{a}" for k in ("base_lin_vel", "base_ang_vel", "projected_gravity") for a in "xyz"]
+    + ["command_vx", "command_vy", "command_yaw", "command_heading"]
+    + [f"{k}_{j}" for k in ("dof_pos", "dof_vel", "torque", "action") for j in range(_abi.MAX_DOF)]
+    + [f"foot_force_{f}" for f in range(_abi.MAX_FEET)]
+    + ["reward", "peak_body_force", "peak_body_index"])
+assert len(TRACE_COLUMNS) == _abi.TRACE_COLS
 
 
 def cell_report(cell, dt, weight):
@@ -97,13 +115,15 @@ class PolicyEvaluator:
         if torch.device(self.device) != torch.device(env.device):
             raise RuntimeError(f"the evaluator runs the policy on the env's device ({env.device}), not {self.device}")
         self.on_gpu = self.device.startswith("cuda")
-        self._graph = None
+        self._graph = self._graph_key = None            # run's captured loop (key: the trace depth)
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
         self._fused = None
         self.last_cells = None
         self.last_push_cells = self.last_push_bins = None
         self.last_cmd_cells = self.last_cmd_bins = None
+        self._trace_depth = None     # the flight recorder's depth in the run under way (None: off)
+        self.last_trace_depth = None  # the depth of the last finished run, None when it was not traced
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -139,10 +159,12 @@ class PolicyEvaluator:
 
     def step(self, ev=None):
         """One eager iteration: act, env.step, eval_accumulate (ev: the eval buffers to record
-        into; default: the plain evaluation's)."""
+        into; default: the plain evaluation's), and trace_record in a traced run."""
         with torch.no_grad():
             self.env.step(self.act())
             self.env.eval_accumulate(ev)
+            if self._trace_depth is not None:
+                self.env.trace_record()
 
     def begin(self, ev=None):
         """Reset every env and start recording. The env's step and reset-call counters (the keys
@@ -158,6 +180,16 @@ class PolicyEvaluator:
             env.reset()
             env.episode_length_buf = torch.zeros_like(env.episode_length_buf)
             env.eval_begin(ev)
+            if self._trace_depth is not None:
+                env.trace_begin()
+
+    def _set_trace(self, trace_depth):
+        """Start a run: the flight recorder's depth for it (None: off; else the env's rings of that
+        depth, allocated once per depth)."""
+        self.last_trace_depth = None
+        self._trace_depth = None if trace_depth is None else int(trace_depth)
+        if self._trace_depth is not None:
+            self.env.trace_buffers(self._trace_depth)
 
     def _capture(self, ev=None):
         """The loop body as one hipGraph (the runner's _capture_rollout is the model): one eager
@@ -172,11 +204,13 @@ class PolicyEvaluator:
                 torch.cuda.graph(g, capture_error_mode=self.alg.capture_mode()):
             env.step(self.act())
             env.eval_accumulate(ev)
+            if self._trace_depth is not None:
+                env.trace_record()
         env.common_step_counter = csc  # host mirror (capture advanced it, the device did not)
         return g
 
     # ------------------------------------------------------------------ run
-    def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None):
+    def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None, trace_depth=None):
         """Evaluate: reset, num_steps x {act, step, accumulate}, reduce, one host read; returns the
         report (JSON-serialisable): per-cell and total entries REPORT_KEYS, None where a cell has
         no data (never NaN).
@@ -193,8 +227,13 @@ class PolicyEvaluator:
         episode_length > max_episode_length (lgx_env.hip env_step_kernel, go2.py:186-204), the
         length counting from 0, so by then every env has finished once and `running` is 0.
         graph: replay the captured loop body where the env allows it (GPU, env.graph_capturable);
-        False forces the eager loop. Both give bit-identical cells."""
+        False forces the eager loop. Both give bit-identical cells.
+        trace_depth: record the last trace_depth steps of every env's episode in the flight recorder
+        (the loop body gains lgx_trace_record, in a captured loop of its own per depth; the cells are
+        bit-identical to an untraced run's); read them with traces(). None: no recorder, the loop
+        and its graph are the untraced ones."""
         env = self.env
+        self._set_trace(trace_depth)
         saved = []  # (buffer, its values before this run)
         try:
             if action_delay_s is not None:
@@ -217,12 +256,13 @@ class PolicyEvaluator:
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
-        if use_graph and self._graph is None:
-            self._graph = self._capture()
+        if use_graph and (self._graph is None or self._graph_key != self._trace_depth):
+            self._graph, self._graph_key = self._capture(), self._trace_depth
         self.begin()
         t0 = self._loop(steps, self._graph if use_graph else None, None)
         cells = env.eval_cells()  # reduce + the host read (synchronises)
         wall = time.perf_counter() - t0
+        self.last_trace_depth = self._trace_depth
         self.last_cells = cells  # [rows, cols, 12] float64, as lgx_eval_reduce wrote them
         return self.report(cells, steps, wall, use_graph)
 
@@ -243,7 +283,8 @@ class PolicyEvaluator:
         return t0
 
     # ------------------------------------------------------------------ push recovery
-    def run_push_test(self, speeds, directions=8, at_s=2.0, settle_tol=0.3, num_steps=None, graph=True):
+    def run_push_test(self, speeds, directions=8, at_s=2.0, settle_tol=0.3, num_steps=None, graph=True,
+                      trace_depth=None):
         """How hard a shove does the policy survive, from which side, and how quickly does it
         settle: one run in which every env is pushed once, at episode step round(at_s / dt), by a
         velocity impulse of its bin (speed index s, direction index d): dvel = speeds[s] *
@@ -258,6 +299,8 @@ class PolicyEvaluator:
         steps is captured (domain_rand.scheduled_pushes = True, or call this before run()).
         The schedule is cleared in place when the run ends, so a following run() is the plain one.
 
+        trace_depth: the flight recorder, as in run().
+
         Returns the report: "bins"[s][d] with the REPORT_KEYS entries and pushed (finished envs
         with post-push samples), mean_peak_tilt_rad, mean_peak_lin_vel_err (m/s), survivors (timed
         out among them) and mean_settle_s (the survivors' mean time from the push to the last step
@@ -266,6 +309,7 @@ class PolicyEvaluator:
         ValueError: no speeds or directions, a negative or non-finite speed, a push step outside
         0 < step < max_episode_length."""
         env = self.env
+        self._set_trace(trace_depth)
         speeds = [float(v) for v in speeds]
         S, D = len(speeds), int(directions)
         if S < 1 or D < 1 or not all(math.isfinite(v) and v >= 0.0 for v in speeds):
@@ -285,12 +329,13 @@ class PolicyEvaluator:
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         key = (S, D, float(settle_tol))
+        gkey = key + (self._trace_depth,)
         try:
             env.set_push_schedule(0, dvel)  # (the first one allocates: refused once a loop is captured)
             ev = env.push_eval_buffers(*key)
             env.push_cell_ids.copy_(bins.to(torch.int32))
-            if use_graph and (self._push_graph is None or self._push_graph_key != key):
-                self._push_graph, self._push_graph_key = self._capture(ev), key
+            if use_graph and (self._push_graph is None or self._push_graph_key != gkey):
+                self._push_graph, self._push_graph_key = self._capture(ev), gkey
             self.begin(ev)
             env.set_push_schedule(step, dvel)  # after begin: its reset ends with an env step of its own
             t0 = self._loop(steps, self._push_graph if use_graph else None, ev)
@@ -299,6 +344,7 @@ class PolicyEvaluator:
         finally:
             env.clear_push_schedule()
         self.last_cells, self.last_push_cells, self.last_push_bins = cells, pcells, bins
+        self.last_trace_depth = self._trace_depth
         dt, w = float(env.dt), self.mass * self.gravity
         both = lambda c, p: {**cell_report(c, dt, w), **push_cell_report(p, dt)}  # noqa: E731
         return {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
@@ -310,7 +356,7 @@ class PolicyEvaluator:
 
     # ------------------------------------------------------------------ command response
     def run_command_test(self, vx, vy=(0.0,), yaw=(0.0,), at_s=2.0, start=(0.0, 0.0, 0.0), steady_after_s=1.0,
-                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True):
+                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None):
         """What does the robot do when commanded, how fast does it get there, and does it stay up:
         one run in which every env holds the command `start` = (vx, vy, yaw rate), switches at
         episode step round(at_s / dt) to the command of its bin (vx[ix], vy[iy], yaw[iw]) and is
@@ -326,6 +372,8 @@ class PolicyEvaluator:
         before the run's reset and cleared in place when the run ends, so a following run() is the
         plain one.
 
+        trace_depth: the flight recorder, as in run().
+
         Returns the report: "bins"[ix][iy][iw] with the REPORT_KEYS entries and switched (finished
         envs with post-switch samples), survivors (timed out among them), mean_settle_s /
         mean_yaw_settle_s (the survivors' mean time from the switch until the linear velocity / yaw
@@ -337,6 +385,7 @@ class PolicyEvaluator:
         ValueError: an empty list, a non-finite entry, a switch step outside 0 < step <
         max_episode_length, a negative or non-finite tolerance or steady_after_s."""
         env = self.env
+        self._set_trace(trace_depth)
         vx, vy, yaw, start = ([float(v) for v in lst] for lst in (vx, vy, yaw, start))
         if min(len(vx), len(vy), len(yaw)) < 1 or len(start) != 3 or \
                 not all(math.isfinite(v) for v in vx + vy + yaw + start):
@@ -358,14 +407,15 @@ class PolicyEvaluator:
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         key = (nx, ny * nw, float(settle_tol), float(yaw_tol), steady)
+        gkey = key + (self._trace_depth,)
         try:
             # before begin: its reset sees segment 0 (the first call allocates: refused once a loop is captured)
             env.set_command_schedule([0, step], values)
             ev = env.cmd_eval_buffers(*key)
             env.cmd_cell_ids.copy_(bins.to(torch.int32))
             env.cmd_switch_step.fill_(step)
-            if use_graph and (self._cmd_graph is None or self._cmd_graph_key != key):
-                self._cmd_graph, self._cmd_graph_key = self._capture(ev), key
+            if use_graph and (self._cmd_graph is None or self._cmd_graph_key != gkey):
+                self._cmd_graph, self._cmd_graph_key = self._capture(ev), gkey
             self.begin(ev)
             t0 = self._loop(steps, self._cmd_graph if use_graph else None, ev)
             cells, ccells = env.eval_command_cells()  # reduce + the host read (synchronises)
@@ -373,6 +423,7 @@ class PolicyEvaluator:
         finally:
             env.clear_command_schedule()
         self.last_cells, self.last_cmd_cells, self.last_cmd_bins = cells, ccells, bins
+        self.last_trace_depth = self._trace_depth
         w = self.mass * self.gravity
         both = lambda c, p, cmd: {**cell_report(c, dt, w), **command_cell_report(p, dt, cmd)}  # noqa: E731
         total = both(cells.reshape(-1, cells.shape[2]).sum(0), ccells.reshape(-1, ccells.shape[2]).sum(0), (0.0, 0.0, 0.0))
@@ -384,6 +435,39 @@ class PolicyEvaluator:
                 "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
                            for iw in range(nw)] for iy in range(ny)] for ix in range(nx)],
                 "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
+
+    # ------------------------------------------------------------------ flight recorder
+    def traces(self, which="falls", max_envs=16):
+        """The recorded traces of chosen envs of the last run (it must have been traced: trace_depth).
+        which: "falls" = the envs whose recorded episode ended in a fall or a blow-up (status 2 or
+        3), the shortest recorded episode first, ties by env id, the first max_envs of them; or a
+        sequence of env ids (max_envs is then ignored). The selection is made and the traces are
+        unrolled on the device (lgx_trace_gather); only the selection crosses to the host.
+
+        Returns a dict of numpy arrays: trace [M, K, 76] (oldest row first, newest last, zero rows in
+        front of an episode shorter than K), length [M] (rows of trace that hold data), env_id [M],
+        status [M] (0 still recording, 1 timed out, 2 fell, 3 blew up), terrain_level / terrain_type
+        [M] (-1 without a terrain grid), columns (TRACE_COLUMNS) and dt (seconds per row)."""
+        env = self.env
+        if self.last_trace_depth is None:
+            raise RuntimeError("traces(): the last run was not traced (pass trace_depth= to run, run_push_test or "
+                               "run_command_test first)")
+        if isinstance(which, str):
+            if which != "falls":
+                raise ValueError(f"traces(): which must be 'falls' or a sequence of env ids (got {which!r})")
+            ids = (env.trace_status >= 2).nonzero().reshape(-1)  # (ascending: the stable sort keeps ties by id)
+            ids = ids[torch.sort(env.trace_count[ids], stable=True).indices][:max(int(max_envs), 0)]
+        else:
+            ids = torch.as_tensor(which).reshape(-1)
+        out, out_len = env.trace_gather(ids)
+        ids = ids.to(env.device).long()
+        grid = getattr(env, "terrain_levels", None) is not None
+        none = torch.full_like(ids, -1)
+        host = lambda t: t.cpu().numpy()  # noqa: E731
+        return {"trace": host(out), "length": host(out_len), "env_id": host(ids), "status": host(env.trace_status[ids]),
+                "terrain_level": host(env.terrain_levels[ids] if grid else none),
+                "terrain_type": host(env.terrain_types[ids] if grid else none),
+                "columns": np.array(TRACE_COLUMNS), "dt": np.float64(env.dt)}
 
     def sweep_action_delay(self, delays_s, **run_kwargs):
         """One report per actuation latency (seconds) of delays_s, each a full run() with that

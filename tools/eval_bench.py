@@ -3,6 +3,7 @@ networks (the timing does not depend on the weights), graph replay and the eager
 
   python tools/eval_bench.py [--task go2] [--num_envs 4096] [--steps N] [--repeats 3] [--out FILE]
   python tools/eval_bench.py --push_vel 0,0.5,1.0,1.5 [--push_dirs 8] ...   # + the push test (run_push_test)
+  python tools/eval_bench.py --trace_depth 100 ...   # + the plain run with the flight recorder on, and traces()
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/eval_bench.py --profile
   python tools/eval_bench.py --stats DIR/..._kernel_stats.csv --merge FILE   # kernel times into FILE
 
@@ -18,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 KERNELS = {"eval_accumulate_kernel": "eval_accumulate_us", "eval_reduce_kernel": "eval_reduce_us",
-           "env_step_kernel": "env_step_us", "act_kernel(lgx_s8_act_args": "act_us"}
+           "env_step_kernel": "env_step_us", "act_kernel(lgx_s8_act_args": "act_us",
+           "trace_record_kernel": "trace_record_us", "trace_gather_kernel": "trace_gather_us"}
 
 
 def merge_stats(stats_csv, out):
@@ -49,6 +51,8 @@ def main():
                         "scheduled_commands; not with --push_vel)")
     p.add_argument("--cmd_vy", type=lambda s: [float(v) for v in s.split(",")], default=[0.0])
     p.add_argument("--cmd_yaw", type=lambda s: [float(v) for v in s.split(",")], default=[0.0])
+    p.add_argument("--trace_depth", type=int, default=None,
+                   help="also time run(trace_depth=K), the flight recorder, and traces('falls', 16) after it")
     p.add_argument("--profile", action="store_true")
     p.add_argument("--stats")
     p.add_argument("--merge")
@@ -75,7 +79,9 @@ def main():
     runner, _ = task_registry.make_alg_runner(env, args=args, train_cfg=tcfg, log_root=None)
     ev = PolicyEvaluator(env, runner)
     if a.profile:
-        r = ev.run(a.steps or 200, graph=False)
+        r = ev.run(a.steps or 200, graph=False, trace_depth=a.trace_depth)
+        if a.trace_depth:
+            ev.traces("falls", 16)
         print(json.dumps({"profiled_steps": r["num_steps"], "total": r["total"]}))
         return
     ev.run(20)  # warm both paths (the capture included)
@@ -91,18 +97,39 @@ def main():
         rates.update(cmd_graph=[], cmd_eager=[])
         cmd(20, True)
         cmd(20, False)
+    traced = (lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
+    if a.trace_depth:
+        rates.update(trace_graph=[], trace_eager=[])
+        traced(20, True)
+        traced(20, False)
     for _ in range(a.repeats):
         for mode in rates:
             graph = mode.endswith("graph")
-            r = (push if mode.startswith("push") else cmd if mode.startswith("cmd") else ev.run)(a.steps, graph)
+            r = (push if mode.startswith("push") else cmd if mode.startswith("cmd") else
+                 traced if mode.startswith("trace") else ev.run)(a.steps, graph)
             assert a.device == "cpu" or r["graph"] == graph
             rates[mode].append(r["env_steps_per_s"])
+    trace_doc = None
+    if a.trace_depth:  # (the last timed run was the traced eager one)
+        import time
+        t0 = time.perf_counter()
+        tr = ev.traces("falls", 16)  # ends in host copies: synchronises
+        n, k = a.num_envs, a.trace_depth
+        trace_doc = {"depth": k, "ring_bytes": n * k * 304, "traces_s": time.perf_counter() - t0,
+                     "envs": int(tr["env_id"].shape[0]), "lengths": tr["length"].tolist(),
+                     # what lgx_trace_record moves per step when every env records: the source rows
+                     # (int64 length, 7 + 3 + 3 + 3 + 4 + 24 + 12 + 12 + 1 floats, all contact forces,
+                     # count / status / reset flags) in, one 304-byte row and the count out
+                     "record_bytes_in_per_step": n * (8 + 69 * 4 + env.num_bodies * 12 + 4 + 1 + 1),
+                     "record_bytes_out_per_step": n * (304 + 4)}
     pr, cr = r if a.push_vel else None, r if a.cmd_vx else None
-    r = ev.run(a.steps) if pr or cr else r
+    r = ev.run(a.steps) if pr or cr or a.trace_depth else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
                                for m, v in rates.items()},
            "total": r["total"]}
+    if trace_doc:
+        doc["flight_recorder"] = trace_doc
     if pr:
         doc["push_test"] = {k: pr[k] for k in ("speeds", "directions_deg", "push_step", "settle_tol", "total")}
         doc["push_test"]["per_speed"] = [
