@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 11
+#define LGX_ABI_VERSION 12
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -54,6 +54,9 @@ extern "C" {
 #define LGX_EVAL_CMD_REC 8        /* per-env step-response record columns (lgx_eval_buffers.cmd_rec) */
 #define LGX_EVAL_CMD_COLS 9       /* per-cell step-response columns (lgx_eval_buffers.cmd_cells) */
 #define LGX_TRACE_COLS 76         /* columns of a flight-recorder row (lgx_trace_buffers.ring) */
+#define LGX_GAIT_FOOT_COLS 16     /* per-env per-foot gait record columns (lgx_gait_buffers.foot) */
+#define LGX_GAIT_BODY_COLS 12     /* per-env gait record columns (lgx_gait_buffers.body) */
+#define LGX_GAIT_CELL_COLS 61     /* per-cell gait columns: 1 + 12 + LGX_MAX_FEET * 12 (lgx_gait_buffers.cells) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -573,6 +576,79 @@ int lgx_trace_record(lgx_env* env, const lgx_trace_buffers* tb, void* hip_stream
  * rows are zero and its out_len is -1. out: [m, depth, LGX_TRACE_COLS], out_len: [m]. */
 int lgx_trace_gather(lgx_env* env, const lgx_trace_buffers* tb, const int32_t* ids, int32_t m, float* out,
                      int32_t* out_len, void* hip_stream);
+/* ABI 12. Gait record: a small state machine per foot that runs after every step and says how the
+ * robot walks (stance and swing times, stride frequency, foot clearance, slip, touchdown force, which
+ * feet move together), per env for the env's FIRST episode since lgx_gait_begin (the rule of
+ * lgx_eval_buffers.status), then reduced per cell. Stand-alone like the flight recorder: buffers and a
+ * status array of its own, one launch per step; lgx_eval_buffers and the step are untouched. The
+ * reference has no counterpart. Buffers are the caller's, in the env's memory space (device, or host
+ * for device < 0). */
+typedef struct lgx_gait_buffers {
+  float* foot;       /* [N, LGX_MAX_FEET, LGX_GAIT_FOOT_COLS] per-env per-foot record, columns below */
+  float* body;       /* [N, LGX_GAIT_BODY_COLS] per-env record */
+  uint8_t* status;   /* [N] 0 recording, 1 timed out, 2 fell, 3 blew up: the lgx_eval_buffers.status rule */
+  double* cells;     /* [cell_rows*cell_cols, LGX_GAIT_CELL_COLS], written by lgx_gait_reduce */
+  uint32_t* overflow;/* [1] written by lgx_gait_reduce, as lgx_eval_buffers.overflow */
+  int32_t cell_rows, cell_cols;
+  const int32_t* cell_ids; /* [N] optional: the same meaning and range rule as lgx_eval_buffers.cell_ids */
+} lgx_gait_buffers;
+int64_t lgx_sizeof_gait_buffers(void);
+/* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph. Each
+ * refuses (naming the culprit) a NULL foot, body, status or overflow (lgx_gait_reduce: also cells), a
+ * foot that is not 16-byte aligned (the kernel moves a foot's record as four 16-byte accesses),
+ * cell_rows or cell_cols < 1, an unbound contact_forces, rigid_body_states, reset or time_out, and a
+ * feet_idx outside the bodies; blew_up, terrain_levels and terrain_types are optional.
+ * lgx_gait_begin: zero foot, body, status and overflow. */
+int lgx_gait_begin(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream);
+/* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
+ * status[e] == 0:
+ *   reset[e]: status[e] = 3 if blew_up is bound and set, else 1 if time_out[e], else 2; no sample.
+ *   else one sample. For foot f < num_feet, with b = feet_idx[f], F = contact_forces[e][b],
+ *   R = rigid_body_states[e][b], dt = params.dt, in fp32 without contraction:
+ *     c = F.z > 1.0f (the step's own contact rule, unfiltered), z = R[2], vh = sqrtf(R[7]^2 + R[8]^2),
+ *     fh = sqrtf(F.x^2 + F.y^2), fn = sqrtf(F.x^2 + F.y^2 + F.z^2),
+ *   r = foot[e][f] and first = (body[e][0] == 0), read before anything is written. Foot columns:
+ *     0   contact state of the last sample (0/1)                                       state
+ *     1   steps in the current phase (stance or swing), counting the transition sample; 0: the
+ *         start of this phase was not observed (the episode's first phase)             state
+ *     2   z at the last stance sample                                                  state
+ *     3   max z in the current swing                                                   state
+ *     4   stance samples            5   touchdowns
+ *     6, 7   completed stances: count, sum of steps
+ *     8, 9   completed swings: count, sum of steps
+ *     10  sum over completed swings of (col 3 - col 2): clearance over the lift-off height
+ *     11  sum of vh*dt over stance samples (slip distance)
+ *     12  sum of F.z over stance samples
+ *     13  max fn over touchdown samples
+ *     14  sum of vh*dt over swing samples (swing path)
+ *     15  samples with fh > 5*|F.z| (legged_gym's feet_stumble rule, independent of c)
+ *   Order within a sample:
+ *     1. first: r[0] = c; r[1] = 0.
+ *     2. else, with p = r[0]:
+ *          touchdown (c && !p): r[5] += 1; r[13] = max(r[13], fn);
+ *                               if (r[1] > 0) { r[8] += 1; r[9] += r[1]; r[10] += r[3] - r[2]; }  r[1] = 1
+ *          lift-off (!c && p):  if (r[1] > 0) { r[6] += 1; r[7] += r[1]; }  r[1] = 1; r[3] = z
+ *          no transition:       r[1] = r[1] > 0 ? r[1] + 1 : 0
+ *          then r[0] = c.
+ *     3. every sample, the first included:
+ *          c:    r[4] += 1; r[11] += vh*dt; r[12] += F.z; r[2] = z
+ *          else: r[3] = first ? z : max(r[3], z); r[14] += vh*dt
+ *          if (fh > 5*fabsf(F.z)) r[15] += 1
+ *   A swing (a stance) counts as completed only when both its ends were observed: the swing a fall
+ *   interrupts is never counted. Foot slots f >= num_feet stay zero.
+ *   Body columns, m = the number of feet in contact: body[0] += 1 (samples); body[1 + m] += 1
+ *   (histogram, m = 0..4); body[6 + i] += (c_a == c_b) for the foot pairs (0,1), (0,2), (0,3), (1,2),
+ *   (1,3), (2,3) in this order, a pair with a foot >= num_feet not counted.
+ * Envs with status != 0 are never written again. */
+int lgx_gait_record(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream);
+/* cells[cell], over the cell's finished envs (status != 0) with body[0] > 0, the cell being
+ * cell_ids[e] if set, else terrain_levels[e] * cell_cols + terrain_types[e] (cell 0 for an unbound
+ * one): [0] = the number of such envs, [1..12] = sums of body[0..11], [13 + 12 f + k] = sums of foot
+ * f's columns 4 + k, k = 0..11 (the entry of column 13 is therefore a sum of per-env peaks). fp64,
+ * the fixed tree of lgx_eval_reduce, no floating-point atomics: two calls on the same records give
+ * bit-identical cells. A cell outside the grid is never used as an index: such envs are counted in
+ * *overflow, and cells are then left unwritten (the host backend fails the call instead). */
+int lgx_gait_reduce(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream);
 const char* lgx_last_error(const lgx_env* env);
 void lgx_destroy(lgx_env* env);
 

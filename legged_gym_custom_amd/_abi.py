@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -28,6 +28,9 @@ CMD_SEGMENTS = 4     # segments of an env's command schedule (lgx_buffers.cmd_st
 EVAL_CMD_REC = 8     # per-env step-response record columns (lgx_eval_buffers.cmd_rec)
 EVAL_CMD_COLS = 9    # per-cell step-response columns (lgx_eval_buffers.cmd_cells)
 TRACE_COLS = 76      # columns of a flight-recorder row (lgx_trace_buffers.ring)
+GAIT_FOOT_COLS = 16  # per-env per-foot gait record columns (lgx_gait_buffers.foot)
+GAIT_BODY_COLS = 12  # per-env gait record columns (lgx_gait_buffers.body)
+GAIT_CELL_COLS = 61  # per-cell gait columns: 1 + 12 + MAX_FEET * 12 (lgx_gait_buffers.cells)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -162,8 +165,14 @@ class TraceBuffers(C.Structure):
     _fields_ = [("ring", P), ("count", P), ("status", P), ("depth", i32)]
 
 
+class GaitBuffers(C.Structure):
+    """lgx_gait_buffers (ABI 12): the gait record's per-env per-foot records and per-cell sums."""
+    _fields_ = [("foot", P), ("body", P), ("status", P), ("cells", P), ("overflow", P), ("cell_rows", i32),
+                ("cell_cols", i32), ("cell_ids", P)]
+
+
 STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buffers,
-           "lgx_eval_buffers": EvalBuffers, "lgx_trace_buffers": TraceBuffers}
+           "lgx_eval_buffers": EvalBuffers, "lgx_trace_buffers": TraceBuffers, "lgx_gait_buffers": GaitBuffers}
 SIZEOF = {"lgx_sizeof_" + name[len("lgx_"):]: name for name in STRUCTS}  # sizeof export -> typedef
 
 CONSTANTS = {
@@ -176,6 +185,7 @@ CONSTANTS = {
     "LGX_EVAL_PUSH_REC": EVAL_PUSH_REC, "LGX_EVAL_PUSH_COLS": EVAL_PUSH_COLS,
     "LGX_CMD_SEGMENTS": CMD_SEGMENTS, "LGX_EVAL_CMD_REC": EVAL_CMD_REC, "LGX_EVAL_CMD_COLS": EVAL_CMD_COLS,
     "LGX_TRACE_COLS": TRACE_COLS,
+    "LGX_GAIT_FOOT_COLS": GAIT_FOOT_COLS, "LGX_GAIT_BODY_COLS": GAIT_BODY_COLS, "LGX_GAIT_CELL_COLS": GAIT_CELL_COLS,
     "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
     "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
     **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},
@@ -203,6 +213,9 @@ SIGNATURES = {
     "lgx_trace_begin": (cint, (P, P, P)),
     "lgx_trace_record": (cint, (P, P, P)),
     "lgx_trace_gather": (cint, (P, P, P, i32, P, P, P)),
+    "lgx_gait_begin": (cint, (P, P, P)),
+    "lgx_gait_record": (cint, (P, P, P)),
+    "lgx_gait_reduce": (cint, (P, P, P)),
     "lgx_last_error": (C.c_char_p, (P,)),
     "lgx_destroy": (None, (P,)),
 }

@@ -203,6 +203,45 @@ class NativeEnv:
                                              C.c_void_p(out.data_ptr()), C.c_void_p(out_len.data_ptr()),
                                              C.c_void_p(stream)), "lgx_trace_gather")
 
+    def gait_buffers(self, foot, body, status, cells, overflow, cell_ids=None):
+        """lgx_gait_buffers (ABI 12) over the given tensors: foot [N, 4, 16] fp32, body [N, 12] fp32,
+        status [N] uint8, cells [rows, cols, 61] float64, overflow [1] int32 and, optional, cell_ids
+        [N] int32 (the free cell key), all in the env's memory space."""
+        n = self.params.num_envs
+        if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.GAIT_CELL_COLS):
+            raise LgxError(f"gait buffer cells must be [rows, cols, {_abi.GAIT_CELL_COLS}]")
+        want = {"foot": ((n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS), "float32"),
+                "body": ((n, _abi.GAIT_BODY_COLS), "float32"), "status": ((n,), "uint8"),
+                "cells": (None, "float64"), "overflow": ((1,), "int32"), "cell_ids": ((n,), "int32")}
+        gb = _abi.GaitBuffers()
+        for name, t in (("foot", foot), ("body", body), ("status", status), ("cells", cells), ("overflow", overflow),
+                        ("cell_ids", cell_ids)):
+            if t is None:
+                if name == "cell_ids":
+                    continue  # (optional: the struct's member stays NULL)
+                raise LgxError(f"gait buffer {name} is required")
+            shape, dtype = want[name]
+            if (shape is not None and tuple(t.shape) != shape) or str(t.dtype) != "torch." + dtype \
+                    or not t.is_contiguous() or t.device.type != self._dev_type:
+                raise LgxError(f"gait buffer {name} must be a contiguous {dtype} tensor"
+                               f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
+            setattr(gb, name, t.data_ptr())
+        gb.cell_rows, gb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
+        gb._keep = (foot, body, status, cells, overflow, cell_ids)
+        return gb
+
+    def gait_begin(self, gb, stream):
+        """lgx_gait_begin: zero the records, the statuses and the overflow count (gb: gait_buffers(...))."""
+        self._check(self._L.lgx_gait_begin(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_begin")
+
+    def gait_record(self, gb, stream):
+        """lgx_gait_record: one sample per recording env from the step just run."""
+        self._check(self._L.lgx_gait_record(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_record")
+
+    def gait_reduce(self, gb, stream):
+        """lgx_gait_reduce: records -> cells (and the out-of-grid count in gb.overflow)."""
+        self._check(self._L.lgx_gait_reduce(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_reduce")
+
     def __del__(self):
         try:
             if self.handle:

@@ -2912,6 +2912,206 @@ int lgx_trace_gather(lgx_env* env, const lgx_trace_buffers* tb, const int32_t* i
   return 0;
 }
 
+// ------------------------------------------------------------------ gait record (ABI 12)
+namespace lgx {
+// lgx_gait_record: four lanes per env (16 envs per wave, a group never straddles a wave), lane q =
+// foot q. Each lane moves its foot's 16 record columns as four 16-byte accesses (64 contiguous
+// bytes per lane, 4 KB per wave without gaps), keeps them in registers across gait_foot_sample, and
+// reads its foot's contact force (12 B) and three floats of its rigid-body row. Two xor shuffles
+// exchange the four contact bits; lane q then updates body columns 3q..3q+2 (48 contiguous bytes
+// per env). status[e], reset[e] and body[e][0] (the "first sample" test) are read by every lane of
+// the group before the first store of the kernel, and only lane 0 writes status and body[0]: no
+// lane can see this launch's update. Per recording env: 256 + 48 B of records in and out, 4 x 24 B
+// of sources and two flags in, about 700 B (5.0 us at 4096 envs: launch and load latency, a
+// fourteenth of the HBM rate). No LDS, no atomics;
+// frozen envs store nothing, tail lanes load nothing.
+__global__ __launch_bounds__(256) void gait_record_kernel(const lgx_task_params* __restrict__ Pm,
+                                                          const lgx_buffers* __restrict__ Bd, float* foot,
+                                                          float* body, uint8_t* status) {
+  const lgx_buffers& B = *Bd;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 2, q = t & 3;
+  // no early return: the shuffles below need every lane of a group
+  const bool live = e < Pm->num_envs;
+  const int st = live ? status[e] : 1;
+  const int rs = live ? B.reset[e] : 0;
+  const bool sample = st == 0 && !rs;
+  const int nfeet = Pm->num_feet;
+  const bool mine = sample && q < nfeet;
+  float* bq = body + (size_t)e * LGX_GAIT_BODY_COLS + 3 * q;
+  float4* fq = reinterpret_cast<float4*>(foot + ((size_t)e * LGX_MAX_FEET + q) * LGX_GAIT_FOOT_COLS);
+  float r[LGX_GAIT_FOOT_COLS], F[3] = {0.f, 0.f, 0.f}, R[13], b0 = 0.f, b1 = 0.f, b2 = 0.f;
+  bool first = false;
+  if (sample) {
+    first = body[(size_t)e * LGX_GAIT_BODY_COLS] == 0.f;
+    b0 = bq[0];
+    b1 = bq[1];
+    b2 = bq[2];
+  }
+  if (mine) {
+    LGX_UNROLL
+    for (int i = 0; i < 4; ++i) {
+      const float4 v = fq[i];
+      r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+    }
+    const size_t row = (size_t)e * Pm->num_bodies + Pm->feet_idx[q];
+    const float* cf = B.contact_forces + row * 3;
+    const float* rb = B.rigid_body_states + row * 13;
+    F[0] = cf[0]; F[1] = cf[1]; F[2] = cf[2];
+    R[2] = rb[2]; R[7] = rb[7]; R[8] = rb[8];
+  }
+  int bits = (mine && gait_contact(F)) ? (1 << q) : 0;
+  bits |= __shfl_xor(bits, 1, 64);
+  bits |= __shfl_xor(bits, 2, 64);
+  if (!live || st != 0) return;
+  if (rs) {
+    if (q == 0) status[e] = (B.blew_up && B.blew_up[e]) ? 3 : (B.time_out[e] ? 1 : 2);
+    return;
+  }
+  if (mine) {
+    gait_foot_sample(r, first, F, R, Pm->dt);
+    LGX_UNROLL
+    for (int i = 0; i < 4; ++i) fq[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+  }
+  bq[0] = gait_body_col(3 * q, b0, bits, nfeet);
+  bq[1] = gait_body_col(3 * q + 1, b1, bits, nfeet);
+  bq[2] = gait_body_col(3 * q + 2, b2, bits, nfeet);
+}
+
+// lgx_gait_reduce: one block of 256 threads per cell, the shape and the tree of eval_reduce_kernel
+// (thread t scans envs t, t+256, ... in increasing order, fp64 partials, shuffle-down inside each
+// wave, the four wave results in wave order), in five passes so that a thread holds at most 13 fp64
+// partials: pass 0 the env count and the 12 body columns, pass 1 + f foot f's columns 4..15. Every
+// pass scans every env's cell id in the same order, so the result depends only on the records. The
+// out-of-grid count is formed in pass 0: no block writes its cell when there are any, and block 0
+// publishes the count.
+__global__ __launch_bounds__(256) void gait_reduce_kernel(const float* __restrict__ foot,
+                                                          const float* __restrict__ body,
+                                                          const uint8_t* __restrict__ status,
+                                                          const int64_t* __restrict__ levels,
+                                                          const int64_t* __restrict__ types,
+                                                          const int32_t* __restrict__ cell_ids, int N, int rows,
+                                                          int cols, double* __restrict__ cells,
+                                                          uint32_t* __restrict__ overflow) {
+  constexpr int NP = 1 + LGX_GAIT_BODY_COLS, NF = LGX_GAIT_FOOT_COLS - 4;
+  __shared__ double part[4][NP];
+  __shared__ uint32_t bad_s[4];
+  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  uint32_t nbad = 0;
+  for (int pass = 0; pass < 1 + LGX_MAX_FEET; ++pass) {
+    const int nc = pass == 0 ? NP : NF;
+    double s[NP];
+    for (int k = 0; k < NP; ++k) s[k] = 0.0;
+    uint32_t bad = 0;
+    for (int e = tid; e < N; e += 256) {
+      const int id = eval_cell_of(levels, types, cell_ids, e, rows, cols);
+      if (id < 0) { ++bad; continue; }
+      if (id != cell) continue;
+      const float* b = body + (size_t)e * LGX_GAIT_BODY_COLS;
+      if (status[e] == 0 || !(b[0] > 0.f)) continue;
+      if (pass == 0) {
+        s[0] += 1.0;
+        for (int k = 0; k < LGX_GAIT_BODY_COLS; ++k) s[1 + k] += (double)b[k];
+      } else {
+        const float* r = foot + ((size_t)e * LGX_MAX_FEET + (pass - 1)) * LGX_GAIT_FOOT_COLS + 4;
+        for (int k = 0; k < NF; ++k) s[k] += (double)r[k];
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      for (int k = 0; k < NP; ++k) s[k] += __shfl_down(s[k], o, 64);
+      bad += __shfl_down(bad, o, 64);
+    }
+    __syncthreads();  // the previous pass's readers are done with part
+    if (lane == 0) {
+      for (int k = 0; k < NP; ++k) part[wv][k] = s[k];
+      if (pass == 0) bad_s[wv] = bad;
+    }
+    __syncthreads();
+    if (pass == 0) {
+      nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
+      if (tid == 0 && cell == 0) *overflow = nbad;
+    }
+    if (nbad != 0) return;  // (uniform over the block)
+    if (tid < nc) {
+      const int col = pass == 0 ? tid : NP + NF * (pass - 1) + tid;
+      cells[(size_t)cell * LGX_GAIT_CELL_COLS + col] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+    }
+  }
+}
+}  // namespace lgx
+
+// shared checks of the three lgx_gait_* calls
+static int gait_check(lgx_env* env, const lgx_gait_buffers* gb, const char* what, bool reduce) {
+  if (!env) return -2;
+  const std::string w(what);
+  if (!env->bound) return fail(env, w + " before lgx_bind");
+  if (!gb) return fail(env, w + ": gait buffers are NULL");
+  if (!gb->foot) return fail(env, w + ": foot is NULL");
+  if ((uintptr_t)gb->foot % 16 != 0) return fail(env, w + ": foot must be 16-byte aligned");
+  if (!gb->body) return fail(env, w + ": body is NULL");
+  if (!gb->status) return fail(env, w + ": status is NULL");
+  if (!gb->overflow) return fail(env, w + ": overflow is NULL");
+  if (reduce && !gb->cells) return fail(env, w + ": cells is NULL");
+  if (gb->cell_rows < 1 || gb->cell_cols < 1 || (int64_t)gb->cell_rows * gb->cell_cols > (1 << 20))
+    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  const lgx_buffers& b = env->buffers;
+  static const char* names[] = {"contact_forces", "rigid_body_states", "reset", "time_out"};
+  const void* ptrs[] = {b.contact_forces, b.rigid_body_states, b.reset, b.time_out};
+  for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
+    if (!ptrs[i]) return fail(env, w + ": required buffer not bound: " + names[i]);
+  const lgx_task_params& p = env->params;
+  if (p.num_feet < 0 || p.num_feet > LGX_MAX_FEET) return fail(env, w + ": more feet than a record holds");
+  for (int f = 0; f < p.num_feet; ++f)
+    if (p.feet_idx[f] < 0 || p.feet_idx[f] >= p.num_bodies) return fail(env, w + ": feet_idx outside the bodies");
+  return 0;
+}
+
+int64_t lgx_sizeof_gait_buffers(void) { return (int64_t)sizeof(lgx_gait_buffers); }
+
+int lgx_gait_begin(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream) {
+  if (int rc = gait_check(env, gb, "lgx_gait_begin", false)) return rc;
+  if (env->host) {
+    lgxh::gait_begin(&env->params, gb);
+    return 0;
+  }
+  const size_t N = (size_t)env->params.num_envs;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_OK(hipMemsetAsync(gb->foot, 0, sizeof(float) * LGX_GAIT_FOOT_COLS * LGX_MAX_FEET * N, st));
+  HIP_OK(hipMemsetAsync(gb->body, 0, sizeof(float) * LGX_GAIT_BODY_COLS * N, st));
+  HIP_OK(hipMemsetAsync(gb->status, 0, N, st));
+  HIP_OK(hipMemsetAsync(gb->overflow, 0, sizeof(uint32_t), st));
+  return 0;
+}
+
+int lgx_gait_record(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream) {
+  if (int rc = gait_check(env, gb, "lgx_gait_record", false)) return rc;
+  if (env->host) {
+    lgxh::gait_record(&env->params, &env->buffers, gb);
+    return 0;
+  }
+  const int64_t threads = (int64_t)env->params.num_envs * 4;
+  hipLaunchKernelGGL(lgx::gait_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, env->d_params, env->d_buffers, gb->foot, gb->body, gb->status);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int lgx_gait_reduce(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream) {
+  if (int rc = gait_check(env, gb, "lgx_gait_reduce", true)) return rc;
+  if (env->host) {
+    const int bad = lgxh::gait_reduce(&env->params, &env->buffers, gb);
+    if (bad) return fail(env, "lgx_gait_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
+                              "outside the cell grid (cells not written)");
+    return 0;
+  }
+  const lgx_buffers& b = env->buffers;
+  hipLaunchKernelGGL(lgx::gait_reduce_kernel, dim3((unsigned)(gb->cell_rows * gb->cell_cols)), dim3(256), 0,
+                     (hipStream_t)hip_stream, gb->foot, gb->body, gb->status, b.terrain_levels, b.terrain_types,
+                     gb->cell_ids, env->params.num_envs, gb->cell_rows, gb->cell_cols, gb->cells, gb->overflow);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 #ifdef LGX_PHASE_CLOCK
 // dev builds only: per-env phase cycle counters ([num_envs][16] uint32, device memory)
 int lgx_debug_phase_buffer(uint32_t* dev_ptr) {

@@ -368,6 +368,65 @@ LGX_HD void trace_peak_merge(float& pn, int& pb, float n, int b) {
   }
 }
 
+// Gait record (lgx_gait_buffers, include/lgx.h ABI 12). The contact rule of a foot from its net
+// contact force F: the step's own (curc, unfiltered).
+LGX_HD bool gait_contact(const float* F) { return F[2] > 1.0f; }
+// One sample of one foot: the 16 record columns r (in registers in the kernel, in place on the
+// host) from the foot's contact force F and its rigid-body row R (position 0-2, world linear
+// velocity 7-9); first: the env's first sample. The order of the rule text of lgx_gait_record.
+LGX_HD void gait_foot_sample(float* r, bool first, const float* F, const float* R, float dt) {
+  const bool c = gait_contact(F);
+  const float z = R[2], vh = nrm2(R[7], R[8]), fh = nrm2(F[0], F[1]), fn = nrm3(F[0], F[1], F[2]);
+  if (first) {
+    r[1] = 0.f;
+  } else {
+    const bool p = r[0] != 0.f;
+    if (c && !p) {  // touchdown
+      r[5] += 1.0f;
+      r[13] = fmaxf(r[13], fn);
+      if (r[1] > 0.f) {
+        r[8] += 1.0f;
+        r[9] += r[1];
+        r[10] += r[3] - r[2];
+      }
+      r[1] = 1.0f;
+    } else if (!c && p) {  // lift-off
+      if (r[1] > 0.f) {
+        r[6] += 1.0f;
+        r[7] += r[1];
+      }
+      r[1] = 1.0f;
+      r[3] = z;
+    } else {
+      r[1] = r[1] > 0.f ? r[1] + 1.0f : 0.f;
+    }
+  }
+  r[0] = c ? 1.0f : 0.f;
+  if (c) {
+    r[4] += 1.0f;
+    r[11] += vh * dt;
+    r[12] += F[2];
+    r[2] = z;
+  } else {
+    r[3] = first ? z : fmaxf(r[3], z);
+    r[14] += vh * dt;
+  }
+  if (fh > 5.0f * fabsf(F[2])) r[15] += 1.0f;
+}
+// The new value of body column col (0..11) from its old value x; bits: bit f = foot f < nfeet is in
+// contact. (The kernel gives columns 3q..3q+2 to lane q of an env's four lanes, the host loops.)
+LGX_HD float gait_body_col(int col, float x, int bits, int nfeet) {
+  if (col == 0) return x + 1.0f;
+  if (col < 6) {
+    const int m = (bits & 1) + ((bits >> 1) & 1) + ((bits >> 2) & 1) + ((bits >> 3) & 1);
+    return m == col - 1 ? x + 1.0f : x;
+  }
+  const int i = col - 6;  // pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+  const int a = i < 3 ? 0 : (i < 5 ? 1 : 2), b = i < 3 ? i + 1 : (i < 5 ? i - 1 : 3);
+  if (b >= nfeet) return x;
+  return ((bits >> a) & 1) == ((bits >> b) & 1) ? x + 1.0f : x;
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];

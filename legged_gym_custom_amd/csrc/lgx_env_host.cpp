@@ -1247,6 +1247,70 @@ void trace_gather(const lgx_task_params* P, const lgx_trace_buffers* T, const in
   }
 }
 
+void gait_begin(const lgx_task_params* P, const lgx_gait_buffers* G) {
+  const size_t N = (size_t)P->num_envs;
+  memset(G->foot, 0, sizeof(float) * LGX_GAIT_FOOT_COLS * LGX_MAX_FEET * N);
+  memset(G->body, 0, sizeof(float) * LGX_GAIT_BODY_COLS * N);
+  memset(G->status, 0, N);
+  *G->overflow = 0;
+}
+
+// lgx_gait_record (include/lgx.h): the kernel's arithmetic (lgx_env.hip gait_record_kernel), the
+// feet and the body columns in order
+void gait_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G) {
+  const int N = P->num_envs, NB = P->num_bodies, nfeet = P->num_feet;
+  const float dt = P->dt;
+#pragma omp parallel for schedule(static)
+  for (int e = 0; e < N; ++e) {
+    if (G->status[e] != 0) continue;
+    if (B->reset[e]) {
+      G->status[e] = (B->blew_up && B->blew_up[e]) ? 3 : (B->time_out[e] ? 1 : 2);
+      continue;
+    }
+    float* body = G->body + (size_t)e * LGX_GAIT_BODY_COLS;
+    const bool first = body[0] == 0.f;
+    int bits = 0;
+    for (int f = 0; f < nfeet; ++f) {
+      const size_t row = (size_t)e * NB + P->feet_idx[f];
+      const float* F = B->contact_forces + row * 3;
+      bits |= gait_contact(F) ? (1 << f) : 0;
+      gait_foot_sample(G->foot + ((size_t)e * LGX_MAX_FEET + f) * LGX_GAIT_FOOT_COLS, first, F,
+                       B->rigid_body_states + row * 13, dt);
+    }
+    for (int col = 0; col < LGX_GAIT_BODY_COLS; ++col) body[col] = gait_body_col(col, body[col], bits, nfeet);
+  }
+}
+
+// lgx_gait_reduce: the envs in order; returns the number of envs outside the cell grid (cells are
+// written only when it is 0, overflow always is)
+int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G) {
+  const int N = P->num_envs, rows = G->cell_rows, cols = G->cell_cols;
+  auto cell_of = [&](int e) -> int64_t {
+    if (G->cell_ids) return (G->cell_ids[e] < 0 || G->cell_ids[e] >= rows * cols) ? -1 : G->cell_ids[e];
+    const int64_t lv = B->terrain_levels ? B->terrain_levels[e] : 0, ty = B->terrain_types ? B->terrain_types[e] : 0;
+    return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : lv * cols + ty;
+  };
+  int bad = 0;
+  for (int e = 0; e < N; ++e) bad += cell_of(e) < 0;
+  *G->overflow = (uint32_t)bad;
+  if (bad) return bad;
+  const size_t nc = (size_t)rows * cols * LGX_GAIT_CELL_COLS;
+  for (size_t i = 0; i < nc; ++i) G->cells[i] = 0.0;
+  for (int e = 0; e < N; ++e) {  // env order: deterministic
+    const float* body = G->body + (size_t)e * LGX_GAIT_BODY_COLS;
+    if (G->status[e] == 0 || !(body[0] > 0.f)) continue;
+    double* cl = G->cells + (size_t)cell_of(e) * LGX_GAIT_CELL_COLS;
+    cl[0] += 1.0;
+    for (int k = 0; k < LGX_GAIT_BODY_COLS; ++k) cl[1 + k] += (double)body[k];
+    for (int f = 0; f < LGX_MAX_FEET; ++f) {
+      const float* r = G->foot + ((size_t)e * LGX_MAX_FEET + f) * LGX_GAIT_FOOT_COLS;
+      double* cf = cl + 1 + LGX_GAIT_BODY_COLS + (LGX_GAIT_FOOT_COLS - 4) * f;
+      for (int k = 4; k < LGX_GAIT_FOOT_COLS; ++k) cf[k - 4] += (double)r[k];
+    }
+  }
+  return 0;
+}
+
 int threads() { return omp_get_max_threads(); }
 
 }  // namespace lgxh

@@ -37,6 +37,12 @@ void trace_begin(const lgx_task_params* P, const lgx_trace_buffers* T);
 void trace_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_trace_buffers* T);
 void trace_gather(const lgx_task_params* P, const lgx_trace_buffers* T, const int32_t* ids, int32_t m, float* out,
                   int32_t* out_len);
+// lgx_gait_begin / lgx_gait_record / lgx_gait_reduce on host buffers (OpenMP over envs; the
+// reduction in env order): the gait record, include/lgx.h ABI 12. gait_reduce returns the number of
+// envs outside the cell grid, as eval_reduce does.
+void gait_begin(const lgx_task_params* P, const lgx_gait_buffers* G);
+void gait_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G);
+int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G);
 // the worker threads the host backend uses (OpenMP)
 int threads();
 

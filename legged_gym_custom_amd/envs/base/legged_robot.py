@@ -303,6 +303,59 @@ class LeggedRobot(BaseTask):
         self._native.trace_gather(tb, ids, out, out_len, self._stream())
         return out, out_len
 
+    # ------------------------------------------------------------------ gait record
+    def gait_buffers(self, rows=None, cols=None, cell_ids=None):
+        """The gait record's tensors (include/lgx.h lgx_gait_buffers, ABI 12), allocated once per
+        (rows, cols, cell_ids tensor) so a captured loop replays on fixed addresses: gait_foot
+        [N, 4, 16] and gait_body [N, 12] (each env's first episode since gait_begin), gait_status [N]
+        (the eval_status rule) and the cells [rows, cols, 61]. rows / cols None: the terrain grid
+        (1 x 1 without one). cell_ids: an int32 [N] tensor with each env's cell (written in place by
+        the caller), instead of terrain level x type. Every key asked for keeps its tensors (a loop
+        captured on one set never replays on freed memory); the call makes that set the current
+        one, which gait_begin / gait_record / gait_cells and the three attributes refer to."""
+        if rows is None or cols is None:
+            grid = getattr(self, "terrain_levels", None) is not None
+            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
+        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr())
+        if not hasattr(self, "_gaits"):
+            self._gaits = {}  # key -> lgx_gait_buffers (which keeps its tensors, cell_ids included)
+        if key not in self._gaits:
+            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
+            n = self.num_envs
+            self._gaits[key] = self._native.gait_buffers(
+                z(n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS, dtype=torch.float32),
+                z(n, _abi.GAIT_BODY_COLS, dtype=torch.float32), z(n, dtype=torch.uint8),
+                z(key[0], key[1], _abi.GAIT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32), cell_ids=cell_ids)
+        self._gait = self._gaits[key]
+        self.gait_foot, self.gait_body, self.gait_status, self._gait_cells, self._gait_overflow = self._gait._keep[:5]
+        return self._gait
+
+    def _gait_buffers(self):
+        if getattr(self, "_gait", None) is None:
+            raise RuntimeError("no gait record: call gait_buffers(...) first")
+        return self._gait
+
+    def gait_begin(self):
+        """lgx_gait_begin: zero the gait records and record every env's next (first) episode."""
+        self._native.gait_begin(self._gait_buffers(), self._stream())
+
+    def gait_record(self):
+        """lgx_gait_record for the step just run (call after every step(); stream-ordered, no host
+        sync, capturable)."""
+        self._native.gait_record(self._gait_buffers(), self._stream())
+
+    def gait_cells(self):
+        """lgx_gait_reduce, then the cells [rows, cols, 61] float64 on the host: the number of
+        finished envs with samples, the sums of their 12 body columns and of columns 4..15 of each
+        foot. Synchronises. An env whose cell lies outside the grid is an error."""
+        gb = self._gait_buffers()
+        self._native.gait_reduce(gb, self._stream())
+        bad = int(self._gait_overflow.item())
+        if bad:
+            raise _native.LgxError(f"lgx_gait_reduce: {bad} envs have a terrain level / type (or cell id) outside "
+                                   f"the {gb.cell_rows} x {gb.cell_cols} cell grid (cells not written)")
+        return self._gait_cells.cpu().clone()
+
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""
         return torch.cuda.current_stream(self.device).cuda_stream if self.sim_device_id >= 0 else 0

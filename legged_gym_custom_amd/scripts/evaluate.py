@@ -9,7 +9,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
-         [--trace_falls M [--trace_s 2.0]]
+         [--trace_falls M [--trace_s 2.0]] [--gait]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
 history the largest one needs); several values give one report each under "sweep", on one captured
@@ -34,6 +34,14 @@ written to <the JSON's name without .json>_traces.npz (trace [M, depth, 76], len
 terrain_level, terrain_type, columns, dt); the JSON gains "traces": {"file", "envs", "depth"}. With a latency
 sweep the traces are those of its last entry.
 
+--gait: gait analysis (PolicyEvaluator.run(gait=True), gait_cell_report), valid in every mode, alone or with
+--trace_falls: a per-foot contact state machine runs on the device after every step; every cell (plain run), bin
+(push and command tests) and "total" of the JSON gains a "gait" entry: per foot duty factor, stride frequency,
+stance / swing time, clearance, slip, load share, touchdown force, step length and stumble share; per body the
+flight share, the mean number of feet in contact, the six pair synchronies and a gait label (stand / pronk / trot /
+pace / bound / mixed). One summary line per cell or bin with data is printed before the JSON ("gait <where>:
+<label>, stride Hz, mean duty factor, slip").
+
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
 eval_<policy>_command.json)."""
@@ -57,7 +65,7 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
-             cmd_start=None, trace_falls=None, trace_s=2.0):
+             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -93,21 +101,21 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         depth = min(max(int(round(float(trace_s) / float(env.dt))), 1), int(env.max_episode_length))
     if push_vel:
         report = dict(**head, **ev.run_push_test(push_vel, directions=push_dirs, at_s=push_at_s, num_steps=eval_steps,
-                                                 graph=graph, trace_depth=depth))
+                                                 graph=graph, trace_depth=depth, gait=gait))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_push.json")
     elif cmd_vx:
         report = dict(**head, **ev.run_command_test(cmd_vx, vy=cmd_vy or (0.0,), yaw=cmd_yaw or (0.0,), at_s=cmd_at_s,
                                                     start=cmd_start or (0.0, 0.0, 0.0), num_steps=eval_steps,
-                                                    graph=graph, trace_depth=depth))
+                                                    graph=graph, trace_depth=depth, gait=gait))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_command.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
-                                      trace_depth=depth)
+                                      trace_depth=depth, gait=gait)
         report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_latency.json")
     else:
         report = dict(**head, **ev.run(eval_steps, graph=graph, action_delay_s=delays_s[0] if delays_s else None,
-                                       motor_strength=motor_strength, trace_depth=depth))
+                                       motor_strength=motor_strength, trace_depth=depth, gait=gait))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}.json")
     if depth is not None:
         import numpy as np
@@ -118,6 +126,38 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
     with open(out, "w") as f:
         json.dump(report, f, indent=1)
     return report, out
+
+
+def gait_summary(report):
+    """The human-readable lines of a --gait report: one per cell or bin with data, and the total
+    ("-" where it has none)."""
+    fmt = lambda v, spec: "-" if v is None else format(v, spec)  # noqa: E731
+    lines = []
+
+    def line(where, entry, always=False):
+        g = entry.get("gait")
+        if g and (always or g["samples"] > 0):
+            lines.append(f"gait {where}: {g['gait'] or '-'}, stride {fmt(g['mean_stride_hz'], '.2f')} Hz, duty "
+                         f"{fmt(g['mean_duty_factor'], '.2f')}, slip {fmt(g['mean_slip_m_per_stance_s'], '.3f')} m/s, "
+                         f"{g['envs']} envs")
+
+    for i, rep in enumerate(report.get("sweep", [report])):
+        tag = f"delay {report['action_delay_ms'][i]:g} ms " if "sweep" in report else ""
+        if "speeds" in rep:  # the push test
+            for s, row in enumerate(rep["bins"]):
+                for d, cell in enumerate(row):
+                    line(f"{tag}push {rep['speeds'][s]:g} m/s from {rep['directions_deg'][d]:g} deg", cell)
+        elif "vx" in rep:  # the command test
+            for ix, a in enumerate(rep["bins"]):
+                for iy, b in enumerate(a):
+                    for iw, cell in enumerate(b):
+                        line(f"{tag}command vx {rep['vx'][ix]:g} vy {rep['vy'][iy]:g} yaw {rep['yaw'][iw]:g}", cell)
+        else:
+            for r, row in enumerate(rep["cells"]):
+                for c, cell in enumerate(row):
+                    line(f"{tag}level {r} type {c}", cell)
+        line(f"{tag}total", rep["total"], always=True)
+    return lines
 
 
 def main(argv=None):
@@ -137,13 +177,17 @@ def main(argv=None):
     p.add_argument("--cmd_start", type=floats, default=None)
     p.add_argument("--trace_falls", type=int, default=None)
     p.add_argument("--trace_s", type=float, default=2.0)
+    p.add_argument("--gait", action="store_true")
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
     report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
                          action_delay_ms=own.action_delay_ms, motor_strength=own.motor_strength,
                          push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s,
                          cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
-                         cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s)
+                         cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s,
+                         gait=own.gait)
+    for ln in gait_summary(report) if own.gait else ():
+        print(ln)
     print(json.dumps(report))
     return report
 

@@ -36,6 +36,12 @@ the hardest-hit other body, TRACE_COLUMNS) and freezes when the episode ends; af
 chosen envs' traces (the falls, say) are unrolled on the device and copied to the host. Memory: the
 ring takes num_envs x trace_depth x 304 B, 124 MB at 4096 envs and 100 steps.
 
+Gait analysis (gait=True of the three runs): a per-foot contact state machine runs on the device after
+each step (lgx_gait_record, include/lgx.h ABI 12) and is reduced per cell or bin of the run's mode:
+stance and swing times, stride frequency, duty factor, foot clearance, slip, touchdown force, load
+share, which feet move together, and a gait label (gait_cell_report); the per-env records:
+gait_records().
+
 Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
@@ -98,6 +104,90 @@ def command_cell_report(ccell, dt, command):
             "gain": gain}
 
 
+# lgx_gait_record's body pairs (columns 6..11), in order
+GAIT_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+_FOOT_PLACES = {"FL": (0, 0), "FR": (0, 1), "RL": (1, 0), "RR": (1, 1),   # (front 0 / hind 1, left 0 / right 1)
+                "LF": (0, 0), "RF": (0, 1), "LH": (1, 0), "RH": (1, 1)}
+
+
+def _foot_places(foot_names):
+    """(front / hind, left / right) of each foot from its body name (FL/FR/RL/RR or LF/RF/LH/RH as
+    a token of the name); None unless they are four feet on four different corners."""
+    places = []
+    for name in foot_names:
+        hit = [_FOOT_PLACES[t] for t in str(name).upper().replace("-", "_").split("_") if t in _FOOT_PLACES]
+        if len(hit) != 1:
+            return None
+        places.append(hit[0])
+    return places if len(places) == 4 and len(set(places)) == 4 else None
+
+
+def gait_label(mean_duty, pair_sync, foot_names):
+    """The gait label, a rule and not a measurement: diag, lat and fore are the means of the two
+    diagonal, same-side and front/hind pair synchronies (the share of samples in which both feet of
+    the pair had the same contact state). "stand" if the mean duty factor exceeds 0.95; else "pronk"
+    if all three exceed 0.8; else "trot" / "pace" / "bound" for the largest of diag / lat / fore when
+    it leads the other two by at least 0.1; else "mixed". None without data or when the feet cannot
+    be placed from their names."""
+    places = _foot_places(foot_names)
+    if places is None or mean_duty is None or pair_sync is None or any(v is None for v in pair_sync):
+        return None
+    kinds = {"diag": [], "lat": [], "fore": []}
+    for (a, b), v in zip(GAIT_PAIRS, pair_sync):
+        (ea, sa), (eb, sb) = places[a], places[b]
+        kinds["fore" if ea == eb else ("lat" if sa == sb else "diag")].append(v)
+    diag, lat, fore = (sum(kinds[k]) / len(kinds[k]) for k in ("diag", "lat", "fore"))
+    if mean_duty > 0.95:
+        return "stand"
+    if min(diag, lat, fore) > 0.8:
+        return "pronk"
+    ranked = sorted(((diag, "trot"), (lat, "pace"), (fore, "bound")), reverse=True)
+    return ranked[0][1] if ranked[0][0] - ranked[1][0] >= 0.1 else "mixed"
+
+
+def gait_cell_report(row, dt, foot_names):
+    """The gait entries of one gait cell row [61] (lgx_gait_reduce: the number of finished envs with
+    samples, sums of the 12 body columns, sums of columns 4..15 of each foot) for the feet
+    foot_names (their body names, in feet_idx order). JSON-serialisable; None where there is no
+    data, never NaN.
+
+    Per foot ("feet"[name]): duty_factor (stance samples / samples), stride_hz (touchdowns per
+    second), mean_stance_s / mean_swing_s (over the stances / swings whose both ends were seen),
+    mean_clearance_m (the highest point of a completed swing over its lift-off height),
+    slip_m_per_stance_s (horizontal foot travel while in contact, per second of stance), load_share
+    (the foot's share of the summed vertical stance force), mean_touchdown_force (the envs' mean of
+    their hardest touchdown, N), mean_step_length_m (horizontal foot travel per completed swing:
+    the swing path over the completed swings) and stumble_share (samples with a horizontal force
+    above 5 x the vertical one). Per body: flight_share (no foot in contact), mean_feet_in_contact,
+    pair_sync (GAIT_PAIRS order), mean_duty_factor, mean_stride_hz, mean_slip_m_per_stance_s (means
+    over the feet that have data) and gait (gait_label)."""
+    c = [float(v) for v in row]
+    assert len(c) == _abi.GAIT_CELL_COLS
+    div = lambda a, b: a / b if b > 0 else None  # noqa: E731
+    def mean(v):  # over the feet that have data
+        v = [x for x in v if x is not None]
+        return sum(v) / len(v) if v else None
+    n, samples, hist, pairs = int(round(c[0])), c[1], c[2:7], c[7:13]
+    names = [str(x) for x in foot_names][:_abi.MAX_FEET]
+    per = 1 + _abi.GAIT_BODY_COLS
+    blocks = [c[per + 12 * f: per + 12 * (f + 1)] for f in range(len(names))]
+    load = sum(b[8] for b in blocks)
+    feet = {}
+    for name, b in zip(names, blocks):
+        feet[name] = {"duty_factor": div(b[0], samples), "stride_hz": div(b[1], samples * dt),
+                      "mean_stance_s": div(b[3] * dt, b[2]), "mean_swing_s": div(b[5] * dt, b[4]),
+                      "mean_clearance_m": div(b[6], b[4]), "slip_m_per_stance_s": div(b[7], b[0] * dt),
+                      "load_share": div(b[8], load), "mean_touchdown_force": div(b[9], n),
+                      "mean_step_length_m": div(b[10], b[4]), "stumble_share": div(b[11], samples)}
+    sync = [div(pairs[i], samples) if max(GAIT_PAIRS[i]) < len(names) else None for i in range(6)]
+    duty = mean([f["duty_factor"] for f in feet.values()])
+    return {"envs": n, "samples": int(round(samples)), "gait": gait_label(duty, sync, names),
+            "flight_share": div(hist[0], samples),
+            "mean_feet_in_contact": div(sum(m * h for m, h in enumerate(hist)), samples), "pair_sync": sync,
+            "mean_duty_factor": duty, "mean_stride_hz": mean([f["stride_hz"] for f in feet.values()]),
+            "mean_slip_m_per_stance_s": mean([f["slip_m_per_stance_s"] for f in feet.values()]), "feet": feet}
+
+
 def _min_max(t, kind):
     return None if t is None else [kind(t.min()), kind(t.max())]
 
@@ -115,7 +205,7 @@ class PolicyEvaluator:
         if torch.device(self.device) != torch.device(env.device):
             raise RuntimeError(f"the evaluator runs the policy on the env's device ({env.device}), not {self.device}")
         self.on_gpu = self.device.startswith("cuda")
-        self._graph = self._graph_key = None            # run's captured loop (key: the trace depth)
+        self._graph = self._graph_key = None            # run's captured loop (key: the trace depth, gait)
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
         self._fused = None
@@ -124,6 +214,8 @@ class PolicyEvaluator:
         self.last_cmd_cells = self.last_cmd_bins = None
         self._trace_depth = None     # the flight recorder's depth in the run under way (None: off)
         self.last_trace_depth = None  # the depth of the last finished run, None when it was not traced
+        self._gait = False            # whether the run under way keeps the gait record
+        self.last_gait_cells = None   # [rows, cols, 61] of the last finished run, None without gait=True
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -159,10 +251,13 @@ class PolicyEvaluator:
 
     def step(self, ev=None):
         """One eager iteration: act, env.step, eval_accumulate (ev: the eval buffers to record
-        into; default: the plain evaluation's), and trace_record in a traced run."""
+        into; default: the plain evaluation's), gait_record in a gait run and trace_record in a
+        traced run."""
         with torch.no_grad():
             self.env.step(self.act())
             self.env.eval_accumulate(ev)
+            if self._gait:
+                self.env.gait_record()
             if self._trace_depth is not None:
                 self.env.trace_record()
 
@@ -180,13 +275,17 @@ class PolicyEvaluator:
             env.reset()
             env.episode_length_buf = torch.zeros_like(env.episode_length_buf)
             env.eval_begin(ev)
+            if self._gait:
+                env.gait_begin()
             if self._trace_depth is not None:
                 env.trace_begin()
 
-    def _set_trace(self, trace_depth):
+    def _set_trace(self, trace_depth, gait=False):
         """Start a run: the flight recorder's depth for it (None: off; else the env's rings of that
-        depth, allocated once per depth)."""
-        self.last_trace_depth = None
+        depth, allocated once per depth) and whether it keeps the gait record (the mode picks the
+        env's gait buffers: their cell key is the mode's)."""
+        self.last_trace_depth = self.last_gait_cells = None
+        self._gait = bool(gait)
         self._trace_depth = None if trace_depth is None else int(trace_depth)
         if self._trace_depth is not None:
             self.env.trace_buffers(self._trace_depth)
@@ -204,13 +303,16 @@ class PolicyEvaluator:
                 torch.cuda.graph(g, capture_error_mode=self.alg.capture_mode()):
             env.step(self.act())
             env.eval_accumulate(ev)
+            if self._gait:
+                env.gait_record()
             if self._trace_depth is not None:
                 env.trace_record()
         env.common_step_counter = csc  # host mirror (capture advanced it, the device did not)
         return g
 
     # ------------------------------------------------------------------ run
-    def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None, trace_depth=None):
+    def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None, trace_depth=None,
+            gait=False):
         """Evaluate: reset, num_steps x {act, step, accumulate}, reduce, one host read; returns the
         report (JSON-serialisable): per-cell and total entries REPORT_KEYS, None where a cell has
         no data (never NaN).
@@ -231,9 +333,15 @@ class PolicyEvaluator:
         trace_depth: record the last trace_depth steps of every env's episode in the flight recorder
         (the loop body gains lgx_trace_record, in a captured loop of its own per depth; the cells are
         bit-identical to an untraced run's); read them with traces(). None: no recorder, the loop
-        and its graph are the untraced ones."""
+        and its graph are the untraced ones.
+        gait: keep the gait record (the loop body gains lgx_gait_record, in a captured loop of its
+        own; the cells are bit-identical to a run's without it): the report gains a "gait" entry
+        (gait_cell_report) in every cell and in total; the per-env records: gait_records(). False:
+        nothing changes."""
         env = self.env
-        self._set_trace(trace_depth)
+        self._set_trace(trace_depth, gait)
+        if self._gait:
+            env.gait_buffers()  # the terrain grid is the cell key
         saved = []  # (buffer, its values before this run)
         try:
             if action_delay_s is not None:
@@ -256,15 +364,41 @@ class PolicyEvaluator:
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
-        if use_graph and (self._graph is None or self._graph_key != self._trace_depth):
-            self._graph, self._graph_key = self._capture(), self._trace_depth
+        gkey = (self._trace_depth, self._gait)
+        if use_graph and (self._graph is None or self._graph_key != gkey):
+            self._graph, self._graph_key = self._capture(), gkey
         self.begin()
         t0 = self._loop(steps, self._graph if use_graph else None, None)
         cells = env.eval_cells()  # reduce + the host read (synchronises)
+        gcells = env.gait_cells() if self._gait else None
         wall = time.perf_counter() - t0
         self.last_trace_depth = self._trace_depth
         self.last_cells = cells  # [rows, cols, 12] float64, as lgx_eval_reduce wrote them
-        return self.report(cells, steps, wall, use_graph)
+        self.last_gait_cells = gcells  # [rows, cols, 61] float64, as lgx_gait_reduce wrote them
+        out = self.report(cells, steps, wall, use_graph)
+        if gcells is not None:
+            g = self._gait_report(gcells)
+            out["total"]["gait"] = g(gcells.reshape(-1, gcells.shape[2]).sum(0))
+            for r, row in enumerate(out["cells"]):
+                for c, cell in enumerate(row):
+                    cell["gait"] = g(gcells[r, c])
+        return out
+
+    def _gait_report(self, gcells):
+        """gait_cell_report for this env's time step and feet."""
+        env = self.env
+        dt, names = float(env.dt), [env.body_names[i] for i in env.feet_indices.tolist()]
+        return lambda row: gait_cell_report(row, dt, names)
+
+    def gait_records(self):
+        """The per-env gait records of the last run (it must have been one with gait=True), numpy
+        arrays on the host: foot [N, 4, 16], body [N, 12] and status [N] (lgx_gait_buffers)."""
+        if self.last_gait_cells is None:
+            raise RuntimeError("gait_records(): the last run kept no gait record (pass gait=True to run, "
+                               "run_push_test or run_command_test first)")
+        env = self.env
+        return {"foot": env.gait_foot.cpu().numpy(), "body": env.gait_body.cpu().numpy(),
+                "status": env.gait_status.cpu().numpy()}
 
     def _loop(self, steps, g, ev):
         """steps x the loop body (g: its captured graph, or None for the eager loop) recording
@@ -284,7 +418,7 @@ class PolicyEvaluator:
 
     # ------------------------------------------------------------------ push recovery
     def run_push_test(self, speeds, directions=8, at_s=2.0, settle_tol=0.3, num_steps=None, graph=True,
-                      trace_depth=None):
+                      trace_depth=None, gait=False):
         """How hard a shove does the policy survive, from which side, and how quickly does it
         settle: one run in which every env is pushed once, at episode step round(at_s / dt), by a
         velocity impulse of its bin (speed index s, direction index d): dvel = speeds[s] *
@@ -299,7 +433,7 @@ class PolicyEvaluator:
         steps is captured (domain_rand.scheduled_pushes = True, or call this before run()).
         The schedule is cleared in place when the run ends, so a following run() is the plain one.
 
-        trace_depth: the flight recorder, as in run().
+        trace_depth: the flight recorder, as in run(). gait: the gait record, as in run(), per bin.
 
         Returns the report: "bins"[s][d] with the REPORT_KEYS entries and pushed (finished envs
         with post-push samples), mean_peak_tilt_rad, mean_peak_lin_vel_err (m/s), survivors (timed
@@ -309,7 +443,7 @@ class PolicyEvaluator:
         ValueError: no speeds or directions, a negative or non-finite speed, a push step outside
         0 < step < max_episode_length."""
         env = self.env
-        self._set_trace(trace_depth)
+        self._set_trace(trace_depth, gait)
         speeds = [float(v) for v in speeds]
         S, D = len(speeds), int(directions)
         if S < 1 or D < 1 or not all(math.isfinite(v) and v >= 0.0 for v in speeds):
@@ -329,34 +463,44 @@ class PolicyEvaluator:
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         key = (S, D, float(settle_tol))
-        gkey = key + (self._trace_depth,)
+        gkey = key + (self._trace_depth, self._gait)
         try:
             env.set_push_schedule(0, dvel)  # (the first one allocates: refused once a loop is captured)
             ev = env.push_eval_buffers(*key)
             env.push_cell_ids.copy_(bins.to(torch.int32))
+            if self._gait:
+                env.gait_buffers(S, D, env.push_cell_ids)  # the bin is the cell key
             if use_graph and (self._push_graph is None or self._push_graph_key != gkey):
                 self._push_graph, self._push_graph_key = self._capture(ev), gkey
             self.begin(ev)
             env.set_push_schedule(step, dvel)  # after begin: its reset ends with an env step of its own
             t0 = self._loop(steps, self._push_graph if use_graph else None, ev)
             cells, pcells = env.eval_push_cells()  # reduce + the host read (synchronises)
+            gcells = env.gait_cells() if self._gait else None
             wall = time.perf_counter() - t0
         finally:
             env.clear_push_schedule()
         self.last_cells, self.last_push_cells, self.last_push_bins = cells, pcells, bins
-        self.last_trace_depth = self._trace_depth
+        self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells
         dt, w = float(env.dt), self.mass * self.gravity
         both = lambda c, p: {**cell_report(c, dt, w), **push_cell_report(p, dt)}  # noqa: E731
-        return {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
-                "graph": use_graph, "speeds": speeds, "directions_deg": [360.0 * d / D for d in range(D)],
-                "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
-                "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
-                "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)],
-                "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
+        out = {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
+               "graph": use_graph, "speeds": speeds, "directions_deg": [360.0 * d / D for d in range(D)],
+               "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
+               "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
+               "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)],
+               "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
+        if gcells is not None:
+            g = self._gait_report(gcells)
+            out["total"]["gait"] = g(gcells.reshape(-1, gcells.shape[2]).sum(0))
+            for s in range(S):
+                for d in range(D):
+                    out["bins"][s][d]["gait"] = g(gcells[s, d])
+        return out
 
     # ------------------------------------------------------------------ command response
     def run_command_test(self, vx, vy=(0.0,), yaw=(0.0,), at_s=2.0, start=(0.0, 0.0, 0.0), steady_after_s=1.0,
-                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None):
+                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None, gait=False):
         """What does the robot do when commanded, how fast does it get there, and does it stay up:
         one run in which every env holds the command `start` = (vx, vy, yaw rate), switches at
         episode step round(at_s / dt) to the command of its bin (vx[ix], vy[iy], yaw[iw]) and is
@@ -372,7 +516,8 @@ class PolicyEvaluator:
         before the run's reset and cleared in place when the run ends, so a following run() is the
         plain one.
 
-        trace_depth: the flight recorder, as in run().
+        trace_depth: the flight recorder, as in run(). gait: the gait record, as in run(), per bin
+        (how the gait changes with the commanded speed).
 
         Returns the report: "bins"[ix][iy][iw] with the REPORT_KEYS entries and switched (finished
         envs with post-switch samples), survivors (timed out among them), mean_settle_s /
@@ -385,7 +530,7 @@ class PolicyEvaluator:
         ValueError: an empty list, a non-finite entry, a switch step outside 0 < step <
         max_episode_length, a negative or non-finite tolerance or steady_after_s."""
         env = self.env
-        self._set_trace(trace_depth)
+        self._set_trace(trace_depth, gait)
         vx, vy, yaw, start = ([float(v) for v in lst] for lst in (vx, vy, yaw, start))
         if min(len(vx), len(vy), len(yaw)) < 1 or len(start) != 3 or \
                 not all(math.isfinite(v) for v in vx + vy + yaw + start):
@@ -407,34 +552,45 @@ class PolicyEvaluator:
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         key = (nx, ny * nw, float(settle_tol), float(yaw_tol), steady)
-        gkey = key + (self._trace_depth,)
+        gkey = key + (self._trace_depth, self._gait)
         try:
             # before begin: its reset sees segment 0 (the first call allocates: refused once a loop is captured)
             env.set_command_schedule([0, step], values)
             ev = env.cmd_eval_buffers(*key)
             env.cmd_cell_ids.copy_(bins.to(torch.int32))
             env.cmd_switch_step.fill_(step)
+            if self._gait:
+                env.gait_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
             if use_graph and (self._cmd_graph is None or self._cmd_graph_key != gkey):
                 self._cmd_graph, self._cmd_graph_key = self._capture(ev), gkey
             self.begin(ev)
             t0 = self._loop(steps, self._cmd_graph if use_graph else None, ev)
             cells, ccells = env.eval_command_cells()  # reduce + the host read (synchronises)
+            gcells = env.gait_cells() if self._gait else None
             wall = time.perf_counter() - t0
         finally:
             env.clear_command_schedule()
         self.last_cells, self.last_cmd_cells, self.last_cmd_bins = cells, ccells, bins
-        self.last_trace_depth = self._trace_depth
+        self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells
         w = self.mass * self.gravity
         both = lambda c, p, cmd: {**cell_report(c, dt, w), **command_cell_report(p, dt, cmd)}  # noqa: E731
         total = both(cells.reshape(-1, cells.shape[2]).sum(0), ccells.reshape(-1, ccells.shape[2]).sum(0), (0.0, 0.0, 0.0))
         del total["achieved"], total["gain"]  # (means over different commands say nothing)
-        return {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
-                "graph": use_graph, "vx": vx, "vy": vy, "yaw": yaw, "start": start, "switch_step": step,
-                "switch_at_s": step * dt, "steady_after": steady, "settle_tol": float(settle_tol),
-                "yaw_tol": float(yaw_tol), "total": total,
-                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
-                           for iw in range(nw)] for iy in range(ny)] for ix in range(nx)],
-                "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
+        out = {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
+               "graph": use_graph, "vx": vx, "vy": vy, "yaw": yaw, "start": start, "switch_step": step,
+               "switch_at_s": step * dt, "steady_after": steady, "settle_tol": float(settle_tol),
+               "yaw_tol": float(yaw_tol), "total": total,
+               "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
+                          for iw in range(nw)] for iy in range(ny)] for ix in range(nx)],
+               "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
+        if gcells is not None:
+            g = self._gait_report(gcells)
+            total["gait"] = g(gcells.reshape(-1, gcells.shape[2]).sum(0))
+            for ix in range(nx):
+                for iy in range(ny):
+                    for iw in range(nw):
+                        out["bins"][ix][iy][iw]["gait"] = g(gcells[ix, iy * nw + iw])
+        return out
 
     # ------------------------------------------------------------------ flight recorder
     def traces(self, which="falls", max_envs=16):
