@@ -98,6 +98,22 @@ class NativeEnv:
         self._check(self._L.lgx_episode_extras(self.handle, p(means), p(level_mean), p(time_outs), p(step_dev),
                                                C.c_void_p(stream)), "lgx_episode_extras")
 
+    def _fill(self, struct, label, table):
+        """The check every tensor of a buffers struct gets, then struct.name = its address (struct None:
+        check only). table: (name, tensor, shape or None for any, dtype, required) each; label names
+        the struct in the LgxError. An optional tensor that is None leaves its member NULL."""
+        for name, t, shape, dtype, required in table:
+            if t is None:
+                if required:
+                    raise LgxError(f"{label} {name} is required")
+                continue
+            if (shape is not None and tuple(t.shape) != tuple(shape)) or str(t.dtype) != "torch." + dtype \
+                    or not t.is_contiguous() or t.device.type != self._dev_type:
+                raise LgxError(f"{label} {name} must be a contiguous {dtype} tensor"
+                               f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
+            if struct is not None:
+                setattr(struct, name, t.data_ptr())
+
     def eval_buffers(self, acc, status, cells, overflow, cell_ids=None, push_rec=None, push_cells=None,
                      settle_tol=0.0, cmd_switch_step=None, cmd_rec=None, cmd_cells=None, yaw_tol=0.0, steady_after=0):
         """lgx_eval_buffers over the given tensors: acc [N, 8] fp32, status [N] uint8, cells
@@ -108,13 +124,6 @@ class NativeEnv:
         [rows, cols, 9] float64 (needs cmd_rec; cmd_rec without cmd_switch_step is refused by the
         lgx_eval_* calls)."""
         n = self.params.num_envs
-        rc = tuple(cells.shape[:2]) if cells.dim() == 3 else None
-        want = {"acc": ((n, _abi.EVAL_METRICS), "float32"), "status": ((n,), "uint8"),
-                "cells": (None, "float64"), "overflow": ((1,), "int32"), "cell_ids": ((n,), "int32"),
-                "push_rec": ((n, _abi.EVAL_PUSH_REC), "float32"),
-                "push_cells": (None if rc is None else rc + (_abi.EVAL_PUSH_COLS,), "float64"),
-                "cmd_switch_step": ((n,), "int32"), "cmd_rec": ((n, _abi.EVAL_CMD_REC), "float32"),
-                "cmd_cells": (None if rc is None else rc + (_abi.EVAL_CMD_COLS,), "float64")}
         if push_cells is not None and push_rec is None:
             raise LgxError("eval buffer push_cells needs push_rec")
         if not 0.0 <= float(settle_tol) < float("inf"):
@@ -127,19 +136,17 @@ class NativeEnv:
             raise LgxError(f"steady_after must be a step count >= 0 (got {steady_after})")
         ev = _abi.EvalBuffers()
         ev.settle_tol, ev.yaw_tol, ev.steady_after = float(settle_tol), float(yaw_tol), int(steady_after)
-        for name, t in (("acc", acc), ("status", status), ("cells", cells), ("overflow", overflow),
-                        ("cell_ids", cell_ids), ("push_rec", push_rec), ("push_cells", push_cells),
-                        ("cmd_switch_step", cmd_switch_step), ("cmd_rec", cmd_rec), ("cmd_cells", cmd_cells)):
-            if t is None:
-                continue  # (an optional one: the struct's member stays NULL)
-            shape, dtype = want[name]
-            if name == "cells" and (t.dim() != 3 or t.shape[2] != _abi.EVAL_CELL_COLS):
-                raise LgxError(f"eval buffer cells must be [rows, cols, {_abi.EVAL_CELL_COLS}]")
-            if (shape is not None and tuple(t.shape) != shape) or str(t.dtype) != "torch." + dtype \
-                    or not t.is_contiguous() or t.device.type != self._dev_type:
-                raise LgxError(f"eval buffer {name} must be a contiguous {dtype} tensor"
-                               f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
-            setattr(ev, name, t.data_ptr())
+        if cells.dim() != 3 or cells.shape[2] != _abi.EVAL_CELL_COLS:
+            raise LgxError(f"eval buffer cells must be [rows, cols, {_abi.EVAL_CELL_COLS}]")
+        rc = tuple(cells.shape[:2])
+        self._fill(ev, "eval buffer", [  # (a required one left None stays NULL: the lgx_eval_* calls refuse it)
+            ("acc", acc, (n, _abi.EVAL_METRICS), "float32", False), ("status", status, (n,), "uint8", False),
+            ("cells", cells, None, "float64", False), ("overflow", overflow, (1,), "int32", False),
+            ("cell_ids", cell_ids, (n,), "int32", False), ("push_rec", push_rec, (n, _abi.EVAL_PUSH_REC), "float32", False),
+            ("push_cells", push_cells, rc + (_abi.EVAL_PUSH_COLS,), "float64", False),
+            ("cmd_switch_step", cmd_switch_step, (n,), "int32", False),
+            ("cmd_rec", cmd_rec, (n, _abi.EVAL_CMD_REC), "float32", False),
+            ("cmd_cells", cmd_cells, rc + (_abi.EVAL_CMD_COLS,), "float64", False)])
         ev.cell_rows, ev.cell_cols = int(cells.shape[0]), int(cells.shape[1])
         ev._keep = (acc, status, cells, overflow, cell_ids, push_rec, push_cells, cmd_switch_step, cmd_rec, cmd_cells)
         return ev
@@ -163,18 +170,10 @@ class NativeEnv:
         n = self.params.num_envs
         if ring is not None and (ring.dim() != 3 or ring.shape[1] < 1):
             raise LgxError(f"trace buffer ring must be [N, depth >= 1, {_abi.TRACE_COLS}] (depth = 0 holds no row)")
-        want = {"ring": (None if ring is None else (n, ring.shape[1], _abi.TRACE_COLS), "float32"),
-                "count": ((n,), "int32"), "status": ((n,), "uint8")}
         tb = _abi.TraceBuffers()
-        for name, t in (("ring", ring), ("count", count), ("status", status)):
-            if t is None:
-                raise LgxError(f"trace buffer {name} is required")
-            shape, dtype = want[name]
-            if tuple(t.shape) != shape or str(t.dtype) != "torch." + dtype or not t.is_contiguous() \
-                    or t.device.type != self._dev_type:
-                raise LgxError(f"trace buffer {name} must be a contiguous {dtype} tensor {list(shape)} "
-                               f"in the env's memory space")
-            setattr(tb, name, t.data_ptr())
+        self._fill(tb, "trace buffer", [
+            ("ring", ring, None if ring is None else (n, ring.shape[1], _abi.TRACE_COLS), "float32", True),
+            ("count", count, (n,), "int32", True), ("status", status, (n,), "uint8", True)])
         tb.depth = int(ring.shape[1])
         tb._keep = (ring, count, status)
         return tb
@@ -192,13 +191,9 @@ class NativeEnv:
         out_len [m] int32 (all in the env's memory space). An id outside [0, N) gives zero rows and
         out_len -1."""
         m = int(ids.shape[0])
-        want = (("ids", ids, (m,), "int32"), ("out", out, (m, tb.depth, _abi.TRACE_COLS), "float32"),
-                ("out_len", out_len, (m,), "int32"))
-        for name, t, shape, dtype in want:
-            if tuple(t.shape) != shape or str(t.dtype) != "torch." + dtype or not t.is_contiguous() \
-                    or t.device.type != self._dev_type:
-                raise LgxError(f"trace gather {name} must be a contiguous {dtype} tensor {list(shape)} "
-                               f"in the env's memory space")
+        self._fill(None, "trace gather", [("ids", ids, (m,), "int32", True),
+                                          ("out", out, (m, tb.depth, _abi.TRACE_COLS), "float32", True),
+                                          ("out_len", out_len, (m,), "int32", True)])
         self._check(self._L.lgx_trace_gather(self.handle, C.byref(tb), C.c_void_p(ids.data_ptr()), m,
                                              C.c_void_p(out.data_ptr()), C.c_void_p(out_len.data_ptr()),
                                              C.c_void_p(stream)), "lgx_trace_gather")
@@ -210,22 +205,12 @@ class NativeEnv:
         n = self.params.num_envs
         if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.GAIT_CELL_COLS):
             raise LgxError(f"gait buffer cells must be [rows, cols, {_abi.GAIT_CELL_COLS}]")
-        want = {"foot": ((n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS), "float32"),
-                "body": ((n, _abi.GAIT_BODY_COLS), "float32"), "status": ((n,), "uint8"),
-                "cells": (None, "float64"), "overflow": ((1,), "int32"), "cell_ids": ((n,), "int32")}
         gb = _abi.GaitBuffers()
-        for name, t in (("foot", foot), ("body", body), ("status", status), ("cells", cells), ("overflow", overflow),
-                        ("cell_ids", cell_ids)):
-            if t is None:
-                if name == "cell_ids":
-                    continue  # (optional: the struct's member stays NULL)
-                raise LgxError(f"gait buffer {name} is required")
-            shape, dtype = want[name]
-            if (shape is not None and tuple(t.shape) != shape) or str(t.dtype) != "torch." + dtype \
-                    or not t.is_contiguous() or t.device.type != self._dev_type:
-                raise LgxError(f"gait buffer {name} must be a contiguous {dtype} tensor"
-                               f"{'' if shape is None else ' ' + str(list(shape))} in the env's memory space")
-            setattr(gb, name, t.data_ptr())
+        self._fill(gb, "gait buffer", [
+            ("foot", foot, (n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS), "float32", True),
+            ("body", body, (n, _abi.GAIT_BODY_COLS), "float32", True), ("status", status, (n,), "uint8", True),
+            ("cells", cells, None, "float64", True), ("overflow", overflow, (1,), "int32", True),
+            ("cell_ids", cell_ids, (n,), "int32", False)])
         gb.cell_rows, gb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
         gb._keep = (foot, body, status, cells, overflow, cell_ids)
         return gb

@@ -2041,6 +2041,7 @@ __global__ __launch_bounds__(64) void reset_kernel(const lgx_task_params* __rest
 // ============================================================== C ABI
 #include <stdio.h>
 
+#include <initializer_list>
 #include <string>
 
 struct lgx_env {
@@ -2480,7 +2481,7 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
   }
   if (!live || st != 0) return;
   if (rs) {
-    if (q == 0) A.status[e] = (A.blew_up && A.blew_up[e]) ? 3 : (A.time_out[e] ? 1 : 2);
+    if (q == 0) A.status[e] = episode_end_status(A.blew_up, A.time_out, e);
     return;
   }
   const float v0 = A.lin_vel[e * 3], v1 = A.lin_vel[e * 3 + 1], w2 = A.ang_vel[e * 3 + 2];
@@ -2526,24 +2527,48 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
   }
 }
 
-// The cell of env e for lgx_eval_reduce: cell_ids[e] when set, else level * cols + type; -1 when
-// it lies outside the rows x cols grid (never used as an index).
-__device__ inline int eval_cell_of(const int64_t* __restrict__ levels, const int64_t* __restrict__ types,
-                                   const int32_t* __restrict__ cell_ids, int e, int rows, int cols) {
-  if (cell_ids) {
-    const int id = cell_ids[e];
-    return (id < 0 || id >= rows * cols) ? -1 : id;
+// The reduce skeleton of lgx_eval_reduce / lgx_gait_reduce: THE definition of the tree (DESIGN.md
+// "The reduce tree"; tests/test_gpu_reduce_tree.py pins it). One block of 256 threads per cell.
+// Thread t scans envs t, t+256, ... in increasing order (the loads coalesce) and lets add(e, s) add
+// what an env of this block's cell contributes to its NC fp64 partials s; the partials are combined
+// by a fixed tree (shuffle-down inside each wave, then the four wave results in wave order), so the
+// result depends only on the records. Every block scans every env's cell and so knows the number of
+// out-of-grid envs, which is returned: when there are none, thread k < NC hands the sum of
+// partial k to store(k, sum); when there are any, nothing is stored. (A caller that runs several
+// passes puts a barrier between them: the previous pass's readers must be done with the exchange.)
+extern "C++" {  // (a template, inside the C ABI block)
+template <int NC, class Add, class Store>
+__device__ __forceinline__ uint32_t cell_reduce(const int64_t* __restrict__ levels, const int64_t* __restrict__ types,
+                                                const int32_t* __restrict__ cell_ids, int N, int rows, int cols,
+                                                Add add, Store store) {
+  __shared__ double part[4][NC];
+  __shared__ uint32_t bad_s[4];
+  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double s[NC];
+  for (int k = 0; k < NC; ++k) s[k] = 0.0;
+  uint32_t bad = 0;
+  for (int e = tid; e < N; e += 256) {
+    const int id = cell_of_env(levels, types, cell_ids, e, rows, cols);
+    if (id < 0) { ++bad; continue; }
+    if (id == cell) add(e, s);
   }
-  const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
-  return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : (int)(lv * cols + ty);
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int k = 0; k < NC; ++k) s[k] += __shfl_down(s[k], o, 64);
+    bad += __shfl_down(bad, o, 64);
+  }
+  if (lane == 0) {
+    for (int k = 0; k < NC; ++k) part[wv][k] = s[k];
+    bad_s[wv] = bad;
+  }
+  __syncthreads();
+  const uint32_t nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
+  if (nbad == 0 && tid < NC) store(tid, ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]);
+  return nbad;
 }
+}  // extern "C++"
 
-// lgx_eval_reduce: one block of 256 threads per cell. Thread t scans envs t, t+256, ... in
-// increasing order (the loads coalesce) and keeps fp64 partial sums of its cell's finished envs;
-// the partials are combined by a fixed tree (shuffle-down inside each wave, then the four
-// wave results in wave order by thread 0), so the result depends only on the records. Every block
-// scans every env's level / type and so knows the number of out-of-grid envs: no block writes
-// its cell when there are any, and block 0 publishes the count.
+// lgx_eval_reduce: cell_reduce over the records of the cell's finished envs; block 0 publishes the
+// out-of-grid count.
 // ABI 9: cell_ids, when set, is the env's cell instead of level * cols + type (same range rule);
 // push_cells, when set, gets the cell's push-recovery sums from push_rec by the same tree.
 __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restrict__ acc,
@@ -2556,19 +2581,11 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
                                                           double* __restrict__ push_cells,
                                                           uint32_t* __restrict__ overflow) {
   constexpr int NA = LGX_EVAL_CELL_COLS, NC = NA + LGX_EVAL_PUSH_COLS;
-  __shared__ double part[4][NC];
-  __shared__ uint32_t bad_s[4];
-  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  double s[NC];
-  for (int k = 0; k < NC; ++k) s[k] = 0.0;
-  uint32_t bad = 0;
-  for (int e = tid; e < N; e += 256) {
-    const int id = eval_cell_of(levels, types, cell_ids, e, rows, cols);
-    if (id < 0) { ++bad; continue; }
-    if (id != cell) continue;
+  const int cell = blockIdx.x;
+  const uint32_t nbad = cell_reduce<NC>(levels, types, cell_ids, N, rows, cols, [=](int e, auto& s) {
     const int st = status[e];
     s[0] += 1.0;
-    if (st == 0) continue;
+    if (st == 0) return;
     s[1] += st == 1 ? 1.0 : 0.0;  // time-out
     s[2] += st == 2 ? 1.0 : 0.0;  // fall
     s[3] += st == 3 ? 1.0 : 0.0;  // blow-up
@@ -2584,28 +2601,16 @@ __global__ __launch_bounds__(256) void eval_reduce_kernel(const float* __restric
         s[NA + 4] += st == 1 ? (double)r[3] : 0.0;
       }
     }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int k = 0; k < NC; ++k) s[k] += __shfl_down(s[k], o, 64);
-    bad += __shfl_down(bad, o, 64);
-  }
-  if (lane == 0) {
-    for (int k = 0; k < NC; ++k) part[wv][k] = s[k];
-    bad_s[wv] = bad;
-  }
-  __syncthreads();
-  const uint32_t nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
-  if (tid == 0 && cell == 0 && overflow) *overflow = nbad;
-  if (nbad != 0 || tid >= NC) return;
-  const double v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-  if (tid < NA) cells[(size_t)cell * NA + tid] = v;
-  else if (push_cells) push_cells[(size_t)cell * LGX_EVAL_PUSH_COLS + (tid - NA)] = v;
+  }, [=](int k, double v) {
+    if (k < NA) cells[(size_t)cell * NA + k] = v;
+    else if (push_cells) push_cells[(size_t)cell * LGX_EVAL_PUSH_COLS + (k - NA)] = v;
+  });
+  if (threadIdx.x == 0 && cell == 0 && overflow) *overflow = nbad;
 }
 
 // lgx_eval_reduce's step-response cells (ABI 10, cmd_cells set): a second launch of the same
-// shape as eval_reduce_kernel (one block per cell, the same env order per thread and the same
-// fixed tree) over cmd_rec. It counts the out-of-grid envs itself, so it too writes nothing when
-// there are any; eval_reduce_kernel publishes the count.
+// shape as eval_reduce_kernel, cell_reduce over cmd_rec. It counts the out-of-grid envs itself, so
+// it too writes nothing when there are any; eval_reduce_kernel publishes the count.
 __global__ __launch_bounds__(256) void eval_cmd_reduce_kernel(const float* __restrict__ cmd_rec,
                                                               const uint8_t* __restrict__ status,
                                                               const int64_t* __restrict__ levels,
@@ -2613,19 +2618,10 @@ __global__ __launch_bounds__(256) void eval_cmd_reduce_kernel(const float* __res
                                                               const int32_t* __restrict__ cell_ids, int N, int rows,
                                                               int cols, double* __restrict__ cmd_cells) {
   constexpr int NC = LGX_EVAL_CMD_COLS;
-  __shared__ double part[4][NC];
-  __shared__ uint32_t bad_s[4];
-  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  double s[NC];
-  for (int k = 0; k < NC; ++k) s[k] = 0.0;
-  uint32_t bad = 0;
-  for (int e = tid; e < N; e += 256) {
-    const int id = eval_cell_of(levels, types, cell_ids, e, rows, cols);
-    if (id < 0) { ++bad; continue; }
-    if (id != cell) continue;
+  cell_reduce<NC>(levels, types, cell_ids, N, rows, cols, [=](int e, auto& s) {
     const int st = status[e];
     const float* r = cmd_rec + (size_t)e * LGX_EVAL_CMD_REC;
-    if (st == 0 || !(r[0] > 0.f)) continue;
+    if (st == 0 || !(r[0] > 0.f)) return;
     const bool surv = st == 1;
     s[0] += 1.0;
     s[1] += surv ? 1.0 : 0.0;
@@ -2633,62 +2629,67 @@ __global__ __launch_bounds__(256) void eval_cmd_reduce_kernel(const float* __res
     s[3] += surv ? (double)r[2] : 0.0;
     s[4] += (double)r[3];
     for (int k = 4; k < LGX_EVAL_CMD_REC; ++k) s[1 + k] += surv ? (double)r[k] : 0.0;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int k = 0; k < NC; ++k) s[k] += __shfl_down(s[k], o, 64);
-    bad += __shfl_down(bad, o, 64);
-  }
-  if (lane == 0) {
-    for (int k = 0; k < NC; ++k) part[wv][k] = s[k];
-    bad_s[wv] = bad;
-  }
-  __syncthreads();
-  const uint32_t nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
-  if (nbad != 0 || tid >= NC) return;
-  cmd_cells[(size_t)cell * NC + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+  }, [=](int k, double v) { cmd_cells[(size_t)blockIdx.x * NC + k] = v; });
 }
 }  // namespace lgx
 
+// The pieces the checks of the lgx_eval_* / lgx_trace_* / lgx_gait_* calls share. The common prefix:
+// the env is bound and the call's buffers (kind: "eval", "trace", "gait") are given.
+static int check_call(lgx_env* env, const void* bufs, const std::string& w, const char* kind) {
+  if (!env) return -2;
+  if (!env->bound) return fail(env, w + " before lgx_bind");
+  if (!bufs) return fail(env, w + ": " + kind + " buffers are NULL");
+  return 0;
+}
+// Every buffer of the table is bound; the failure is w + text + the first missing one's name.
+struct NamedBuffer { const char* name; const void* ptr; };
+static int check_bound(lgx_env* env, const std::string& w, const char* text,
+                       std::initializer_list<NamedBuffer> table) {
+  for (const NamedBuffer& t : table)
+    if (!t.ptr) return fail(env, w + text + t.name);
+  return 0;
+}
+static int check_feet(lgx_env* env, const std::string& w) {
+  const lgx_task_params& p = env->params;
+  for (int f = 0; f < p.num_feet; ++f)
+    if (p.feet_idx[f] < 0 || p.feet_idx[f] >= p.num_bodies) return fail(env, w + ": feet_idx outside the bodies");
+  return 0;
+}
+static const char* const kNotBound = ": required buffer not bound: ";
+
 // shared checks of the three lgx_eval_* calls
 static int eval_check(lgx_env* env, const lgx_eval_buffers* ev, const char* what, bool reduce) {
-  if (!env) return -2;
   const std::string w(what);
-  if (!env->bound) return fail(env, w + " before lgx_bind");
-  if (!ev) return fail(env, w + ": eval buffers are NULL");
+  if (int rc = check_call(env, ev, w, "eval")) return rc;
   const lgx_buffers& b = env->buffers;
-  static const char* names[] = {"commands", "base_lin_vel", "base_ang_vel", "torques", "dof_state",
-                                "contact_forces", "reset", "time_out"};
-  const void* ptrs[] = {b.commands, b.base_lin_vel, b.base_ang_vel, b.torques, b.dof_state,
-                        b.contact_forces, b.reset, b.time_out};
-  for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
-    if (!ptrs[i]) return fail(env, w + ": required buffer not bound: " + names[i]);
+  if (int rc = check_bound(env, w, kNotBound, {{"commands", b.commands}, {"base_lin_vel", b.base_lin_vel},
+                                               {"base_ang_vel", b.base_ang_vel}, {"torques", b.torques},
+                                               {"dof_state", b.dof_state}, {"contact_forces", b.contact_forces},
+                                               {"reset", b.reset}, {"time_out", b.time_out}}))
+    return rc;
   if (!ev->acc || !ev->status) return fail(env, w + ": acc and status are required");
   if (ev->cell_rows < 1 || ev->cell_cols < 1 || (int64_t)ev->cell_rows * ev->cell_cols > (1 << 20))
     return fail(env, w + ": cell_rows * cell_cols must be >= 1 (and at most 2^20)");
   if (reduce && (!ev->cells || !ev->overflow)) return fail(env, w + ": cells and overflow are required");
   if (ev->push_rec) {
-    static const char* pnames[] = {"projected_gravity", "episode_length", "push_step", "commands", "base_lin_vel"};
-    const void* pptrs[] = {b.projected_gravity, b.episode_length, b.push_step, b.commands, b.base_lin_vel};
-    for (size_t i = 0; i < sizeof(pptrs) / sizeof(pptrs[0]); ++i)
-      if (!pptrs[i]) return fail(env, w + ": push_rec needs a buffer that is not bound: " + pnames[i]);
+    if (int rc = check_bound(env, w, ": push_rec needs a buffer that is not bound: ",
+                             {{"projected_gravity", b.projected_gravity}, {"episode_length", b.episode_length},
+                              {"push_step", b.push_step}, {"commands", b.commands}, {"base_lin_vel", b.base_lin_vel}}))
+      return rc;
     if (!(ev->settle_tol >= 0.f)) return fail(env, w + ": settle_tol must be >= 0");
   }
   if (ev->push_cells && !ev->push_rec) return fail(env, w + ": push_cells needs push_rec");
   if (ev->cmd_rec) {
     if (!ev->cmd_switch_step) return fail(env, w + ": cmd_rec needs cmd_switch_step");
-    static const char* cnames[] = {"projected_gravity", "episode_length"};
-    const void* cptrs[] = {b.projected_gravity, b.episode_length};
-    for (size_t i = 0; i < sizeof(cptrs) / sizeof(cptrs[0]); ++i)
-      if (!cptrs[i]) return fail(env, w + ": cmd_rec needs a buffer that is not bound: " + cnames[i]);
+    if (int rc = check_bound(env, w, ": cmd_rec needs a buffer that is not bound: ",
+                             {{"projected_gravity", b.projected_gravity}, {"episode_length", b.episode_length}}))
+      return rc;
     if (!(ev->settle_tol >= 0.f)) return fail(env, w + ": settle_tol must be >= 0");
     if (!(ev->yaw_tol >= 0.f)) return fail(env, w + ": yaw_tol must be >= 0");
     if (ev->steady_after < 0) return fail(env, w + ": steady_after must be >= 0");
   }
   if (ev->cmd_cells && !ev->cmd_rec) return fail(env, w + ": cmd_cells needs cmd_rec");
-  for (int f = 0; f < env->params.num_feet; ++f)
-    if (env->params.feet_idx[f] < 0 || env->params.feet_idx[f] >= env->params.num_bodies)
-      return fail(env, w + ": feet_idx outside the bodies");
-  return 0;
+  return check_feet(env, w);
 }
 
 int64_t lgx_sizeof_eval_buffers(void) { return (int64_t)sizeof(lgx_eval_buffers); }
@@ -2798,7 +2799,7 @@ __global__ __launch_bounds__(256) void trace_record_kernel(const lgx_task_params
   }
   if (!live || st != 0) return;
   if (rs) {
-    if (l == 0) status[e] = (B.blew_up && B.blew_up[e]) ? 3 : (B.time_out[e] ? 1 : 2);
+    if (l == 0) status[e] = episode_end_status(B, e);
     return;
   }
   float* dst = ring + ((size_t)e * depth + (size_t)(cnt % depth)) * LGX_TRACE_COLS;
@@ -2840,28 +2841,25 @@ __global__ __launch_bounds__(256) void trace_gather_kernel(const float* __restri
 
 // shared checks of the three lgx_trace_* calls
 static int trace_check(lgx_env* env, const lgx_trace_buffers* tb, const char* what, bool record) {
-  if (!env) return -2;
   const std::string w(what);
-  if (!env->bound) return fail(env, w + " before lgx_bind");
-  if (!tb) return fail(env, w + ": trace buffers are NULL");
+  if (int rc = check_call(env, tb, w, "trace")) return rc;
   if (tb->depth < 1) return fail(env, w + ": depth must be >= 1");
   if (!tb->ring) return fail(env, w + ": ring is NULL");
   if (!tb->count) return fail(env, w + ": count is NULL");
   if (!tb->status) return fail(env, w + ": status is NULL");
   if (!record) return 0;
   const lgx_buffers& b = env->buffers;
-  static const char* names[] = {"episode_length", "root_states", "base_lin_vel", "base_ang_vel", "projected_gravity",
-                                "commands", "dof_state", "torques", "actions", "contact_forces", "rew", "reset",
-                                "time_out"};
-  const void* ptrs[] = {b.episode_length, b.root_states, b.base_lin_vel, b.base_ang_vel, b.projected_gravity,
-                        b.commands, b.dof_state, b.torques, b.actions, b.contact_forces, b.rew, b.reset, b.time_out};
-  for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
-    if (!ptrs[i]) return fail(env, w + ": required buffer not bound: " + names[i]);
+  if (int rc = check_bound(env, w, kNotBound,
+                           {{"episode_length", b.episode_length}, {"root_states", b.root_states},
+                            {"base_lin_vel", b.base_lin_vel}, {"base_ang_vel", b.base_ang_vel},
+                            {"projected_gravity", b.projected_gravity}, {"commands", b.commands},
+                            {"dof_state", b.dof_state}, {"torques", b.torques}, {"actions", b.actions},
+                            {"contact_forces", b.contact_forces}, {"rew", b.rew}, {"reset", b.reset},
+                            {"time_out", b.time_out}}))
+    return rc;
   const lgx_task_params& p = env->params;
   if (p.num_dof > LGX_MAX_DOF || p.num_actions > LGX_MAX_DOF) return fail(env, w + ": more joints than a row holds");
-  for (int f = 0; f < p.num_feet; ++f)
-    if (p.feet_idx[f] < 0 || p.feet_idx[f] >= p.num_bodies) return fail(env, w + ": feet_idx outside the bodies");
-  return 0;
+  return check_feet(env, w);
 }
 
 int64_t lgx_sizeof_trace_buffers(void) { return (int64_t)sizeof(lgx_trace_buffers); }
@@ -2965,7 +2963,7 @@ __global__ __launch_bounds__(256) void gait_record_kernel(const lgx_task_params*
   bits |= __shfl_xor(bits, 2, 64);
   if (!live || st != 0) return;
   if (rs) {
-    if (q == 0) status[e] = (B.blew_up && B.blew_up[e]) ? 3 : (B.time_out[e] ? 1 : 2);
+    if (q == 0) status[e] = episode_end_status(B, e);
     return;
   }
   if (mine) {
@@ -2978,13 +2976,12 @@ __global__ __launch_bounds__(256) void gait_record_kernel(const lgx_task_params*
   bq[2] = gait_body_col(3 * q + 2, b2, bits, nfeet);
 }
 
-// lgx_gait_reduce: one block of 256 threads per cell, the shape and the tree of eval_reduce_kernel
-// (thread t scans envs t, t+256, ... in increasing order, fp64 partials, shuffle-down inside each
-// wave, the four wave results in wave order), in five passes so that a thread holds at most 13 fp64
-// partials: pass 0 the env count and the 12 body columns, pass 1 + f foot f's columns 4..15. Every
-// pass scans every env's cell id in the same order, so the result depends only on the records. The
-// out-of-grid count is formed in pass 0: no block writes its cell when there are any, and block 0
-// publishes the count.
+// lgx_gait_reduce: cell_reduce (above: the block shape, the env order and the tree) in five passes
+// so that a thread holds at most 13 fp64 partials: pass 0 the 12 body columns, pass 1 + f foot f's
+// columns 4..15, each in partials 0..11, and the env count in partial 12 (one layout for every pass
+// keeps the partials in registers). Every pass scans every env's cell id in the same order, so
+// the result depends only on the records (and every pass forms the same out-of-grid count): no
+// block writes its cell when there are any, and block 0 publishes the count.
 __global__ __launch_bounds__(256) void gait_reduce_kernel(const float* __restrict__ foot,
                                                           const float* __restrict__ body,
                                                           const uint8_t* __restrict__ status,
@@ -2994,58 +2991,30 @@ __global__ __launch_bounds__(256) void gait_reduce_kernel(const float* __restric
                                                           int cols, double* __restrict__ cells,
                                                           uint32_t* __restrict__ overflow) {
   constexpr int NP = 1 + LGX_GAIT_BODY_COLS, NF = LGX_GAIT_FOOT_COLS - 4;
-  __shared__ double part[4][NP];
-  __shared__ uint32_t bad_s[4];
-  const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  uint32_t nbad = 0;
+  static_assert(NF == LGX_GAIT_BODY_COLS, "a pass sums 12 columns (partials 0..11) and the env count (partial 12)");
+  double* c = cells + (size_t)blockIdx.x * LGX_GAIT_CELL_COLS;
   for (int pass = 0; pass < 1 + LGX_MAX_FEET; ++pass) {
-    const int nc = pass == 0 ? NP : NF;
-    double s[NP];
-    for (int k = 0; k < NP; ++k) s[k] = 0.0;
-    uint32_t bad = 0;
-    for (int e = tid; e < N; e += 256) {
-      const int id = eval_cell_of(levels, types, cell_ids, e, rows, cols);
-      if (id < 0) { ++bad; continue; }
-      if (id != cell) continue;
+    if (pass) __syncthreads();  // the previous pass's readers are done with the exchange
+    const uint32_t nbad = cell_reduce<NP>(levels, types, cell_ids, N, rows, cols, [=](int e, auto& s) {
       const float* b = body + (size_t)e * LGX_GAIT_BODY_COLS;
-      if (status[e] == 0 || !(b[0] > 0.f)) continue;
-      if (pass == 0) {
-        s[0] += 1.0;
-        for (int k = 0; k < LGX_GAIT_BODY_COLS; ++k) s[1 + k] += (double)b[k];
-      } else {
-        const float* r = foot + ((size_t)e * LGX_MAX_FEET + (pass - 1)) * LGX_GAIT_FOOT_COLS + 4;
-        for (int k = 0; k < NF; ++k) s[k] += (double)r[k];
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      for (int k = 0; k < NP; ++k) s[k] += __shfl_down(s[k], o, 64);
-      bad += __shfl_down(bad, o, 64);
-    }
-    __syncthreads();  // the previous pass's readers are done with part
-    if (lane == 0) {
-      for (int k = 0; k < NP; ++k) part[wv][k] = s[k];
-      if (pass == 0) bad_s[wv] = bad;
-    }
-    __syncthreads();
-    if (pass == 0) {
-      nbad = bad_s[0] + bad_s[1] + bad_s[2] + bad_s[3];
-      if (tid == 0 && cell == 0) *overflow = nbad;
-    }
+      if (status[e] == 0 || !(b[0] > 0.f)) return;
+      const float* r = pass == 0 ? b : foot + ((size_t)e * LGX_MAX_FEET + (pass - 1)) * LGX_GAIT_FOOT_COLS + 4;
+      for (int k = 0; k < NF; ++k) s[k] += (double)r[k];
+      s[NF] += 1.0;  // the env count (stored by pass 0)
+    }, [=](int k, double v) {
+      if (k < NF) c[pass == 0 ? 1 + k : NP + NF * (pass - 1) + k] = v;
+      else if (pass == 0) c[0] = v;
+    });
+    if (pass == 0 && threadIdx.x == 0 && blockIdx.x == 0) *overflow = nbad;
     if (nbad != 0) return;  // (uniform over the block)
-    if (tid < nc) {
-      const int col = pass == 0 ? tid : NP + NF * (pass - 1) + tid;
-      cells[(size_t)cell * LGX_GAIT_CELL_COLS + col] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
-    }
   }
 }
 }  // namespace lgx
 
 // shared checks of the three lgx_gait_* calls
 static int gait_check(lgx_env* env, const lgx_gait_buffers* gb, const char* what, bool reduce) {
-  if (!env) return -2;
   const std::string w(what);
-  if (!env->bound) return fail(env, w + " before lgx_bind");
-  if (!gb) return fail(env, w + ": gait buffers are NULL");
+  if (int rc = check_call(env, gb, w, "gait")) return rc;
   if (!gb->foot) return fail(env, w + ": foot is NULL");
   if ((uintptr_t)gb->foot % 16 != 0) return fail(env, w + ": foot must be 16-byte aligned");
   if (!gb->body) return fail(env, w + ": body is NULL");
@@ -3055,15 +3024,13 @@ static int gait_check(lgx_env* env, const lgx_gait_buffers* gb, const char* what
   if (gb->cell_rows < 1 || gb->cell_cols < 1 || (int64_t)gb->cell_rows * gb->cell_cols > (1 << 20))
     return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
   const lgx_buffers& b = env->buffers;
-  static const char* names[] = {"contact_forces", "rigid_body_states", "reset", "time_out"};
-  const void* ptrs[] = {b.contact_forces, b.rigid_body_states, b.reset, b.time_out};
-  for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); ++i)
-    if (!ptrs[i]) return fail(env, w + ": required buffer not bound: " + names[i]);
-  const lgx_task_params& p = env->params;
-  if (p.num_feet < 0 || p.num_feet > LGX_MAX_FEET) return fail(env, w + ": more feet than a record holds");
-  for (int f = 0; f < p.num_feet; ++f)
-    if (p.feet_idx[f] < 0 || p.feet_idx[f] >= p.num_bodies) return fail(env, w + ": feet_idx outside the bodies");
-  return 0;
+  if (int rc = check_bound(env, w, kNotBound, {{"contact_forces", b.contact_forces},
+                                               {"rigid_body_states", b.rigid_body_states}, {"reset", b.reset},
+                                               {"time_out", b.time_out}}))
+    return rc;
+  const int nf = env->params.num_feet;
+  if (nf < 0 || nf > LGX_MAX_FEET) return fail(env, w + ": more feet than a record holds");
+  return check_feet(env, w);
 }
 
 int64_t lgx_sizeof_gait_buffers(void) { return (int64_t)sizeof(lgx_gait_buffers); }

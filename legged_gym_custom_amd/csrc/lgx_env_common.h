@@ -368,6 +368,24 @@ LGX_HD void trace_peak_merge(float& pn, int& pb, float n, int b) {
   }
 }
 
+// The episode-end rule of the three records (eval, trace and gait status): how the episode of env e
+// ended in the step just run, which reset it: 3 blew up (when blew_up is bound), 1 timed out, 2 fell.
+LGX_HD int episode_end_status(const uint8_t* blew_up, const uint8_t* time_out, int e) {
+  return (blew_up && blew_up[e]) ? 3 : (time_out[e] ? 1 : 2);
+}
+LGX_HD int episode_end_status(const lgx_buffers& B, int e) { return episode_end_status(B.blew_up, B.time_out, e); }
+// The env-to-cell rule of lgx_eval_reduce / lgx_gait_reduce: cell_ids[e] when set, else level * cols
+// + type (0 for an unbound one); -1 when it lies outside the rows x cols grid (never used as an index).
+LGX_HD int cell_of_env(const int64_t* levels, const int64_t* types, const int32_t* cell_ids, int e, int rows,
+                       int cols) {
+  if (cell_ids) {
+    const int id = cell_ids[e];
+    return (id < 0 || id >= rows * cols) ? -1 : id;
+  }
+  const int64_t lv = levels ? levels[e] : 0, ty = types ? types[e] : 0;
+  return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : (int)(lv * cols + ty);
+}
+
 // Gait record (lgx_gait_buffers, include/lgx.h ABI 12). The contact rule of a foot from its net
 // contact force F: the step's own (curc, unfiltered).
 LGX_HD bool gait_contact(const float* F) { return F[2] > 1.0f; }

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 
 #include "lgx_env_common.h"
@@ -1094,7 +1095,7 @@ void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_e
   for (int e = 0; e < N; ++e) {
     if (E->status[e] != 0) continue;
     if (B->reset[e]) {
-      E->status[e] = (B->blew_up && B->blew_up[e]) ? 3 : (B->time_out[e] ? 1 : 2);
+      E->status[e] = episode_end_status(*B, e);
       continue;
     }
     const float* v = B->base_lin_vel + (size_t)e * 3;
@@ -1142,25 +1143,30 @@ void eval_accumulate(const lgx_task_params* P, const lgx_buffers* B, const lgx_e
   }
 }
 
+// The start of eval_reduce / gait_reduce: counts the envs outside the rows x cols grid, publishes
+// the count and returns it; when it is 0, zeroes the cell tables (pointer, columns per cell; a NULL
+// one is skipped), which the caller then fills in env order.
+struct CellTable { double* cells; int cols; };
+static int reduce_begin(const lgx_buffers* B, const int32_t* cell_ids, int N, int rows, int cols, uint32_t* overflow,
+                        std::initializer_list<CellTable> tables) {
+  int bad = 0;
+  for (int e = 0; e < N; ++e) bad += cell_of_env(B->terrain_levels, B->terrain_types, cell_ids, e, rows, cols) < 0;
+  *overflow = (uint32_t)bad;
+  if (bad) return bad;
+  for (const CellTable& t : tables)
+    if (t.cells) std::fill(t.cells, t.cells + (size_t)rows * cols * t.cols, 0.0);
+  return 0;
+}
+
 int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_buffers* E) {
   const int N = P->num_envs, rows = E->cell_rows, cols = E->cell_cols;
-  auto cell_of = [&](int e) -> int64_t {
-    if (E->cell_ids) return (E->cell_ids[e] < 0 || E->cell_ids[e] >= rows * cols) ? -1 : E->cell_ids[e];
-    const int64_t lv = B->terrain_levels ? B->terrain_levels[e] : 0, ty = B->terrain_types ? B->terrain_types[e] : 0;
-    return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : lv * cols + ty;
-  };
-  int bad = 0;
-  for (int e = 0; e < N; ++e) bad += cell_of(e) < 0;
-  *E->overflow = (uint32_t)bad;
-  if (bad) return bad;
-  const size_t nc = (size_t)rows * cols * LGX_EVAL_CELL_COLS;
-  for (size_t i = 0; i < nc; ++i) E->cells[i] = 0.0;
-  if (E->push_cells)
-    for (size_t i = 0; i < (size_t)rows * cols * LGX_EVAL_PUSH_COLS; ++i) E->push_cells[i] = 0.0;
-  if (E->cmd_cells)
-    for (size_t i = 0; i < (size_t)rows * cols * LGX_EVAL_CMD_COLS; ++i) E->cmd_cells[i] = 0.0;
+  if (int bad = reduce_begin(B, E->cell_ids, N, rows, cols, E->overflow,
+                             {{E->cells, LGX_EVAL_CELL_COLS}, {E->push_cells, LGX_EVAL_PUSH_COLS},
+                              {E->cmd_cells, LGX_EVAL_CMD_COLS}}))
+    return bad;
   for (int e = 0; e < N; ++e) {  // env order: deterministic
-    double* cl = E->cells + (size_t)cell_of(e) * LGX_EVAL_CELL_COLS;
+    const size_t id = (size_t)cell_of_env(B->terrain_levels, B->terrain_types, E->cell_ids, e, rows, cols);
+    double* cl = E->cells + id * LGX_EVAL_CELL_COLS;
     const int st = E->status[e];
     cl[0] += 1.0;
     if (st == 0) continue;
@@ -1169,7 +1175,7 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
     for (int k = 0; k < LGX_EVAL_METRICS; ++k) cl[4 + k] += (double)a[k];
     const float* r = E->push_cells ? E->push_rec + (size_t)e * LGX_EVAL_PUSH_REC : nullptr;
     if (r && r[0] > 0.f) {
-      double* pc = E->push_cells + (size_t)cell_of(e) * LGX_EVAL_PUSH_COLS;
+      double* pc = E->push_cells + id * LGX_EVAL_PUSH_COLS;
       pc[0] += 1.0;
       pc[1] += (double)r[1];
       pc[2] += (double)r[2];
@@ -1177,7 +1183,7 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
     }
     const float* cr = E->cmd_cells ? E->cmd_rec + (size_t)e * LGX_EVAL_CMD_REC : nullptr;
     if (cr && cr[0] > 0.f) {
-      double* cc = E->cmd_cells + (size_t)cell_of(e) * LGX_EVAL_CMD_COLS;
+      double* cc = E->cmd_cells + id * LGX_EVAL_CMD_COLS;
       cc[0] += 1.0;
       cc[4] += (double)cr[3];
       if (st == 1) {
@@ -1206,7 +1212,7 @@ void trace_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_trac
   for (int e = 0; e < N; ++e) {
     if (T->status[e] != 0) continue;
     if (B->reset[e]) {
-      T->status[e] = (B->blew_up && B->blew_up[e]) ? 3 : (B->time_out[e] ? 1 : 2);
+      T->status[e] = episode_end_status(*B, e);
       continue;
     }
     const int cnt = T->count[e];
@@ -1264,7 +1270,7 @@ void gait_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_
   for (int e = 0; e < N; ++e) {
     if (G->status[e] != 0) continue;
     if (B->reset[e]) {
-      G->status[e] = (B->blew_up && B->blew_up[e]) ? 3 : (B->time_out[e] ? 1 : 2);
+      G->status[e] = episode_end_status(*B, e);
       continue;
     }
     float* body = G->body + (size_t)e * LGX_GAIT_BODY_COLS;
@@ -1285,21 +1291,12 @@ void gait_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_
 // written only when it is 0, overflow always is)
 int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G) {
   const int N = P->num_envs, rows = G->cell_rows, cols = G->cell_cols;
-  auto cell_of = [&](int e) -> int64_t {
-    if (G->cell_ids) return (G->cell_ids[e] < 0 || G->cell_ids[e] >= rows * cols) ? -1 : G->cell_ids[e];
-    const int64_t lv = B->terrain_levels ? B->terrain_levels[e] : 0, ty = B->terrain_types ? B->terrain_types[e] : 0;
-    return (lv < 0 || lv >= rows || ty < 0 || ty >= cols) ? -1 : lv * cols + ty;
-  };
-  int bad = 0;
-  for (int e = 0; e < N; ++e) bad += cell_of(e) < 0;
-  *G->overflow = (uint32_t)bad;
-  if (bad) return bad;
-  const size_t nc = (size_t)rows * cols * LGX_GAIT_CELL_COLS;
-  for (size_t i = 0; i < nc; ++i) G->cells[i] = 0.0;
+  if (int bad = reduce_begin(B, G->cell_ids, N, rows, cols, G->overflow, {{G->cells, LGX_GAIT_CELL_COLS}})) return bad;
   for (int e = 0; e < N; ++e) {  // env order: deterministic
     const float* body = G->body + (size_t)e * LGX_GAIT_BODY_COLS;
     if (G->status[e] == 0 || !(body[0] > 0.f)) continue;
-    double* cl = G->cells + (size_t)cell_of(e) * LGX_GAIT_CELL_COLS;
+    const int id = cell_of_env(B->terrain_levels, B->terrain_types, G->cell_ids, e, rows, cols);
+    double* cl = G->cells + (size_t)id * LGX_GAIT_CELL_COLS;
     cl[0] += 1.0;
     for (int k = 0; k < LGX_GAIT_BODY_COLS; ++k) cl[1 + k] += (double)body[k];
     for (int f = 0; f < LGX_MAX_FEET; ++f) {

@@ -132,6 +132,9 @@ class LeggedRobot(BaseTask):
         self._publish_extras()
 
     # ------------------------------------------------------------------ policy evaluation
+    def _zeros(self, *shape, dtype=torch.float32):
+        return torch.zeros(*shape, device=self.device, dtype=dtype)
+
     def _eval_buffers(self):
         """The evaluation's tensors (include/lgx.h lgx_eval_buffers), allocated once so a captured
         loop replays on fixed addresses: eval_acc [N, 8] and eval_status [N] (each env's first
@@ -140,8 +143,8 @@ class LeggedRobot(BaseTask):
         if getattr(self, "_eval", None) is None:
             grid = getattr(self, "terrain_levels", None) is not None
             rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
-            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
-            self.eval_acc = z(self.num_envs, _abi.EVAL_METRICS, dtype=torch.float32)
+            z = self._zeros
+            self.eval_acc = z(self.num_envs, _abi.EVAL_METRICS)
             self.eval_status = z(self.num_envs, dtype=torch.uint8)
             self._eval_cells = z(rows, cols, _abi.EVAL_CELL_COLS, dtype=torch.float64)
             self._eval_overflow = z(1, dtype=torch.int32)
@@ -155,22 +158,28 @@ class LeggedRobot(BaseTask):
         loop replays on fixed addresses: push_cell_ids [N] int32 (the caller writes each env's bin
         in place), push_rec [N, 4] and, after eval_push_cells, cells [rows, cols, 12] and push cells
         [rows, cols, 5]. Pass the result as `ev` to eval_begin / eval_accumulate."""
-        key = (int(rows), int(cols), float(settle_tol))
-        if getattr(self, "_push_eval_key", None) != key:
-            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
-            n = self.num_envs
-            self.push_eval_acc = z(n, _abi.EVAL_METRICS, dtype=torch.float32)
-            self.push_eval_status = z(n, dtype=torch.uint8)
-            self.push_cell_ids = z(n, dtype=torch.int32)
-            self.push_rec = z(n, _abi.EVAL_PUSH_REC, dtype=torch.float32)
-            self._push_eval_cells = z(key[0], key[1], _abi.EVAL_CELL_COLS, dtype=torch.float64)
-            self._push_cells = z(key[0], key[1], _abi.EVAL_PUSH_COLS, dtype=torch.float64)
-            self._push_eval_overflow = z(1, dtype=torch.int32)
-            self._push_eval = self._native.eval_buffers(
-                self.push_eval_acc, self.push_eval_status, self._push_eval_cells, self._push_eval_overflow,
-                cell_ids=self.push_cell_ids, push_rec=self.push_rec, push_cells=self._push_cells, settle_tol=key[2])
-            self._push_eval_key = key
-        return self._push_eval
+        return self._bin_eval_buffers("push", int(rows), int(cols), _abi.EVAL_PUSH_REC, _abi.EVAL_PUSH_COLS,
+                                      settle_tol=float(settle_tol))
+
+    def _bin_eval_buffers(self, p, rows, cols, rec_cols, cell_cols, **tols):
+        """The allocator behind push_eval_buffers (p = "push") and cmd_eval_buffers (p = "cmd"): eval
+        tensors with a free cell key, a per-env record of rec_cols columns and its cells of
+        cell_cols columns, allocated once per (rows, cols, the tolerances). The tensors become the
+        attributes <p>_eval_acc, <p>_eval_status, <p>_cell_ids, <p>_rec (and cmd_switch_step),
+        _<p>_eval_cells, _<p>_cells and _<p>_eval_overflow; returns the lgx_eval_buffers _<p>_eval."""
+        key = (rows, cols) + tuple(tols.values())
+        if getattr(self, f"_{p}_eval_key", None) != key:
+            z, n = self._zeros, self.num_envs
+            acc, status, ids, rec = z(n, _abi.EVAL_METRICS), z(n, dtype=torch.uint8), z(n, dtype=torch.int32), z(n, rec_cols)
+            cells, bins = (z(rows, cols, k, dtype=torch.float64) for k in (_abi.EVAL_CELL_COLS, cell_cols))
+            overflow = z(1, dtype=torch.int32)
+            extra = {"cmd_switch_step": z(n, dtype=torch.int32)} if p == "cmd" else {}
+            ev = self._native.eval_buffers(acc, status, cells, overflow, cell_ids=ids, **extra, **tols,
+                                           **{f"{p}_rec": rec, f"{p}_cells": bins})
+            vars(self).update({f"{p}_eval_acc": acc, f"{p}_eval_status": status, f"{p}_cell_ids": ids, f"{p}_rec": rec,
+                               f"_{p}_eval_cells": cells, f"_{p}_cells": bins, f"_{p}_eval_overflow": overflow,
+                               f"_{p}_eval": ev, f"_{p}_eval_key": key}, **extra)
+        return getattr(self, f"_{p}_eval")
 
     def eval_begin(self, ev=None):
         """lgx_eval_begin: start recording every env's next (first) episode (ev: another set of
@@ -187,13 +196,19 @@ class LeggedRobot(BaseTask):
         [rows, cols, 5]: n, sum of peak tilt, sum of peak tracking error, survivors, sum of the
         survivors' settle steps) float64 on the host. Synchronises. A cell id outside the grid is
         an error."""
-        ev = self._push_eval
-        self._native.eval_reduce(ev, self._stream())
-        bad = int(self._push_eval_overflow.item())
+        return self._reduced_cells("lgx_eval_reduce", self._push_eval, self._push_eval_overflow, "a cell id",
+                                   self._push_eval_cells, self._push_cells)
+
+    def _reduced_cells(self, call, bufs, overflow, what, *cells):
+        """The readers' common part: the native reduce `call` on bufs, the host read of its out-of-grid
+        count (synchronises; any such env is an error that names `what` lay outside the grid), then
+        the cell tensors cloned to the host."""
+        getattr(self._native, call[len("lgx_"):])(bufs, self._stream())
+        bad = int(overflow.item())
         if bad:
-            raise _native.LgxError(f"lgx_eval_reduce: {bad} envs have a cell id outside the "
-                                   f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
-        return self._push_eval_cells.cpu().clone(), self._push_cells.cpu().clone()
+            raise _native.LgxError(f"{call}: {bad} envs have {what} outside the {bufs.cell_rows} x {bufs.cell_cols} "
+                                   f"cell grid (cells not written)")
+        return tuple(c.cpu().clone() for c in cells)
 
     def cmd_eval_buffers(self, rows, cols, settle_tol, yaw_tol, steady_after):
         """A set of evaluation tensors of its own for the command test (lgx_eval_buffers with
@@ -203,49 +218,24 @@ class LeggedRobot(BaseTask):
         the episode step its record counts from in place; <= 0: no record), cmd_rec [N, 8] and,
         after eval_command_cells, cells [rows, cols, 12] and command cells [rows, cols, 9]. Pass
         the result as `ev` to eval_begin / eval_accumulate."""
-        key = (int(rows), int(cols), float(settle_tol), float(yaw_tol), int(steady_after))
-        if getattr(self, "_cmd_eval_key", None) != key:
-            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
-            n = self.num_envs
-            self.cmd_eval_acc = z(n, _abi.EVAL_METRICS, dtype=torch.float32)
-            self.cmd_eval_status = z(n, dtype=torch.uint8)
-            self.cmd_cell_ids = z(n, dtype=torch.int32)
-            self.cmd_switch_step = z(n, dtype=torch.int32)
-            self.cmd_rec = z(n, _abi.EVAL_CMD_REC, dtype=torch.float32)
-            self._cmd_eval_cells = z(key[0], key[1], _abi.EVAL_CELL_COLS, dtype=torch.float64)
-            self._cmd_cells = z(key[0], key[1], _abi.EVAL_CMD_COLS, dtype=torch.float64)
-            self._cmd_eval_overflow = z(1, dtype=torch.int32)
-            self._cmd_eval = self._native.eval_buffers(
-                self.cmd_eval_acc, self.cmd_eval_status, self._cmd_eval_cells, self._cmd_eval_overflow,
-                cell_ids=self.cmd_cell_ids, cmd_switch_step=self.cmd_switch_step, cmd_rec=self.cmd_rec,
-                cmd_cells=self._cmd_cells, settle_tol=key[2], yaw_tol=key[3], steady_after=key[4])
-            self._cmd_eval_key = key
-        return self._cmd_eval
+        return self._bin_eval_buffers("cmd", int(rows), int(cols), _abi.EVAL_CMD_REC, _abi.EVAL_CMD_COLS,
+                                      settle_tol=float(settle_tol), yaw_tol=float(yaw_tol),
+                                      steady_after=int(steady_after))
 
     def eval_command_cells(self):
         """lgx_eval_reduce on the command test's buffers, then (cells [rows, cols, 12], command
         cells [rows, cols, 9]: n, survivors, the survivors' sums of linear and yaw settle steps, sum
         of peak tilt, the survivors' sums of steady samples and of achieved vx, vy, yaw rate) float64
         on the host. Synchronises. A cell id outside the grid is an error."""
-        ev = self._cmd_eval
-        self._native.eval_reduce(ev, self._stream())
-        bad = int(self._cmd_eval_overflow.item())
-        if bad:
-            raise _native.LgxError(f"lgx_eval_reduce: {bad} envs have a cell id outside the "
-                                   f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
-        return self._cmd_eval_cells.cpu().clone(), self._cmd_cells.cpu().clone()
+        return self._reduced_cells("lgx_eval_reduce", self._cmd_eval, self._cmd_eval_overflow, "a cell id",
+                                   self._cmd_eval_cells, self._cmd_cells)
 
     def eval_cells(self):
         """lgx_eval_reduce, then the cells [rows, cols, 12] float64 on the host: n_envs, n_timeout,
         n_fall, n_blowup and the sums of the 8 record columns over each cell's finished envs.
         Synchronises. An env whose terrain level / type lies outside the grid is an error."""
-        ev = self._eval_buffers()
-        self._native.eval_reduce(ev, self._stream())
-        bad = int(self._eval_overflow.item())
-        if bad:
-            raise _native.LgxError(f"lgx_eval_reduce: {bad} envs have a terrain level / type outside the "
-                                   f"{ev.cell_rows} x {ev.cell_cols} cell grid (cells not written)")
-        return self._eval_cells.cpu().clone()
+        return self._reduced_cells("lgx_eval_reduce", self._eval_buffers(), self._eval_overflow,
+                                   "a terrain level / type", self._eval_cells)[0]
 
     # ------------------------------------------------------------------ flight recorder
     def trace_buffers(self, depth):
@@ -263,9 +253,9 @@ class LeggedRobot(BaseTask):
         if not hasattr(self, "_traces"):
             self._traces = {}  # depth -> lgx_trace_buffers: a loop captured at a depth keeps its rings
         if depth not in self._traces:
-            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
+            z = self._zeros
             self._traces[depth] = self._native.trace_buffers(
-                z(self.num_envs, depth, _abi.TRACE_COLS, dtype=torch.float32), z(self.num_envs, dtype=torch.int32),
+                z(self.num_envs, depth, _abi.TRACE_COLS), z(self.num_envs, dtype=torch.int32),
                 z(self.num_envs, dtype=torch.uint8))
         self._trace = self._traces[depth]  # the current recorder: trace_begin / _record / _gather use it
         self.trace_ring, self.trace_count, self.trace_status = self._trace._keep
@@ -320,11 +310,9 @@ class LeggedRobot(BaseTask):
         if not hasattr(self, "_gaits"):
             self._gaits = {}  # key -> lgx_gait_buffers (which keeps its tensors, cell_ids included)
         if key not in self._gaits:
-            z = lambda *s, dtype: torch.zeros(*s, device=self.device, dtype=dtype)  # noqa: E731
-            n = self.num_envs
+            z, n = self._zeros, self.num_envs
             self._gaits[key] = self._native.gait_buffers(
-                z(n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS, dtype=torch.float32),
-                z(n, _abi.GAIT_BODY_COLS, dtype=torch.float32), z(n, dtype=torch.uint8),
+                z(n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS), z(n, _abi.GAIT_BODY_COLS), z(n, dtype=torch.uint8),
                 z(key[0], key[1], _abi.GAIT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32), cell_ids=cell_ids)
         self._gait = self._gaits[key]
         self.gait_foot, self.gait_body, self.gait_status, self._gait_cells, self._gait_overflow = self._gait._keep[:5]
@@ -348,13 +336,8 @@ class LeggedRobot(BaseTask):
         """lgx_gait_reduce, then the cells [rows, cols, 61] float64 on the host: the number of
         finished envs with samples, the sums of their 12 body columns and of columns 4..15 of each
         foot. Synchronises. An env whose cell lies outside the grid is an error."""
-        gb = self._gait_buffers()
-        self._native.gait_reduce(gb, self._stream())
-        bad = int(self._gait_overflow.item())
-        if bad:
-            raise _native.LgxError(f"lgx_gait_reduce: {bad} envs have a terrain level / type (or cell id) outside "
-                                   f"the {gb.cell_rows} x {gb.cell_cols} cell grid (cells not written)")
-        return self._gait_cells.cpu().clone()
+        return self._reduced_cells("lgx_gait_reduce", self._gait_buffers(), self._gait_overflow,
+                                   "a terrain level / type (or cell id)", self._gait_cells)[0]
 
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""
@@ -507,7 +490,7 @@ class LeggedRobot(BaseTask):
         bound once to the native env."""
         n, d, nb, na = self.num_envs, self.num_dof, self.num_bodies, self.num_actions
         dev = self.device
-        z = lambda *s, dtype=torch.float: torch.zeros(*s, device=dev, dtype=dtype)  # noqa: E731
+        z = self._zeros
         self.root_states = z(n, 13)
         self.root_states[:] = self.base_init_state
         self.root_states[:, :3] += self.env_origins

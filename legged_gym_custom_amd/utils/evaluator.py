@@ -254,12 +254,17 @@ class PolicyEvaluator:
         into; default: the plain evaluation's), gait_record in a gait run and trace_record in a
         traced run."""
         with torch.no_grad():
-            self.env.step(self.act())
-            self.env.eval_accumulate(ev)
-            if self._gait:
-                self.env.gait_record()
-            if self._trace_depth is not None:
-                self.env.trace_record()
+            self._body(ev)
+
+    def _body(self, ev):
+        """The loop body, written once for the eager loop (step) and the capture (_capture)."""
+        env = self.env
+        env.step(self.act())
+        env.eval_accumulate(ev)
+        if self._gait:
+            env.gait_record()
+        if self._trace_depth is not None:
+            env.trace_record()
 
     def begin(self, ev=None):
         """Reset every env and start recording. The env's step and reset-call counters (the keys
@@ -301,12 +306,7 @@ class PolicyEvaluator:
         g = torch.cuda.CUDAGraph()
         with torch.inference_mode(False), torch.no_grad(), \
                 torch.cuda.graph(g, capture_error_mode=self.alg.capture_mode()):
-            env.step(self.act())
-            env.eval_accumulate(ev)
-            if self._gait:
-                env.gait_record()
-            if self._trace_depth is not None:
-                env.trace_record()
+            self._body(ev)
         env.common_step_counter = csc  # host mirror (capture advanced it, the device did not)
         return g
 
@@ -355,40 +355,77 @@ class PolicyEvaluator:
                 env.set_motor_strength(motor_strength)  # (the first one allocates: refused once a loop is captured)
                 if not had:
                     saved.append((env.motor_strengths, torch.ones_like(env.motor_strengths)))
-            return self._run(num_steps, graph)
+            cells, gcells, head, rates = self._drive("_graph", (), num_steps, graph, env.eval_cells)
+            out = self.report(cells, head["num_steps"], rates["wall_s"], head["graph"])
+            self._attach_gait(gcells, out["total"], [cell for row in out["cells"] for cell in row])
+            return out
         finally:
             for buf, old in saved:
                 buf.copy_(old)
 
-    def _run(self, num_steps, graph):
+    def _drive(self, slot, key, num_steps, graph, read_cells, prepare=None, started=None, cleanup=None):
+        """The run of all three modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
+        "_cmd_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
+        the trace depth and the gait flag are added: the loop is captured when there is no graph or
+        the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
+        buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
+        always, when the run ends or fails. read_cells(): the mode's reduce and host read
+        (synchronises), one tensor or a tuple with the [rows, cols, 12] cells first.
+        Returns (what read_cells returned, the gait cells or None, the report's common head, its
+        wall_s / env_steps_per_s tail) and sets last_cells, last_trace_depth and last_gait_cells."""
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
-        gkey = (self._trace_depth, self._gait)
-        if use_graph and (self._graph is None or self._graph_key != gkey):
-            self._graph, self._graph_key = self._capture(), gkey
-        self.begin()
-        t0 = self._loop(steps, self._graph if use_graph else None, None)
-        cells = env.eval_cells()  # reduce + the host read (synchronises)
-        gcells = env.gait_cells() if self._gait else None
-        wall = time.perf_counter() - t0
-        self.last_trace_depth = self._trace_depth
-        self.last_cells = cells  # [rows, cols, 12] float64, as lgx_eval_reduce wrote them
-        self.last_gait_cells = gcells  # [rows, cols, 61] float64, as lgx_gait_reduce wrote them
-        out = self.report(cells, steps, wall, use_graph)
-        if gcells is not None:
-            g = self._gait_report(gcells)
-            out["total"]["gait"] = g(gcells.reshape(-1, gcells.shape[2]).sum(0))
-            for r, row in enumerate(out["cells"]):
-                for c, cell in enumerate(row):
-                    cell["gait"] = g(gcells[r, c])
-        return out
+        gkey = key + (self._trace_depth, self._gait)
+        try:
+            ev = prepare() if prepare else None
+            if use_graph and (getattr(self, slot) is None or getattr(self, slot + "_key") != gkey):
+                setattr(self, slot, self._capture(ev))
+                setattr(self, slot + "_key", gkey)
+            self.begin(ev)
+            if started:
+                started()
+            t0 = self._loop(steps, getattr(self, slot) if use_graph else None, ev)
+            cells = read_cells()
+            gcells = env.gait_cells() if self._gait else None
+            wall = time.perf_counter() - t0
+        finally:
+            if cleanup:
+                cleanup()
+        self.last_cells = cells[0] if isinstance(cells, tuple) else cells  # as lgx_eval_reduce wrote them
+        self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells  # ([rows, cols, 61] float64)
+        return cells, gcells, self._head(steps, use_graph), self._rates(steps, wall)
 
-    def _gait_report(self, gcells):
-        """gait_cell_report for this env's time step and feet."""
+    def _head(self, steps, graph):
+        return {"policy": self.policy, "num_envs": int(self.env.num_envs), "num_steps": steps, "dt": float(self.env.dt),
+                "nominal_mass": self.mass, "graph": graph}
+
+    def _rates(self, steps, wall):
+        return {"wall_s": wall, "env_steps_per_s": steps * self.env.num_envs / wall if wall > 0 else None}
+
+    def _attach_gait(self, gcells, total, bins):
+        """The "gait" entry (gait_cell_report) of the total and of every bin; bins: the report's cells
+        or bins flat, in the order of gcells' cells. Nothing without a gait record."""
+        if gcells is None:
+            return
         env = self.env
         dt, names = float(env.dt), [env.body_names[i] for i in env.feet_indices.tolist()]
-        return lambda row: gait_cell_report(row, dt, names)
+        flat = gcells.reshape(-1, gcells.shape[2])
+        total["gait"] = gait_cell_report(flat.sum(0), dt, names)
+        for row, b in zip(flat, bins):
+            b["gait"] = gait_cell_report(row, dt, names)
+
+    def _switch_step(self, at_s, test):
+        """at_s (seconds into the episode) as an episode step of the push / command test."""
+        at, last = float(at_s), int(self.env.max_episode_length)
+        step = int(round(at / float(self.env.dt))) if math.isfinite(at) else -1
+        if not 0 < step < last:
+            raise ValueError(f"{test}: at_s = {at_s} s is step {step}, outside 0 < step < max_episode_length = {last}")
+        return step
+
+    def _bins(self, count):
+        """Each env's bin of `count`: randperm(num_envs, seeded with env.seed) % count."""
+        return torch.randperm(self.env.num_envs, generator=torch.Generator().manual_seed(int(self.env.seed))) % count
 
     def gait_records(self):
         """The per-env gait records of the last run (it must have been one with gait=True), numpy
@@ -450,52 +487,33 @@ class PolicyEvaluator:
             raise ValueError(f"push test: need at least one finite speed >= 0 and one direction (got {speeds}, {directions})")
         if not (math.isfinite(float(settle_tol)) and float(settle_tol) >= 0.0):
             raise ValueError(f"push test: settle_tol must be finite and >= 0 (got {settle_tol})")
-        at = float(at_s)
-        step = int(round(at / float(env.dt))) if math.isfinite(at) else -1
-        if not 0 < step < int(env.max_episode_length):
-            raise ValueError(f"push test: at_s = {at_s} s is step {step}, outside 0 < step < max_episode_length = "
-                             f"{int(env.max_episode_length)}")
-        n = env.num_envs
-        bins = torch.randperm(n, generator=torch.Generator().manual_seed(int(env.seed))) % (S * D)
+        step = self._switch_step(at_s, "push test")
+        bins = self._bins(S * D)
         theta = 2.0 * math.pi * (bins % D).double() / D
         v = torch.tensor(speeds, dtype=torch.float64)[bins // D]
         dvel = torch.stack([v * torch.cos(theta), v * torch.sin(theta), torch.zeros_like(v)], 1).float()
-        steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
-        use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         key = (S, D, float(settle_tol))
-        gkey = key + (self._trace_depth, self._gait)
-        try:
+
+        def prepare():
             env.set_push_schedule(0, dvel)  # (the first one allocates: refused once a loop is captured)
             ev = env.push_eval_buffers(*key)
             env.push_cell_ids.copy_(bins.to(torch.int32))
             if self._gait:
                 env.gait_buffers(S, D, env.push_cell_ids)  # the bin is the cell key
-            if use_graph and (self._push_graph is None or self._push_graph_key != gkey):
-                self._push_graph, self._push_graph_key = self._capture(ev), gkey
-            self.begin(ev)
-            env.set_push_schedule(step, dvel)  # after begin: its reset ends with an env step of its own
-            t0 = self._loop(steps, self._push_graph if use_graph else None, ev)
-            cells, pcells = env.eval_push_cells()  # reduce + the host read (synchronises)
-            gcells = env.gait_cells() if self._gait else None
-            wall = time.perf_counter() - t0
-        finally:
-            env.clear_push_schedule()
-        self.last_cells, self.last_push_cells, self.last_push_bins = cells, pcells, bins
-        self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells
-        dt, w = float(env.dt), self.mass * self.gravity
+            return ev
+
+        (cells, pcells), gcells, head, rates = self._drive(
+            "_push_graph", key, num_steps, graph, env.eval_push_cells, prepare,
+            lambda: env.set_push_schedule(step, dvel),  # after begin: its reset ends with an env step of its own
+            env.clear_push_schedule)
+        self.last_push_cells, self.last_push_bins = pcells, bins
+        dt, w = head["dt"], self.mass * self.gravity
         both = lambda c, p: {**cell_report(c, dt, w), **push_cell_report(p, dt)}  # noqa: E731
-        out = {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
-               "graph": use_graph, "speeds": speeds, "directions_deg": [360.0 * d / D for d in range(D)],
+        out = {**head, "speeds": speeds, "directions_deg": [360.0 * d / D for d in range(D)],
                "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
                "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
-               "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)],
-               "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
-        if gcells is not None:
-            g = self._gait_report(gcells)
-            out["total"]["gait"] = g(gcells.reshape(-1, gcells.shape[2]).sum(0))
-            for s in range(S):
-                for d in range(D):
-                    out["bins"][s][d]["gait"] = g(gcells[s, d])
+               "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)], **rates}
+        self._attach_gait(gcells, out["total"], [b for row in out["bins"] for b in row])
         return out
 
     # ------------------------------------------------------------------ command response
@@ -539,21 +557,15 @@ class PolicyEvaluator:
         for name, tol in (("settle_tol", settle_tol), ("yaw_tol", yaw_tol), ("steady_after_s", steady_after_s)):
             if not (math.isfinite(float(tol)) and float(tol) >= 0.0):
                 raise ValueError(f"command test: {name} must be finite and >= 0 (got {tol})")
-        dt, at = float(env.dt), float(at_s)
-        step = int(round(at / dt)) if math.isfinite(at) else -1
-        if not 0 < step < int(env.max_episode_length):
-            raise ValueError(f"command test: at_s = {at_s} s is step {step}, outside 0 < step < max_episode_length = "
-                             f"{int(env.max_episode_length)}")
+        dt, step = float(env.dt), self._switch_step(at_s, "command test")
         steady = int(round(float(steady_after_s) / dt))
         n, nx, ny, nw = env.num_envs, len(vx), len(vy), len(yaw)
-        bins = torch.randperm(n, generator=torch.Generator().manual_seed(int(env.seed))) % (nx * ny * nw)
+        bins = self._bins(nx * ny * nw)
         grid = torch.tensor([[a, b, c, 0.0] for a in vx for b in vy for c in yaw], dtype=torch.float32)
         values = torch.stack([torch.tensor(start + [0.0], dtype=torch.float32).expand(n, 4), grid[bins]], 1)
-        steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
-        use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
         key = (nx, ny * nw, float(settle_tol), float(yaw_tol), steady)
-        gkey = key + (self._trace_depth, self._gait)
-        try:
+
+        def prepare():
             # before begin: its reset sees segment 0 (the first call allocates: refused once a loop is captured)
             env.set_command_schedule([0, step], values)
             ev = env.cmd_eval_buffers(*key)
@@ -561,35 +573,21 @@ class PolicyEvaluator:
             env.cmd_switch_step.fill_(step)
             if self._gait:
                 env.gait_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
-            if use_graph and (self._cmd_graph is None or self._cmd_graph_key != gkey):
-                self._cmd_graph, self._cmd_graph_key = self._capture(ev), gkey
-            self.begin(ev)
-            t0 = self._loop(steps, self._cmd_graph if use_graph else None, ev)
-            cells, ccells = env.eval_command_cells()  # reduce + the host read (synchronises)
-            gcells = env.gait_cells() if self._gait else None
-            wall = time.perf_counter() - t0
-        finally:
-            env.clear_command_schedule()
-        self.last_cells, self.last_cmd_cells, self.last_cmd_bins = cells, ccells, bins
-        self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells
+            return ev
+
+        (cells, ccells), gcells, head, rates = self._drive("_cmd_graph", key, num_steps, graph, env.eval_command_cells,
+                                                           prepare, cleanup=env.clear_command_schedule)
+        self.last_cmd_cells, self.last_cmd_bins = ccells, bins
         w = self.mass * self.gravity
         both = lambda c, p, cmd: {**cell_report(c, dt, w), **command_cell_report(p, dt, cmd)}  # noqa: E731
         total = both(cells.reshape(-1, cells.shape[2]).sum(0), ccells.reshape(-1, ccells.shape[2]).sum(0), (0.0, 0.0, 0.0))
         del total["achieved"], total["gain"]  # (means over different commands say nothing)
-        out = {"policy": self.policy, "num_envs": int(n), "num_steps": steps, "dt": dt, "nominal_mass": self.mass,
-               "graph": use_graph, "vx": vx, "vy": vy, "yaw": yaw, "start": start, "switch_step": step,
+        out = {**head, "vx": vx, "vy": vy, "yaw": yaw, "start": start, "switch_step": step,
                "switch_at_s": step * dt, "steady_after": steady, "settle_tol": float(settle_tol),
                "yaw_tol": float(yaw_tol), "total": total,
                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
-                          for iw in range(nw)] for iy in range(ny)] for ix in range(nx)],
-               "wall_s": wall, "env_steps_per_s": steps * n / wall if wall > 0 else None}
-        if gcells is not None:
-            g = self._gait_report(gcells)
-            total["gait"] = g(gcells.reshape(-1, gcells.shape[2]).sum(0))
-            for ix in range(nx):
-                for iy in range(ny):
-                    for iw in range(nw):
-                        out["bins"][ix][iy][iw]["gait"] = g(gcells[ix, iy * nw + iw])
+                          for iw in range(nw)] for iy in range(ny)] for ix in range(nx)], **rates}
+        self._attach_gait(gcells, total, [b for plane in out["bins"] for row in plane for b in row])
         return out
 
     # ------------------------------------------------------------------ flight recorder
@@ -638,13 +636,11 @@ class PolicyEvaluator:
         rows, cols = int(cells.shape[0]), int(cells.shape[1])
         assert cells.shape[2] == _abi.EVAL_CELL_COLS
         total = cells.reshape(-1, _abi.EVAL_CELL_COLS).sum(0)
-        out = {"policy": self.policy, "num_envs": int(env.num_envs), "num_steps": steps, "dt": dt,
-               "nominal_mass": self.mass, "graph": graph, "terrain_levels": rows, "terrain_types": cols,
+        out = {**self._head(steps, graph), "terrain_levels": rows, "terrain_types": cols,
                "action_delay_substeps": _min_max(getattr(env, "action_delay_substeps", None), int),
                "motor_strength": _min_max(getattr(env, "motor_strengths", None), float),
                "total": cell_report(total, dt, w),
                "cells": [[cell_report(cells[r, c], dt, w) for c in range(cols)] for r in range(rows)]}
         if wall is not None and steps:
-            out["wall_s"] = wall
-            out["env_steps_per_s"] = steps * env.num_envs / wall if wall > 0 else None
+            out.update(self._rates(steps, wall))
         return out

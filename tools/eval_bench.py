@@ -9,7 +9,8 @@ networks (the timing does not depend on the weights), graph replay and the eager
   python tools/eval_bench.py --stats DIR/..._kernel_stats.csv --merge FILE   # kernel times into FILE
 
 Times are host clocks around runs that end in the evaluator's host read (a device synchronise);
---profile runs one short eager evaluation only (kernel times come from the trace, not from here)."""
+--profile runs one short eager evaluation only, and one short eager command test with --cmd_vx (kernel
+times come from the trace, not from here)."""
 import argparse
 import csv
 import json
@@ -20,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 KERNELS = {"eval_accumulate_kernel": "eval_accumulate_us", "eval_reduce_kernel": "eval_reduce_us",
+           "eval_cmd_reduce_kernel": "eval_cmd_reduce_us",
            "env_step_kernel": "env_step_us", "act_kernel(lgx_s8_act_args": "act_us",
            "trace_record_kernel": "trace_record_us", "trace_gather_kernel": "trace_gather_us",
            "gait_record_kernel": "gait_record_us", "gait_reduce_kernel": "gait_reduce_us"}
@@ -85,6 +87,8 @@ def main():
         r = ev.run(a.steps or 200, graph=False, trace_depth=a.trace_depth, gait=a.gait)
         if a.trace_depth:
             ev.traces("falls", 16)
+        if a.cmd_vx:  # (the only run with eval_cmd_reduce_kernel)
+            ev.run_command_test(a.cmd_vx, vy=a.cmd_vy, yaw=a.cmd_yaw, num_steps=a.steps or 200, graph=False)
         print(json.dumps({"profiled_steps": r["num_steps"], "total": r["total"]}))
         return
     ev.run(20)  # warm both paths (the capture included)
@@ -100,16 +104,16 @@ def main():
         rates.update(cmd_graph=[], cmd_eager=[])
         cmd(20, True)
         cmd(20, False)
-    traced = (lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
-    if a.trace_depth:
-        rates.update(trace_graph=[], trace_eager=[])
-        traced(20, True)
-        traced(20, False)
     gaited = (lambda steps, graph: ev.run(steps, graph, gait=True))
     if a.gait:
         rates.update(gait_graph=[], gait_eager=[])
         gaited(20, True)
         gaited(20, False)
+    traced = (lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
+    if a.trace_depth:  # (the last mode: traces() below reads the last timed run's rings)
+        rates.update(trace_graph=[], trace_eager=[])
+        traced(20, True)
+        traced(20, False)
     gr = None
     for _ in range(a.repeats):
         for mode in rates:
