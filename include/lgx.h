@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 12
+#define LGX_ABI_VERSION 13
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -57,6 +57,9 @@ extern "C" {
 #define LGX_GAIT_FOOT_COLS 16     /* per-env per-foot gait record columns (lgx_gait_buffers.foot) */
 #define LGX_GAIT_BODY_COLS 12     /* per-env gait record columns (lgx_gait_buffers.body) */
 #define LGX_GAIT_CELL_COLS 61     /* per-cell gait columns: 1 + 12 + LGX_MAX_FEET * 12 (lgx_gait_buffers.cells) */
+#define LGX_JOINT_COLS 16         /* per-env per-joint record columns (lgx_joint_buffers.joint) */
+#define LGX_JOINT_BODY_COLS 4     /* per-env record columns (lgx_joint_buffers.body) */
+#define LGX_JOINT_CELL_COLS 246   /* per-cell joint columns: 6 + LGX_MAX_DOF * 20 (lgx_joint_buffers.cells) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -649,6 +652,72 @@ int lgx_gait_record(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream);
  * bit-identical cells. A cell outside the grid is never used as an index: such envs are counted in
  * *overflow, and cells are then left unwritten (the host backend fails the call instead). */
 int lgx_gait_reduce(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream);
+/* ABI 13. Joint-load record: what the policy asks of each motor (torque saturation, heat, work,
+ * speed and range use, action rate and clipping), per env and joint for the env's FIRST episode since
+ * lgx_joint_begin (the rule of lgx_eval_buffers.status), then reduced per cell. Stand-alone like the
+ * flight recorder and the gait record: buffers and a status array of its own, one launch per step;
+ * lgx_eval_buffers and the step are untouched. The reference has no counterpart. Buffers are the
+ * caller's, in the env's memory space (device, or host for device < 0). */
+typedef struct lgx_joint_buffers {
+  float* joint;      /* [N, LGX_MAX_DOF, LGX_JOINT_COLS] per-env per-joint record, 16-byte aligned, columns below */
+  float* body;       /* [N, LGX_JOINT_BODY_COLS] per-env record, 16-byte aligned */
+  uint8_t* status;   /* [N] 0 recording, 1 timed out, 2 fell, 3 blew up: the lgx_eval_buffers.status rule */
+  double* cells;     /* [cell_rows*cell_cols, LGX_JOINT_CELL_COLS], written by lgx_joint_reduce */
+  uint32_t* overflow;/* [1] written by lgx_joint_reduce, as lgx_eval_buffers.overflow */
+  int32_t cell_rows, cell_cols;
+  const int32_t* cell_ids; /* [N] optional: the same meaning and range rule as lgx_gait_buffers.cell_ids */
+} lgx_joint_buffers;
+int64_t lgx_sizeof_joint_buffers(void);
+/* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph. Each
+ * refuses (naming the culprit) a NULL joint, body, status or overflow (lgx_joint_reduce: also cells), a
+ * joint or body that is not 16-byte aligned (the kernel moves a joint's record as four 16-byte
+ * accesses and body as one), cell_rows or cell_cols < 1 or their product above 2^20, an unbound
+ * torques, dof_state, actions, reset or time_out, and a num_dof outside [0, LGX_MAX_DOF]; blew_up,
+ * terrain_levels and terrain_types are optional.
+ * lgx_joint_begin: zero joint, body, status and overflow. */
+int lgx_joint_begin(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream);
+/* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
+ * status[e] == 0:
+ *   reset[e]: status[e] = 3 if blew_up is bound and set, else 1 if time_out[e], else 2; no sample.
+ *   else one sample, in fp32 without contraction. first = (body[e][0] == 0), read before anything is
+ *   written; dt = params.dt. For joint j < num_dof: tau = torques[e][j], q = dof_state[e][j][0],
+ *   qd = dof_state[e][j][1], p = tau*qd, a = actions[e][j] (0 for j >= num_actions),
+ *   L = torque_limits[j], V = dof_vel_limits[j], lo, hi = dof_pos_limits[j], C = clip_actions,
+ *   r = joint[e][j]. Joint columns:
+ *     0   = a (after column 12 has used the old value)   state: the last sample's action
+ *     1   += fabsf(tau) >= L                             torque-saturated samples
+ *     2   += tau*tau                                     for the RMS torque (heat)
+ *     3   = max(r3, fabsf(tau))                          peak torque
+ *     4   += fmaxf(p, 0)*dt                              positive work, J
+ *     5   += fmaxf(-p, 0)*dt                             negative (braking) work, J
+ *     6   = max(r6, fabsf(p))                            peak mechanical power
+ *     7   = max(r7, fabsf(qd))                           peak speed
+ *     8   += fabsf(qd) > V                               samples above the speed limit
+ *     9   += (q < lo || q > hi)                          samples outside the soft position limits
+ *     10  = first ? q : min(r10, q)                      lowest angle used
+ *     11  = first ? q : max(r11, q)                      highest angle used
+ *     12  += first ? 0 : (a - r0)*(a - r0)               action rate
+ *     13  += fabsf(a) >= C                               samples with the action at its clip
+ *     14  += p < 0                                       braking samples
+ *     15  += fabsf(qd)                                   for the mean speed
+ *   Joint slots j >= num_dof stay zero.
+ *   Body columns: body[0] += 1 (samples); body[1] = max(body[1], P), the peak total power, P the sum
+ *   of s_j = fabsf(p_j) over 16 slots (slots >= num_dof zero) by the fixed pairwise tree
+ *   (((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)))+(((s8+s9)+(s10+s11))+((s12+s13)+(s14+s15))) (what a four-stage
+ *   xor butterfly computes on every lane); body[2] += any joint met column 1's condition in this
+ *   sample; body[3] += any joint met column 9's condition in this sample.
+ * Envs with status != 0 are never written again. */
+int lgx_joint_record(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream);
+/* cells[cell], over the cell's finished envs (status != 0) with body[0] > 0, the cell being
+ * cell_ids[e] if set, else terrain_levels[e] * cell_cols + terrain_types[e] (cell 0 for an unbound
+ * one): [0] = the number of such envs, [1..4] = sums of body[0..3], [5] = max of body[1],
+ * [6 + 20 j + k], k = 0..14 = sums of joint j's columns 1 + k, [6 + 20 j + 15..17] = max of its columns
+ * 3, 6, 7, [6 + 20 j + 18] = min of column 10, [6 + 20 j + 19] = max of column 11. A cell with no such
+ * env is all zero. The sums: fp64, the fixed tree of lgx_eval_reduce, no floating-point atomics: two
+ * calls on the same records give bit-identical cells; the maxima and minima are order-independent,
+ * hence exact. A cell outside the grid is never used as an index: such envs are counted in
+ * *overflow, and cells are then left unwritten (the host backend fails the call instead). */
+int lgx_joint_reduce(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream);
 const char* lgx_last_error(const lgx_env* env);
 void lgx_destroy(lgx_env* env);
 

@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -31,6 +31,9 @@ TRACE_COLS = 76      # columns of a flight-recorder row (lgx_trace_buffers.ring)
 GAIT_FOOT_COLS = 16  # per-env per-foot gait record columns (lgx_gait_buffers.foot)
 GAIT_BODY_COLS = 12  # per-env gait record columns (lgx_gait_buffers.body)
 GAIT_CELL_COLS = 61  # per-cell gait columns: 1 + 12 + MAX_FEET * 12 (lgx_gait_buffers.cells)
+JOINT_COLS = 16      # per-env per-joint record columns (lgx_joint_buffers.joint)
+JOINT_BODY_COLS = 4  # per-env record columns (lgx_joint_buffers.body)
+JOINT_CELL_COLS = 246  # per-cell joint columns: 6 + MAX_DOF * 20 (lgx_joint_buffers.cells)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -171,8 +174,15 @@ class GaitBuffers(C.Structure):
                 ("cell_cols", i32), ("cell_ids", P)]
 
 
+class JointBuffers(C.Structure):
+    """lgx_joint_buffers (ABI 13): the joint-load record's per-env per-joint records and per-cell sums."""
+    _fields_ = [("joint", P), ("body", P), ("status", P), ("cells", P), ("overflow", P), ("cell_rows", i32),
+                ("cell_cols", i32), ("cell_ids", P)]
+
+
 STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buffers,
-           "lgx_eval_buffers": EvalBuffers, "lgx_trace_buffers": TraceBuffers, "lgx_gait_buffers": GaitBuffers}
+           "lgx_eval_buffers": EvalBuffers, "lgx_trace_buffers": TraceBuffers, "lgx_gait_buffers": GaitBuffers,
+           "lgx_joint_buffers": JointBuffers}
 SIZEOF = {"lgx_sizeof_" + name[len("lgx_"):]: name for name in STRUCTS}  # sizeof export -> typedef
 
 CONSTANTS = {
@@ -186,6 +196,7 @@ CONSTANTS = {
     "LGX_CMD_SEGMENTS": CMD_SEGMENTS, "LGX_EVAL_CMD_REC": EVAL_CMD_REC, "LGX_EVAL_CMD_COLS": EVAL_CMD_COLS,
     "LGX_TRACE_COLS": TRACE_COLS,
     "LGX_GAIT_FOOT_COLS": GAIT_FOOT_COLS, "LGX_GAIT_BODY_COLS": GAIT_BODY_COLS, "LGX_GAIT_CELL_COLS": GAIT_CELL_COLS,
+    "LGX_JOINT_COLS": JOINT_COLS, "LGX_JOINT_BODY_COLS": JOINT_BODY_COLS, "LGX_JOINT_CELL_COLS": JOINT_CELL_COLS,
     "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
     "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
     **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},
@@ -216,6 +227,9 @@ SIGNATURES = {
     "lgx_gait_begin": (cint, (P, P, P)),
     "lgx_gait_record": (cint, (P, P, P)),
     "lgx_gait_reduce": (cint, (P, P, P)),
+    "lgx_joint_begin": (cint, (P, P, P)),
+    "lgx_joint_record": (cint, (P, P, P)),
+    "lgx_joint_reduce": (cint, (P, P, P)),
     "lgx_last_error": (C.c_char_p, (P,)),
     "lgx_destroy": (None, (P,)),
 }

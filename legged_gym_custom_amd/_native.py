@@ -227,6 +227,35 @@ class NativeEnv:
         """lgx_gait_reduce: records -> cells (and the out-of-grid count in gb.overflow)."""
         self._check(self._L.lgx_gait_reduce(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_reduce")
 
+    def joint_buffers(self, joint, body, status, cells, overflow, cell_ids=None):
+        """lgx_joint_buffers (ABI 13) over the given tensors: joint [N, 12, 16] fp32, body [N, 4] fp32,
+        status [N] uint8, cells [rows, cols, 246] float64, overflow [1] int32 and, optional, cell_ids
+        [N] int32 (the free cell key), all in the env's memory space."""
+        n = self.params.num_envs
+        if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.JOINT_CELL_COLS):
+            raise LgxError(f"joint buffer cells must be [rows, cols, {_abi.JOINT_CELL_COLS}]")
+        jb = _abi.JointBuffers()
+        self._fill(jb, "joint buffer", [
+            ("joint", joint, (n, _abi.MAX_DOF, _abi.JOINT_COLS), "float32", True),
+            ("body", body, (n, _abi.JOINT_BODY_COLS), "float32", True), ("status", status, (n,), "uint8", True),
+            ("cells", cells, None, "float64", True), ("overflow", overflow, (1,), "int32", True),
+            ("cell_ids", cell_ids, (n,), "int32", False)])
+        jb.cell_rows, jb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
+        jb._keep = (joint, body, status, cells, overflow, cell_ids)
+        return jb
+
+    def joint_begin(self, jb, stream):
+        """lgx_joint_begin: zero the records, the statuses and the overflow count (jb: joint_buffers(...))."""
+        self._check(self._L.lgx_joint_begin(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_begin")
+
+    def joint_record(self, jb, stream):
+        """lgx_joint_record: one sample per recording env from the step just run."""
+        self._check(self._L.lgx_joint_record(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_record")
+
+    def joint_reduce(self, jb, stream):
+        """lgx_joint_reduce: records -> cells (and the out-of-grid count in jb.overflow)."""
+        self._check(self._L.lgx_joint_reduce(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_reduce")
+
     def __del__(self):
         try:
             if self.handle:

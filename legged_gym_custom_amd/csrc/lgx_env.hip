@@ -3079,6 +3079,226 @@ int lgx_gait_reduce(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream) 
   return 0;
 }
 
+// ------------------------------------------------------------------ joint-load record (ABI 13)
+namespace lgx {
+// lgx_joint_record: sixteen lanes per env (4 envs per wave, a group never straddles a wave), lane
+// q < num_dof = joint q; lanes from num_dof on (12..15 at least) idle on the joint part. Each joint
+// lane moves its joint's 16 record columns as four 16-byte accesses (64 contiguous bytes per lane,
+// the env's 768 bytes and the wave's 3 KB without gaps), keeps them in registers across
+// joint_sample, and reads its torque (4 B), its dof_state pair (8 B), its action (4 B) and its five
+// limits from the device copy of the params (192 B that every group shares: cache hits). The total
+// power P is joint_power_sum's four xor shuffles inside the group (offsets 1, 2, 4, 8), and the
+// two "any joint" flags ride the same four stages as an OR. status[e], reset[e] and body[e] (one
+// float4; its column 0 is the "first sample" test) are read by every lane of the group before the
+// first store of the kernel, and only lane 0 writes status and body: no lane can see this launch's
+// update. Per recording env: 768 + 16 B of records in and out, 12 x 16 B of sources and two flags
+// in, about 1.8 KB. No LDS, no atomics; frozen envs store nothing, tail lanes load nothing.
+__global__ __launch_bounds__(256) void joint_record_kernel(const lgx_task_params* __restrict__ Pm,
+                                                           const lgx_buffers* __restrict__ Bd, float* joint,
+                                                           float* body, uint8_t* status) {
+  const lgx_buffers& B = *Bd;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 4, q = t & 15;
+  // no early return: the shuffles below need every lane of a group
+  const bool live = e < Pm->num_envs;
+  const int st = live ? status[e] : 1;
+  const int rs = live ? B.reset[e] : 0;
+  const bool sample = st == 0 && !rs;
+  const int D = Pm->num_dof;
+  const bool mine = sample && q < D;
+  float4* bq = reinterpret_cast<float4*>(body + (size_t)e * LGX_JOINT_BODY_COLS);
+  float4* jq = reinterpret_cast<float4*>(joint + ((size_t)e * LGX_MAX_DOF + q) * LGX_JOINT_COLS);
+  float r[LGX_JOINT_COLS], b[LGX_JOINT_BODY_COLS] = {0.f, 0.f, 0.f, 0.f}, ap = 0.f;
+  bool sat = false, out = false;
+  if (sample) {
+    const float4 v = *bq;
+    b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
+  }
+  if (mine) {
+    LGX_UNROLL
+    for (int i = 0; i < 4; ++i) {
+      const float4 v = jq[i];
+      r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+    }
+    const size_t j = (size_t)e * D + q;
+    const float a = q < Pm->num_actions ? B.actions[(size_t)e * Pm->num_actions + q] : 0.f;
+    ap = joint_sample(r, b[0] == 0.f, B.torques[j], B.dof_state[2 * j], B.dof_state[2 * j + 1], a,
+                      Pm->torque_limits[q], Pm->dof_vel_limits[q], Pm->dof_pos_limits[q][0], Pm->dof_pos_limits[q][1],
+                      Pm->clip_actions, Pm->dt, sat, out);
+  }
+  int any = (sat ? 1 : 0) | (out ? 2 : 0);
+  const float P = joint_power_sum(ap, [&](float s, int o) {
+    any |= __shfl_xor(any, o, 64);
+    return __shfl_xor(s, o, 64);
+  });
+  if (!live || st != 0) return;
+  if (rs) {
+    if (q == 0) status[e] = episode_end_status(B, e);
+    return;
+  }
+  if (mine) {
+    LGX_UNROLL
+    for (int i = 0; i < 4; ++i) jq[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+  }
+  if (q == 0) {
+    joint_body_sample(b, P, any & 1, any & 2);
+    *bq = make_float4(b[0], b[1], b[2], b[3]);
+  }
+}
+
+// lgx_joint_reduce: cell_reduce (above: the block shape, the env order and the tree) in six passes
+// of two joints, so that a thread holds 35 fp64 partials: pass p sums columns 1..15 of joints
+// 2p and 2p+1 in partials 0..29, the four body columns in partials 30..33 and the env count in partial
+// 34 (one layout for every pass keeps the partials in registers; pass 0 stores the body sums and the
+// count; three joints a pass take 256 VGPRs and spill into AGPRs, two take 205 and spill nothing).
+// The maxima and minima ride the same scan in 12 fp32 partials x (per joint the maxima of
+// columns 3, 6, 7, of -column 10 and of column 11; the max of body 1; 1 when an env contributed),
+// combined by fmaxf in cell_reduce's shape: shuffle-down inside each wave, then the four wave
+// results. A maximum does not depend on the order, so they are exact; a cell without an env gets
+// zeros. Every pass scans every env's cell id in the same order, so the result depends only on the
+// records (and every pass forms the same out-of-grid count): no block writes its cell when there
+// are any, and block 0 publishes the count.
+__global__ __launch_bounds__(256) void joint_reduce_kernel(const float* __restrict__ joint,
+                                                           const float* __restrict__ body,
+                                                           const uint8_t* __restrict__ status,
+                                                           const int64_t* __restrict__ levels,
+                                                           const int64_t* __restrict__ types,
+                                                           const int32_t* __restrict__ cell_ids, int N, int rows,
+                                                           int cols, double* __restrict__ cells,
+                                                           uint32_t* __restrict__ overflow) {
+  constexpr int JP = 2, NS = LGX_JOINT_COLS - 1, NB = LGX_JOINT_BODY_COLS, NC = NS * JP + NB + 1, NX = 5 * JP + 2;
+  static_assert(LGX_MAX_DOF % JP == 0, "every pass reduces JP joints");
+  static_assert(LGX_JOINT_CELL_COLS == 2 + NB + LGX_MAX_DOF * (NS + 5), "the cell layout of include/lgx.h");
+  __shared__ float xs[4][NX];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double* c = cells + (size_t)blockIdx.x * LGX_JOINT_CELL_COLS;
+  for (int pass = 0; pass < LGX_MAX_DOF / JP; ++pass) {
+    if (pass) __syncthreads();  // the previous pass's readers are done with the exchanges
+    float x[NX];
+    LGX_UNROLL
+    for (int k = 0; k < NX; ++k) x[k] = -INFINITY;
+    const uint32_t nbad = cell_reduce<NC>(levels, types, cell_ids, N, rows, cols, [&](int e, auto& s) {
+      const float4 b = *reinterpret_cast<const float4*>(body + (size_t)e * NB);
+      if (status[e] == 0 || !(b.x > 0.f)) return;
+      LGX_UNROLL
+      for (int jj = 0; jj < JP; ++jj) {
+        const float4* r4 = reinterpret_cast<const float4*>(joint + ((size_t)e * LGX_MAX_DOF + JP * pass + jj) * LGX_JOINT_COLS);
+        float r[LGX_JOINT_COLS];
+        LGX_UNROLL
+        for (int i = 0; i < 4; ++i) {
+          const float4 v = r4[i];
+          r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+        }
+        LGX_UNROLL
+        for (int k = 0; k < NS; ++k) s[NS * jj + k] += (double)r[1 + k];
+        x[5 * jj] = fmaxf(x[5 * jj], r[3]);
+        x[5 * jj + 1] = fmaxf(x[5 * jj + 1], r[6]);
+        x[5 * jj + 2] = fmaxf(x[5 * jj + 2], r[7]);
+        x[5 * jj + 3] = fmaxf(x[5 * jj + 3], -r[10]);
+        x[5 * jj + 4] = fmaxf(x[5 * jj + 4], r[11]);
+      }
+      s[NS * JP] += (double)b.x;
+      s[NS * JP + 1] += (double)b.y;
+      s[NS * JP + 2] += (double)b.z;
+      s[NS * JP + 3] += (double)b.w;
+      s[NC - 1] += 1.0;  // the env count (stored by pass 0)
+      x[5 * JP] = fmaxf(x[5 * JP], b.y);
+      x[5 * JP + 1] = 1.0f;
+    }, [=](int k, double v) {
+      if (k < NS * JP) c[2 + NB + (NS + 5) * (JP * pass + k / NS) + k % NS] = v;
+      else if (pass == 0) c[k == NC - 1 ? 0 : 1 + (k - NS * JP)] = v;
+    });
+    if (pass == 0 && tid == 0 && blockIdx.x == 0) *overflow = nbad;
+    if (nbad != 0) return;  // (uniform over the block)
+    for (int o = 32; o > 0; o >>= 1) {
+      LGX_UNROLL
+      for (int k = 0; k < NX; ++k) x[k] = fmaxf(x[k], __shfl_down(x[k], o, 64));
+    }
+    if (lane == 0) {
+      LGX_UNROLL
+      for (int k = 0; k < NX; ++k) xs[wv][k] = x[k];
+    }
+    __syncthreads();
+    if (tid < NX - 1 && (tid < 5 * JP || pass == 0)) {
+      const bool some = fmaxf(fmaxf(xs[0][NX - 1], xs[1][NX - 1]), fmaxf(xs[2][NX - 1], xs[3][NX - 1])) > 0.f;
+      const float m = fmaxf(fmaxf(xs[0][tid], xs[1][tid]), fmaxf(xs[2][tid], xs[3][tid]));
+      const double v = !some ? 0.0 : (double)(tid % 5 == 3 && tid < 5 * JP ? -m : m);
+      if (tid < 5 * JP) c[2 + NB + (NS + 5) * (JP * pass + tid / 5) + NS + tid % 5] = v;
+      else c[1 + NB] = v;
+    }
+  }
+}
+}  // namespace lgx
+
+// shared checks of the three lgx_joint_* calls
+static int joint_check(lgx_env* env, const lgx_joint_buffers* jb, const char* what, bool reduce) {
+  const std::string w(what);
+  if (int rc = check_call(env, jb, w, "joint")) return rc;
+  if (!jb->joint) return fail(env, w + ": joint is NULL");
+  if ((uintptr_t)jb->joint % 16 != 0) return fail(env, w + ": joint must be 16-byte aligned");
+  if (!jb->body) return fail(env, w + ": body is NULL");
+  if ((uintptr_t)jb->body % 16 != 0) return fail(env, w + ": body must be 16-byte aligned");
+  if (!jb->status) return fail(env, w + ": status is NULL");
+  if (!jb->overflow) return fail(env, w + ": overflow is NULL");
+  if (reduce && !jb->cells) return fail(env, w + ": cells is NULL");
+  if (jb->cell_rows < 1 || jb->cell_cols < 1 || (int64_t)jb->cell_rows * jb->cell_cols > (1 << 20))
+    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  const lgx_buffers& b = env->buffers;
+  if (int rc = check_bound(env, w, kNotBound, {{"torques", b.torques}, {"dof_state", b.dof_state},
+                                               {"actions", b.actions}, {"reset", b.reset},
+                                               {"time_out", b.time_out}}))
+    return rc;
+  const int nd = env->params.num_dof;
+  if (nd < 0 || nd > LGX_MAX_DOF) return fail(env, w + ": more joints than a record holds");
+  return 0;
+}
+
+int64_t lgx_sizeof_joint_buffers(void) { return (int64_t)sizeof(lgx_joint_buffers); }
+
+int lgx_joint_begin(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream) {
+  if (int rc = joint_check(env, jb, "lgx_joint_begin", false)) return rc;
+  if (env->host) {
+    lgxh::joint_begin(&env->params, jb);
+    return 0;
+  }
+  const size_t N = (size_t)env->params.num_envs;
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_OK(hipMemsetAsync(jb->joint, 0, sizeof(float) * LGX_JOINT_COLS * LGX_MAX_DOF * N, st));
+  HIP_OK(hipMemsetAsync(jb->body, 0, sizeof(float) * LGX_JOINT_BODY_COLS * N, st));
+  HIP_OK(hipMemsetAsync(jb->status, 0, N, st));
+  HIP_OK(hipMemsetAsync(jb->overflow, 0, sizeof(uint32_t), st));
+  return 0;
+}
+
+int lgx_joint_record(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream) {
+  if (int rc = joint_check(env, jb, "lgx_joint_record", false)) return rc;
+  if (env->host) {
+    lgxh::joint_record(&env->params, &env->buffers, jb);
+    return 0;
+  }
+  const int64_t threads = (int64_t)env->params.num_envs * 16;
+  hipLaunchKernelGGL(lgx::joint_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, env->d_params, env->d_buffers, jb->joint, jb->body, jb->status);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int lgx_joint_reduce(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream) {
+  if (int rc = joint_check(env, jb, "lgx_joint_reduce", true)) return rc;
+  if (env->host) {
+    const int bad = lgxh::joint_reduce(&env->params, &env->buffers, jb);
+    if (bad) return fail(env, "lgx_joint_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
+                              "outside the cell grid (cells not written)");
+    return 0;
+  }
+  const lgx_buffers& b = env->buffers;
+  hipLaunchKernelGGL(lgx::joint_reduce_kernel, dim3((unsigned)(jb->cell_rows * jb->cell_cols)), dim3(256), 0,
+                     (hipStream_t)hip_stream, jb->joint, jb->body, jb->status, b.terrain_levels, b.terrain_types,
+                     jb->cell_ids, env->params.num_envs, jb->cell_rows, jb->cell_cols, jb->cells, jb->overflow);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 #ifdef LGX_PHASE_CLOCK
 // dev builds only: per-env phase cycle counters ([num_envs][16] uint32, device memory)
 int lgx_debug_phase_buffer(uint32_t* dev_ptr) {

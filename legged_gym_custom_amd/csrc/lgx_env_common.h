@@ -445,6 +445,53 @@ LGX_HD float gait_body_col(int col, float x, int bits, int nfeet) {
   return ((bits >> a) & 1) == ((bits >> b) & 1) ? x + 1.0f : x;
 }
 
+// Joint-load record (lgx_joint_buffers, include/lgx.h ABI 13). One sample of one joint: the 16
+// record columns r (in registers in the kernel, in place on the host) from the joint's torque tau,
+// angle q, speed qd and action a and its limits (L torque, V speed, lo / hi angle, C action clip);
+// first: the env's first sample. Returns fabsf(tau*qd), the joint's term of the total power; sat /
+// out: the conditions of columns 1 and 9. The order of the rule text of lgx_joint_record.
+LGX_HD float joint_sample(float* r, bool first, float tau, float q, float qd, float a, float L, float V, float lo,
+                          float hi, float C, float dt, bool& sat, bool& out) {
+  const float p = tau * qd, at = fabsf(tau), av = fabsf(qd), ap = fabsf(p), da = a - r[0];
+  sat = at >= L;
+  out = q < lo || q > hi;
+  r[12] += first ? 0.f : da * da;
+  r[0] = a;
+  r[1] += sat ? 1.0f : 0.f;
+  r[2] += tau * tau;
+  r[3] = fmaxf(r[3], at);
+  r[4] += fmaxf(p, 0.f) * dt;
+  r[5] += fmaxf(-p, 0.f) * dt;
+  r[6] = fmaxf(r[6], ap);
+  r[7] = fmaxf(r[7], av);
+  r[8] += av > V ? 1.0f : 0.f;
+  r[9] += out ? 1.0f : 0.f;
+  r[10] = first ? q : fminf(r[10], q);
+  r[11] = first ? q : fmaxf(r[11], q);
+  r[13] += fabsf(a) >= C ? 1.0f : 0.f;
+  r[14] += p < 0.f ? 1.0f : 0.f;
+  r[15] += av;
+  return ap;
+}
+// The total power P of a sample: the sum of 16 slots by the fixed pairwise tree of the rule text,
+// written as four butterfly stages. xchg(s, o) is the value of s held by the slot whose index
+// differs in bit o: a xor shuffle inside the kernel's 16-lane group (T = float, a lane's slot), a
+// permutation of all 16 slots on the host (T = its array of them). Every slot ends with the same
+// bits (fp32 addition commutes).
+template <class T, class Xchg>
+LGX_HD T joint_power_sum(T s, Xchg xchg) {
+  LGX_UNROLL
+  for (int o = 1; o < 16; o <<= 1) s = s + xchg(s, o);
+  return s;
+}
+// The body columns [4] after a sample: P as above, sat / out: any joint met column 1's / 9's condition.
+LGX_HD void joint_body_sample(float* b, float P, bool sat, bool out) {
+  b[0] += 1.0f;
+  b[1] = fmaxf(b[1], P);
+  b[2] += sat ? 1.0f : 0.f;
+  b[3] += out ? 1.0f : 0.f;
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];

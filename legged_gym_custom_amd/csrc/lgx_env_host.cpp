@@ -1308,6 +1308,86 @@ int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_b
   return 0;
 }
 
+void joint_begin(const lgx_task_params* P, const lgx_joint_buffers* J) {
+  const size_t N = (size_t)P->num_envs;
+  memset(J->joint, 0, sizeof(float) * LGX_JOINT_COLS * LGX_MAX_DOF * N);
+  memset(J->body, 0, sizeof(float) * LGX_JOINT_BODY_COLS * N);
+  memset(J->status, 0, N);
+  *J->overflow = 0;
+}
+
+// The kernel's 16-lane group as one value: joint_power_sum's butterfly on all 16 slots at once.
+struct Slots16 { float v[16]; };
+static inline Slots16 operator+(const Slots16& a, const Slots16& b) {
+  Slots16 r;
+  for (int i = 0; i < 16; ++i) r.v[i] = a.v[i] + b.v[i];
+  return r;
+}
+
+// lgx_joint_record (include/lgx.h): the kernel's arithmetic (lgx_env.hip joint_record_kernel), the
+// joints in order
+void joint_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint_buffers* J) {
+  const int N = P->num_envs, D = P->num_dof, A = P->num_actions;
+#pragma omp parallel for schedule(static)
+  for (int e = 0; e < N; ++e) {
+    if (J->status[e] != 0) continue;
+    if (B->reset[e]) {
+      J->status[e] = episode_end_status(*B, e);
+      continue;
+    }
+    float* body = J->body + (size_t)e * LGX_JOINT_BODY_COLS;
+    const bool first = body[0] == 0.f;
+    Slots16 s = {};
+    bool any_sat = false, any_out = false;
+    for (int j = 0; j < D; ++j) {
+      const size_t k = (size_t)e * D + j;
+      bool sat, out;
+      s.v[j] = joint_sample(J->joint + ((size_t)e * LGX_MAX_DOF + j) * LGX_JOINT_COLS, first, B->torques[k],
+                            B->dof_state[2 * k], B->dof_state[2 * k + 1], j < A ? B->actions[(size_t)e * A + j] : 0.f,
+                            P->torque_limits[j], P->dof_vel_limits[j], P->dof_pos_limits[j][0], P->dof_pos_limits[j][1],
+                            P->clip_actions, P->dt, sat, out);
+      any_sat |= sat;
+      any_out |= out;
+    }
+    const Slots16 total = joint_power_sum(s, [](const Slots16& x, int o) {
+      Slots16 r;
+      for (int i = 0; i < 16; ++i) r.v[i] = x.v[i ^ o];
+      return r;
+    });
+    joint_body_sample(body, total.v[0], any_sat, any_out);
+  }
+}
+
+// lgx_joint_reduce: the envs in order; returns the number of envs outside the cell grid (cells are
+// written only when it is 0, overflow always is)
+int joint_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint_buffers* J) {
+  const int N = P->num_envs, rows = J->cell_rows, cols = J->cell_cols;
+  if (int bad = reduce_begin(B, J->cell_ids, N, rows, cols, J->overflow, {{J->cells, LGX_JOINT_CELL_COLS}})) return bad;
+  constexpr int NS = LGX_JOINT_COLS - 1, PER = NS + 5;
+  for (int e = 0; e < N; ++e) {  // env order: deterministic
+    const float* body = J->body + (size_t)e * LGX_JOINT_BODY_COLS;
+    if (J->status[e] == 0 || !(body[0] > 0.f)) continue;
+    const int id = cell_of_env(B->terrain_levels, B->terrain_types, J->cell_ids, e, rows, cols);
+    double* cl = J->cells + (size_t)id * LGX_JOINT_CELL_COLS;
+    const bool init = cl[0] == 0.0;  // the cell's first env sets the maxima and minima
+    const auto hi = [init](double& m, float v) { m = init ? (double)v : std::max(m, (double)v); };
+    cl[0] += 1.0;
+    for (int k = 0; k < LGX_JOINT_BODY_COLS; ++k) cl[1 + k] += (double)body[k];
+    hi(cl[1 + LGX_JOINT_BODY_COLS], body[1]);
+    for (int j = 0; j < LGX_MAX_DOF; ++j) {
+      const float* r = J->joint + ((size_t)e * LGX_MAX_DOF + j) * LGX_JOINT_COLS;
+      double* cj = cl + 2 + LGX_JOINT_BODY_COLS + PER * j;
+      for (int k = 0; k < NS; ++k) cj[k] += (double)r[1 + k];
+      hi(cj[NS], r[3]);
+      hi(cj[NS + 1], r[6]);
+      hi(cj[NS + 2], r[7]);
+      cj[NS + 3] = init ? (double)r[10] : std::min(cj[NS + 3], (double)r[10]);
+      hi(cj[NS + 4], r[11]);
+    }
+  }
+  return 0;
+}
+
 int threads() { return omp_get_max_threads(); }
 
 }  // namespace lgxh

@@ -43,6 +43,12 @@ void trace_gather(const lgx_task_params* P, const lgx_trace_buffers* T, const in
 void gait_begin(const lgx_task_params* P, const lgx_gait_buffers* G);
 void gait_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G);
 int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_buffers* G);
+// lgx_joint_begin / lgx_joint_record / lgx_joint_reduce on host buffers (OpenMP over envs; the
+// reduction in env order): the joint-load record, include/lgx.h ABI 13. joint_reduce returns the
+// number of envs outside the cell grid, as eval_reduce does.
+void joint_begin(const lgx_task_params* P, const lgx_joint_buffers* J);
+void joint_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint_buffers* J);
+int joint_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint_buffers* J);
 // the worker threads the host backend uses (OpenMP)
 int threads();
 

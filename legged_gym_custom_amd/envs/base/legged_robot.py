@@ -339,6 +339,51 @@ class LeggedRobot(BaseTask):
         return self._reduced_cells("lgx_gait_reduce", self._gait_buffers(), self._gait_overflow,
                                    "a terrain level / type (or cell id)", self._gait_cells)[0]
 
+    # ------------------------------------------------------------------ joint-load record
+    def joint_buffers(self, rows=None, cols=None, cell_ids=None):
+        """The joint-load record's tensors (include/lgx.h lgx_joint_buffers, ABI 13), allocated once
+        per (rows, cols, cell_ids tensor) so a captured loop replays on fixed addresses: joint_rec
+        [N, 12, 16] and joint_body [N, 4] (each env's first episode since joint_begin), joint_status
+        [N] (the eval_status rule) and the cells [rows, cols, 246]. rows, cols and cell_ids as in
+        gait_buffers; every key asked for keeps its tensors, and the call makes that set the current
+        one, which joint_begin / joint_record / joint_cells and the three attributes refer to."""
+        if rows is None or cols is None:
+            grid = getattr(self, "terrain_levels", None) is not None
+            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
+        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr())
+        if not hasattr(self, "_joints"):
+            self._joints = {}  # key -> lgx_joint_buffers (which keeps its tensors, cell_ids included)
+        if key not in self._joints:
+            z, n = self._zeros, self.num_envs
+            self._joints[key] = self._native.joint_buffers(
+                z(n, _abi.MAX_DOF, _abi.JOINT_COLS), z(n, _abi.JOINT_BODY_COLS), z(n, dtype=torch.uint8),
+                z(key[0], key[1], _abi.JOINT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32), cell_ids=cell_ids)
+        self._joint = self._joints[key]
+        self.joint_rec, self.joint_body, self.joint_status, self._joint_cells, self._joint_overflow = self._joint._keep[:5]
+        return self._joint
+
+    def _joint_buffers(self):
+        if getattr(self, "_joint", None) is None:
+            raise RuntimeError("no joint record: call joint_buffers(...) first")
+        return self._joint
+
+    def joint_begin(self):
+        """lgx_joint_begin: zero the joint records and record every env's next (first) episode."""
+        self._native.joint_begin(self._joint_buffers(), self._stream())
+
+    def joint_record(self):
+        """lgx_joint_record for the step just run (call after every step(); stream-ordered, no host
+        sync, capturable)."""
+        self._native.joint_record(self._joint_buffers(), self._stream())
+
+    def joint_cells(self):
+        """lgx_joint_reduce, then the cells [rows, cols, 246] float64 on the host: the number of
+        finished envs with samples, the sums and the peak of their body columns and, per joint, the
+        sums of columns 1..15 and the extremes of columns 3, 6, 7, 10 and 11. Synchronises. An env
+        whose cell lies outside the grid is an error."""
+        return self._reduced_cells("lgx_joint_reduce", self._joint_buffers(), self._joint_overflow,
+                                   "a terrain level / type (or cell id)", self._joint_cells)[0]
+
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""
         return torch.cuda.current_stream(self.device).cuda_stream if self.sim_device_id >= 0 else 0

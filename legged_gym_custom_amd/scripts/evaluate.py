@@ -9,7 +9,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
-         [--trace_falls M [--trace_s 2.0]] [--gait]
+         [--trace_falls M [--trace_s 2.0]] [--gait] [--joints]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
 history the largest one needs); several values give one report each under "sweep", on one captured
@@ -42,6 +42,15 @@ flight share, the mean number of feet in contact, the six pair synchronies and a
 pace / bound / mixed). One summary line per cell or bin with data is printed before the JSON ("gait <where>:
 <label>, stride Hz, mean duty factor, slip").
 
+--joints: the joint load (PolicyEvaluator.run(joints=True), joint_cell_report), valid in every mode, alone or with
+--gait and --trace_falls: a per-joint record runs on the device after every step; every cell, bin and "total" of
+the JSON gains a "joints" entry: per joint the torque saturation share, RMS and peak torque (also over the limit),
+positive and braking power, work share, peak power, peak and mean speed, over-speed and out-of-range shares, the
+range used and its margin to the soft limits, action rate, clip share and braking share; per body the peak total
+power, the shares of samples with any joint saturated / out of range, and flags. For the total one line per joint
+is printed before the JSON ("joint total <name>: saturation share, RMS torque / limit, peak speed / limit, range
+margin, action rate, flags").
+
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
 eval_<policy>_command.json)."""
@@ -65,7 +74,7 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
-             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False):
+             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -101,21 +110,21 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         depth = min(max(int(round(float(trace_s) / float(env.dt))), 1), int(env.max_episode_length))
     if push_vel:
         report = dict(**head, **ev.run_push_test(push_vel, directions=push_dirs, at_s=push_at_s, num_steps=eval_steps,
-                                                 graph=graph, trace_depth=depth, gait=gait))
+                                                 graph=graph, trace_depth=depth, gait=gait, joints=joints))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_push.json")
     elif cmd_vx:
         report = dict(**head, **ev.run_command_test(cmd_vx, vy=cmd_vy or (0.0,), yaw=cmd_yaw or (0.0,), at_s=cmd_at_s,
                                                     start=cmd_start or (0.0, 0.0, 0.0), num_steps=eval_steps,
-                                                    graph=graph, trace_depth=depth, gait=gait))
+                                                    graph=graph, trace_depth=depth, gait=gait, joints=joints))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_command.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
-                                      trace_depth=depth, gait=gait)
+                                      trace_depth=depth, gait=gait, joints=joints)
         report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_latency.json")
     else:
         report = dict(**head, **ev.run(eval_steps, graph=graph, action_delay_s=delays_s[0] if delays_s else None,
-                                       motor_strength=motor_strength, trace_depth=depth, gait=gait))
+                                       motor_strength=motor_strength, trace_depth=depth, gait=gait, joints=joints))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}.json")
     if depth is not None:
         import numpy as np
@@ -160,6 +169,24 @@ def gait_summary(report):
     return lines
 
 
+def joint_summary(report):
+    """The human-readable lines of a --joints report: one per joint of the total (of every entry of
+    a latency sweep; "-" where it has no data)."""
+    fmt = lambda v, spec: "-" if v is None else format(v, spec)  # noqa: E731
+    lines = []
+    for i, rep in enumerate(report.get("sweep", [report])):
+        tag = f"delay {report['action_delay_ms'][i]:g} ms " if "sweep" in report else ""
+        total = rep["total"].get("joints")
+        for name, j in (total["joints"] if total else {}).items():
+            flags = [f.split(": ", 1)[1] for f in total["flags"] or () if f.startswith(name + ": ")]
+            lines.append(f"joint {tag}total {name}: saturated {fmt(j['torque_saturation_share'], '.1%')}, RMS torque "
+                         f"{fmt(j['rms_torque_over_limit'], '.2f')} of the limit, peak speed "
+                         f"{fmt(j['max_peak_speed_over_limit'], '.2f')} of the limit, range margin "
+                         f"{fmt(j['range_margin_rad'], '.3f')} rad, action rate {fmt(j['action_rate_rms'], '.3f')}, "
+                         f"flags: {'; '.join(flags) or 'none'}")
+    return lines
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument("--policy", choices=("student", "teacher"), default="student")
@@ -178,6 +205,7 @@ def main(argv=None):
     p.add_argument("--trace_falls", type=int, default=None)
     p.add_argument("--trace_s", type=float, default=2.0)
     p.add_argument("--gait", action="store_true")
+    p.add_argument("--joints", action="store_true")
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
     report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
@@ -185,8 +213,8 @@ def main(argv=None):
                          push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s,
                          cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
                          cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s,
-                         gait=own.gait)
-    for ln in gait_summary(report) if own.gait else ():
+                         gait=own.gait, joints=own.joints)
+    for ln in (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []):
         print(ln)
     print(json.dumps(report))
     return report

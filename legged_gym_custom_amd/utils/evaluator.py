@@ -42,6 +42,12 @@ stance and swing times, stride frequency, duty factor, foot clearance, slip, tou
 share, which feet move together, and a gait label (gait_cell_report); the per-env records:
 gait_records().
 
+Joint load (joints=True of the three runs): a per-joint record runs on the device after each step
+(lgx_joint_record, include/lgx.h ABI 13) and is reduced per cell or bin of the run's mode: what the
+policy asks of each motor: torque saturation, RMS and peak torque, positive and braking work, peak
+speed, use of the joint range, action rate and clipping, and a list of flags (joint_cell_report);
+the per-env records: joint_records().
+
 Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
@@ -188,6 +194,99 @@ def gait_cell_report(row, dt, foot_names):
             "mean_slip_m_per_stance_s": mean([f["slip_m_per_stance_s"] for f in feet.values()]), "feet": feet}
 
 
+# joint_cell_report's flags: the shares of a joint's samples above which it is named
+JOINT_FLAG_SATURATION = 0.05  # torque at or above the limit
+JOINT_FLAG_RANGE = 0.01       # angle outside the soft position limits
+JOINT_FLAG_CLIP = 0.01        # action at or above clip_actions
+_JOINT_PER = _abi.JOINT_COLS + 4  # columns of a joint in a cell row: 15 sums, 5 extremes
+_JOINT_BASE = 2 + _abi.JOINT_BODY_COLS
+assert _JOINT_BASE + _abi.MAX_DOF * _JOINT_PER == _abi.JOINT_CELL_COLS
+
+
+def _joint_extremes():
+    """The cell columns that are maxima and those that are minima (lgx_joint_reduce)."""
+    hi, lo = [1 + _abi.JOINT_BODY_COLS], []
+    for j in range(_abi.MAX_DOF):
+        b = _JOINT_BASE + _JOINT_PER * j
+        hi += [b + 15, b + 16, b + 17, b + 19]
+        lo.append(b + 18)
+    return hi, lo
+
+
+def joint_total_row(cells):
+    """The joint cell row [246] of all cells [..., 246] together: the sums added, the maxima / minima
+    taken over the cells that have an env (an empty cell's zeros are no angle or torque anyone
+    used); all zero when every cell is empty."""
+    flat = torch.as_tensor(cells, dtype=torch.float64).reshape(-1, _abi.JOINT_CELL_COLS)
+    total = flat.sum(0)
+    full = flat[flat[:, 0] > 0]
+    hi, lo = _joint_extremes()
+    total[hi] = full[:, hi].max(0).values if len(full) else 0.0
+    total[lo] = full[:, lo].min(0).values if len(full) else 0.0
+    return total
+
+
+def joint_cell_report(row, dt, joint_names, params):
+    """The joint-load entries of one joint cell row [246] (lgx_joint_reduce) for the joints
+    joint_names (env.dof_names); params: the limits, an object with torque_limits [j], dof_vel_limits
+    [j], dof_pos_limits [j][2] and clip_actions (the env's lgx_task_params). JSON-serialisable; None
+    where there is no data, never NaN.
+
+    Per joint ("joints"[name]): torque_saturation_share (samples with |torque| at the limit),
+    rms_torque and rms_torque_over_limit (heat), mean_peak_torque (the envs' mean of their peak),
+    max_peak_torque and max_peak_torque_over_limit, mean_positive_power_w / mean_negative_power_w
+    (positive / braking work per second of recorded time), work_share (the joint's share of the
+    positive work), max_peak_power_w, max_peak_speed, max_peak_speed_over_limit, over_speed_share,
+    out_of_range_share (outside the soft position limits), range_used [min q, max q],
+    range_margin_rad (min(min q - lo, hi - max q): negative when the range was left),
+    action_rate_rms (over the samples that have a predecessor: samples - envs), action_clip_share,
+    braking_share (samples with negative power) and mean_speed. Per body: envs, samples,
+    mean_peak_power_w (the envs' mean of their peak total power), max_peak_power_w,
+    any_saturation_share / any_out_of_range_share (samples in which any joint was) and flags.
+
+    flags is a rule and not a measurement: one string per joint and crossing, for a torque
+    saturation share above JOINT_FLAG_SATURATION, any sample above the speed limit, an out-of-range
+    share above JOINT_FLAG_RANGE and an action clip share above JOINT_FLAG_CLIP."""
+    c = [float(v) for v in row]
+    assert len(c) == _abi.JOINT_CELL_COLS
+    div = lambda a, b: a / b if b > 0 else None  # noqa: E731
+    root = lambda v: None if v is None else math.sqrt(v)  # noqa: E731
+    n, samples = int(round(c[0])), c[1]
+    have = lambda v: v if n > 0 else None  # noqa: E731  (an extreme of no env is no value)
+    names = [str(x) for x in joint_names][:_abi.MAX_DOF]
+    blocks = [c[_JOINT_BASE + _JOINT_PER * j: _JOINT_BASE + _JOINT_PER * (j + 1)] for j in range(len(names))]
+    work = sum(b[3] for b in blocks)
+    joints, flags = {}, []
+    for j, (name, b) in enumerate(zip(names, blocks)):
+        L, V = float(params.torque_limits[j]), float(params.dof_vel_limits[j])
+        lo, hi = float(params.dof_pos_limits[j][0]), float(params.dof_pos_limits[j][1])
+        rms = root(div(b[1], samples))
+        e = {"torque_saturation_share": div(b[0], samples), "rms_torque": rms,
+             "rms_torque_over_limit": None if rms is None else div(rms, L), "mean_peak_torque": div(b[2], n),
+             "max_peak_torque": have(b[15]), "max_peak_torque_over_limit": have(div(b[15], L)),
+             "mean_positive_power_w": div(b[3], samples * dt), "mean_negative_power_w": div(b[4], samples * dt),
+             "work_share": have(div(b[3], work)), "max_peak_power_w": have(b[16]), "max_peak_speed": have(b[17]),
+             "max_peak_speed_over_limit": have(div(b[17], V)), "over_speed_share": div(b[7], samples),
+             "out_of_range_share": div(b[8], samples), "range_used": have([b[18], b[19]]),
+             "range_margin_rad": have(min(b[18] - lo, hi - b[19])), "action_rate_rms": root(div(b[11], samples - n)),
+             "action_clip_share": div(b[12], samples), "braking_share": div(b[13], samples),
+             "mean_speed": div(b[14], samples)}
+        joints[name] = e
+        if n > 0:
+            if e["torque_saturation_share"] > JOINT_FLAG_SATURATION:
+                flags.append(f"{name}: torque at its limit in {e['torque_saturation_share']:.1%} of the samples")
+            if b[7] > 0:
+                flags.append(f"{name}: above the speed limit in {int(round(b[7]))} samples "
+                             f"({e['over_speed_share']:.2%})")
+            if e["out_of_range_share"] > JOINT_FLAG_RANGE:
+                flags.append(f"{name}: outside the soft position limits in {e['out_of_range_share']:.1%} of the samples")
+            if e["action_clip_share"] > JOINT_FLAG_CLIP:
+                flags.append(f"{name}: action at its clip in {e['action_clip_share']:.1%} of the samples")
+    return {"envs": n, "samples": int(round(samples)), "mean_peak_power_w": div(c[2], n), "max_peak_power_w": have(c[5]),
+            "any_saturation_share": div(c[3], samples), "any_out_of_range_share": div(c[4], samples),
+            "flags": flags if n > 0 else None, "joints": joints}
+
+
 def _min_max(t, kind):
     return None if t is None else [kind(t.min()), kind(t.max())]
 
@@ -205,7 +304,7 @@ class PolicyEvaluator:
         if torch.device(self.device) != torch.device(env.device):
             raise RuntimeError(f"the evaluator runs the policy on the env's device ({env.device}), not {self.device}")
         self.on_gpu = self.device.startswith("cuda")
-        self._graph = self._graph_key = None            # run's captured loop (key: the trace depth, gait)
+        self._graph = self._graph_key = None            # run's captured loop (key: the trace depth, gait, joints)
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
         self._fused = None
@@ -216,6 +315,8 @@ class PolicyEvaluator:
         self.last_trace_depth = None  # the depth of the last finished run, None when it was not traced
         self._gait = False            # whether the run under way keeps the gait record
         self.last_gait_cells = None   # [rows, cols, 61] of the last finished run, None without gait=True
+        self._joints = False          # whether the run under way keeps the joint-load record
+        self.last_joint_cells = None  # [rows, cols, 246] of the last finished run, None without joints=True
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -251,8 +352,8 @@ class PolicyEvaluator:
 
     def step(self, ev=None):
         """One eager iteration: act, env.step, eval_accumulate (ev: the eval buffers to record
-        into; default: the plain evaluation's), gait_record in a gait run and trace_record in a
-        traced run."""
+        into; default: the plain evaluation's), gait_record in a gait run, joint_record in a joints
+        run and trace_record in a traced run."""
         with torch.no_grad():
             self._body(ev)
 
@@ -263,6 +364,8 @@ class PolicyEvaluator:
         env.eval_accumulate(ev)
         if self._gait:
             env.gait_record()
+        if self._joints:
+            env.joint_record()
         if self._trace_depth is not None:
             env.trace_record()
 
@@ -282,15 +385,17 @@ class PolicyEvaluator:
             env.eval_begin(ev)
             if self._gait:
                 env.gait_begin()
+            if self._joints:
+                env.joint_begin()
             if self._trace_depth is not None:
                 env.trace_begin()
 
-    def _set_trace(self, trace_depth, gait=False):
+    def _set_trace(self, trace_depth, gait=False, joints=False):
         """Start a run: the flight recorder's depth for it (None: off; else the env's rings of that
-        depth, allocated once per depth) and whether it keeps the gait record (the mode picks the
-        env's gait buffers: their cell key is the mode's)."""
-        self.last_trace_depth = self.last_gait_cells = None
-        self._gait = bool(gait)
+        depth, allocated once per depth) and whether it keeps the gait record and the joint-load
+        record (the mode picks the env's gait / joint buffers: their cell key is the mode's)."""
+        self.last_trace_depth = self.last_gait_cells = self.last_joint_cells = None
+        self._gait, self._joints = bool(gait), bool(joints)
         self._trace_depth = None if trace_depth is None else int(trace_depth)
         if self._trace_depth is not None:
             self.env.trace_buffers(self._trace_depth)
@@ -312,7 +417,7 @@ class PolicyEvaluator:
 
     # ------------------------------------------------------------------ run
     def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None, trace_depth=None,
-            gait=False):
+            gait=False, joints=False):
         """Evaluate: reset, num_steps x {act, step, accumulate}, reduce, one host read; returns the
         report (JSON-serialisable): per-cell and total entries REPORT_KEYS, None where a cell has
         no data (never NaN).
@@ -337,11 +442,17 @@ class PolicyEvaluator:
         gait: keep the gait record (the loop body gains lgx_gait_record, in a captured loop of its
         own; the cells are bit-identical to a run's without it): the report gains a "gait" entry
         (gait_cell_report) in every cell and in total; the per-env records: gait_records(). False:
-        nothing changes."""
+        nothing changes.
+        joints: keep the joint-load record (the loop body gains lgx_joint_record, in a captured loop
+        of its own; the cells are bit-identical to a run's without it): the report gains a "joints"
+        entry (joint_cell_report) in every cell and in total; the per-env records: joint_records().
+        False: nothing changes."""
         env = self.env
-        self._set_trace(trace_depth, gait)
+        self._set_trace(trace_depth, gait, joints)
         if self._gait:
             env.gait_buffers()  # the terrain grid is the cell key
+        if self._joints:
+            env.joint_buffers()  # likewise
         saved = []  # (buffer, its values before this run)
         try:
             if action_delay_s is not None:
@@ -357,7 +468,9 @@ class PolicyEvaluator:
                     saved.append((env.motor_strengths, torch.ones_like(env.motor_strengths)))
             cells, gcells, head, rates = self._drive("_graph", (), num_steps, graph, env.eval_cells)
             out = self.report(cells, head["num_steps"], rates["wall_s"], head["graph"])
-            self._attach_gait(gcells, out["total"], [cell for row in out["cells"] for cell in row])
+            bins = [cell for row in out["cells"] for cell in row]
+            self._attach_gait(gcells, out["total"], bins)
+            self._attach_joints(out["total"], bins)
             return out
         finally:
             for buf, old in saved:
@@ -366,17 +479,18 @@ class PolicyEvaluator:
     def _drive(self, slot, key, num_steps, graph, read_cells, prepare=None, started=None, cleanup=None):
         """The run of all three modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
         "_cmd_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
-        the trace depth and the gait flag are added: the loop is captured when there is no graph or
+        the trace depth, the gait flag and the joints flag are added: the loop is captured when there is no graph or
         the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
         buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
         always, when the run ends or fails. read_cells(): the mode's reduce and host read
         (synchronises), one tensor or a tuple with the [rows, cols, 12] cells first.
         Returns (what read_cells returned, the gait cells or None, the report's common head, its
-        wall_s / env_steps_per_s tail) and sets last_cells, last_trace_depth and last_gait_cells."""
+        wall_s / env_steps_per_s tail) and sets last_cells, last_trace_depth, last_gait_cells and
+        last_joint_cells (the joint cells of a joints run)."""
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
-        gkey = key + (self._trace_depth, self._gait)
+        gkey = key + (self._trace_depth, self._gait, self._joints)
         try:
             ev = prepare() if prepare else None
             if use_graph and (getattr(self, slot) is None or getattr(self, slot + "_key") != gkey):
@@ -388,12 +502,14 @@ class PolicyEvaluator:
             t0 = self._loop(steps, getattr(self, slot) if use_graph else None, ev)
             cells = read_cells()
             gcells = env.gait_cells() if self._gait else None
+            jcells = env.joint_cells() if self._joints else None
             wall = time.perf_counter() - t0
         finally:
             if cleanup:
                 cleanup()
         self.last_cells = cells[0] if isinstance(cells, tuple) else cells  # as lgx_eval_reduce wrote them
         self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells  # ([rows, cols, 61] float64)
+        self.last_joint_cells = jcells  # ([rows, cols, 246] float64)
         return cells, gcells, self._head(steps, use_graph), self._rates(steps, wall)
 
     def _head(self, steps, graph):
@@ -414,6 +530,19 @@ class PolicyEvaluator:
         total["gait"] = gait_cell_report(flat.sum(0), dt, names)
         for row, b in zip(flat, bins):
             b["gait"] = gait_cell_report(row, dt, names)
+
+    def _attach_joints(self, total, bins):
+        """The "joints" entry (joint_cell_report) of the total and of every bin, from the finished
+        run's last_joint_cells; bins as in _attach_gait. Nothing without a joint-load record."""
+        jcells = self.last_joint_cells
+        if jcells is None:
+            return
+        env = self.env
+        dt, names, params = float(env.dt), env.dof_names, env._native.params
+        flat = jcells.reshape(-1, jcells.shape[2])
+        total["joints"] = joint_cell_report(joint_total_row(flat), dt, names, params)
+        for row, b in zip(flat, bins):
+            b["joints"] = joint_cell_report(row, dt, names, params)
 
     def _switch_step(self, at_s, test):
         """at_s (seconds into the episode) as an episode step of the push / command test."""
@@ -437,6 +566,16 @@ class PolicyEvaluator:
         return {"foot": env.gait_foot.cpu().numpy(), "body": env.gait_body.cpu().numpy(),
                 "status": env.gait_status.cpu().numpy()}
 
+    def joint_records(self):
+        """The per-env joint-load records of the last run (it must have been one with joints=True),
+        numpy arrays on the host: joint [N, 12, 16], body [N, 4] and status [N] (lgx_joint_buffers)."""
+        if self.last_joint_cells is None:
+            raise RuntimeError("joint_records(): the last run kept no joint record (pass joints=True to run, "
+                               "run_push_test or run_command_test first)")
+        env = self.env
+        return {"joint": env.joint_rec.cpu().numpy(), "body": env.joint_body.cpu().numpy(),
+                "status": env.joint_status.cpu().numpy()}
+
     def _loop(self, steps, g, ev):
         """steps x the loop body (g: its captured graph, or None for the eager loop) recording
         into ev; returns the start time."""
@@ -455,7 +594,7 @@ class PolicyEvaluator:
 
     # ------------------------------------------------------------------ push recovery
     def run_push_test(self, speeds, directions=8, at_s=2.0, settle_tol=0.3, num_steps=None, graph=True,
-                      trace_depth=None, gait=False):
+                      trace_depth=None, gait=False, joints=False):
         """How hard a shove does the policy survive, from which side, and how quickly does it
         settle: one run in which every env is pushed once, at episode step round(at_s / dt), by a
         velocity impulse of its bin (speed index s, direction index d): dvel = speeds[s] *
@@ -471,6 +610,7 @@ class PolicyEvaluator:
         The schedule is cleared in place when the run ends, so a following run() is the plain one.
 
         trace_depth: the flight recorder, as in run(). gait: the gait record, as in run(), per bin.
+        joints: the joint-load record, as in run(), per bin.
 
         Returns the report: "bins"[s][d] with the REPORT_KEYS entries and pushed (finished envs
         with post-push samples), mean_peak_tilt_rad, mean_peak_lin_vel_err (m/s), survivors (timed
@@ -480,7 +620,7 @@ class PolicyEvaluator:
         ValueError: no speeds or directions, a negative or non-finite speed, a push step outside
         0 < step < max_episode_length."""
         env = self.env
-        self._set_trace(trace_depth, gait)
+        self._set_trace(trace_depth, gait, joints)
         speeds = [float(v) for v in speeds]
         S, D = len(speeds), int(directions)
         if S < 1 or D < 1 or not all(math.isfinite(v) and v >= 0.0 for v in speeds):
@@ -500,6 +640,8 @@ class PolicyEvaluator:
             env.push_cell_ids.copy_(bins.to(torch.int32))
             if self._gait:
                 env.gait_buffers(S, D, env.push_cell_ids)  # the bin is the cell key
+            if self._joints:
+                env.joint_buffers(S, D, env.push_cell_ids)
             return ev
 
         (cells, pcells), gcells, head, rates = self._drive(
@@ -513,12 +655,15 @@ class PolicyEvaluator:
                "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
                "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
                "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)], **rates}
-        self._attach_gait(gcells, out["total"], [b for row in out["bins"] for b in row])
+        flat = [b for row in out["bins"] for b in row]
+        self._attach_gait(gcells, out["total"], flat)
+        self._attach_joints(out["total"], flat)
         return out
 
     # ------------------------------------------------------------------ command response
     def run_command_test(self, vx, vy=(0.0,), yaw=(0.0,), at_s=2.0, start=(0.0, 0.0, 0.0), steady_after_s=1.0,
-                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None, gait=False):
+                         settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None, gait=False,
+                         joints=False):
         """What does the robot do when commanded, how fast does it get there, and does it stay up:
         one run in which every env holds the command `start` = (vx, vy, yaw rate), switches at
         episode step round(at_s / dt) to the command of its bin (vx[ix], vy[iy], yaw[iw]) and is
@@ -535,7 +680,8 @@ class PolicyEvaluator:
         plain one.
 
         trace_depth: the flight recorder, as in run(). gait: the gait record, as in run(), per bin
-        (how the gait changes with the commanded speed).
+        (how the gait changes with the commanded speed). joints: the joint-load record, as in run(),
+        per bin (what each commanded speed asks of the motors).
 
         Returns the report: "bins"[ix][iy][iw] with the REPORT_KEYS entries and switched (finished
         envs with post-switch samples), survivors (timed out among them), mean_settle_s /
@@ -548,7 +694,7 @@ class PolicyEvaluator:
         ValueError: an empty list, a non-finite entry, a switch step outside 0 < step <
         max_episode_length, a negative or non-finite tolerance or steady_after_s."""
         env = self.env
-        self._set_trace(trace_depth, gait)
+        self._set_trace(trace_depth, gait, joints)
         vx, vy, yaw, start = ([float(v) for v in lst] for lst in (vx, vy, yaw, start))
         if min(len(vx), len(vy), len(yaw)) < 1 or len(start) != 3 or \
                 not all(math.isfinite(v) for v in vx + vy + yaw + start):
@@ -573,6 +719,8 @@ class PolicyEvaluator:
             env.cmd_switch_step.fill_(step)
             if self._gait:
                 env.gait_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
+            if self._joints:
+                env.joint_buffers(nx, ny * nw, env.cmd_cell_ids)
             return ev
 
         (cells, ccells), gcells, head, rates = self._drive("_cmd_graph", key, num_steps, graph, env.eval_command_cells,
@@ -587,7 +735,9 @@ class PolicyEvaluator:
                "yaw_tol": float(yaw_tol), "total": total,
                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
                           for iw in range(nw)] for iy in range(ny)] for ix in range(nx)], **rates}
-        self._attach_gait(gcells, total, [b for plane in out["bins"] for row in plane for b in row])
+        flat = [b for plane in out["bins"] for row in plane for b in row]
+        self._attach_gait(gcells, total, flat)
+        self._attach_joints(total, flat)
         return out
 
     # ------------------------------------------------------------------ flight recorder

@@ -5,6 +5,7 @@ networks (the timing does not depend on the weights), graph replay and the eager
   python tools/eval_bench.py --push_vel 0,0.5,1.0,1.5 [--push_dirs 8] ...   # + the push test (run_push_test)
   python tools/eval_bench.py --trace_depth 100 ...   # + the plain run with the flight recorder on, and traces()
   python tools/eval_bench.py --gait ...   # + the plain run with the gait record on (run(gait=True))
+  python tools/eval_bench.py --joints ...   # + the plain run with the joint-load record on (run(joints=True))
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/eval_bench.py --profile
   python tools/eval_bench.py --stats DIR/..._kernel_stats.csv --merge FILE   # kernel times into FILE
 
@@ -24,7 +25,8 @@ KERNELS = {"eval_accumulate_kernel": "eval_accumulate_us", "eval_reduce_kernel":
            "eval_cmd_reduce_kernel": "eval_cmd_reduce_us",
            "env_step_kernel": "env_step_us", "act_kernel(lgx_s8_act_args": "act_us",
            "trace_record_kernel": "trace_record_us", "trace_gather_kernel": "trace_gather_us",
-           "gait_record_kernel": "gait_record_us", "gait_reduce_kernel": "gait_reduce_us"}
+           "gait_record_kernel": "gait_record_us", "gait_reduce_kernel": "gait_reduce_us",
+           "joint_record_kernel": "joint_record_us", "joint_reduce_kernel": "joint_reduce_us"}
 
 
 def merge_stats(stats_csv, out):
@@ -58,6 +60,7 @@ def main():
     p.add_argument("--trace_depth", type=int, default=None,
                    help="also time run(trace_depth=K), the flight recorder, and traces('falls', 16) after it")
     p.add_argument("--gait", action="store_true", help="also time run(gait=True), the gait record")
+    p.add_argument("--joints", action="store_true", help="also time run(joints=True), the joint-load record")
     p.add_argument("--profile", action="store_true")
     p.add_argument("--stats")
     p.add_argument("--merge")
@@ -84,7 +87,7 @@ def main():
     runner, _ = task_registry.make_alg_runner(env, args=args, train_cfg=tcfg, log_root=None)
     ev = PolicyEvaluator(env, runner)
     if a.profile:
-        r = ev.run(a.steps or 200, graph=False, trace_depth=a.trace_depth, gait=a.gait)
+        r = ev.run(a.steps or 200, graph=False, trace_depth=a.trace_depth, gait=a.gait, joints=a.joints)
         if a.trace_depth:
             ev.traces("falls", 16)
         if a.cmd_vx:  # (the only run with eval_cmd_reduce_kernel)
@@ -109,18 +112,25 @@ def main():
         rates.update(gait_graph=[], gait_eager=[])
         gaited(20, True)
         gaited(20, False)
+    jointed = (lambda steps, graph: ev.run(steps, graph, joints=True))
+    if a.joints:
+        rates.update(joints_graph=[], joints_eager=[])
+        jointed(20, True)
+        jointed(20, False)
     traced = (lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
     if a.trace_depth:  # (the last mode: traces() below reads the last timed run's rings)
         rates.update(trace_graph=[], trace_eager=[])
         traced(20, True)
         traced(20, False)
-    gr = None
+    gr = jr = None
     for _ in range(a.repeats):
         for mode in rates:
             graph = mode.endswith("graph")
             r = (push if mode.startswith("push") else cmd if mode.startswith("cmd") else
-                 traced if mode.startswith("trace") else gaited if mode.startswith("gait") else ev.run)(a.steps, graph)
+                 traced if mode.startswith("trace") else gaited if mode.startswith("gait") else
+                 jointed if mode.startswith("joints") else ev.run)(a.steps, graph)
             gr = r if mode.startswith("gait") else gr
+            jr = r if mode.startswith("joints") else jr
             assert a.device == "cpu" or r["graph"] == graph
             rates[mode].append(r["env_steps_per_s"])
     trace_doc = None
@@ -137,7 +147,7 @@ def main():
                      "record_bytes_in_per_step": n * (8 + 69 * 4 + env.num_bodies * 12 + 4 + 1 + 1),
                      "record_bytes_out_per_step": n * (304 + 4)}
     pr, cr = r if a.push_vel else None, r if a.cmd_vx else None
-    r = ev.run(a.steps) if pr or cr or a.trace_depth or a.gait else r
+    r = ev.run(a.steps) if pr or cr or a.trace_depth or a.gait or a.joints else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
                                for m, v in rates.items()},
@@ -152,6 +162,14 @@ def main():
                        # the status and reset flags
                        "record_bytes_in_per_step": n * (256 + 48 + 4 * 24 + 2),
                        "record_bytes_out_per_step": n * (256 + 48)}
+    if jr:
+        n = a.num_envs
+        doc["joints"] = {"total": jr["total"]["joints"],
+                         # what lgx_joint_record moves per step when every env records: the joint and
+                         # body records in and out, per joint its torque, dof_state pair and action,
+                         # the status and reset flags
+                         "record_bytes_in_per_step": n * (768 + 16 + 12 * 16 + 2),
+                         "record_bytes_out_per_step": n * (768 + 16)}
     if pr:
         doc["push_test"] = {k: pr[k] for k in ("speeds", "directions_deg", "push_step", "settle_tol", "total")}
         doc["push_test"]["per_speed"] = [
