@@ -154,7 +154,12 @@ int32_t lgx_s8_dx_group_aux(const lgx_s8_gemm_args* args, int32_t n, const struc
  * multiple of 4 each, zero gaps), width = its K (a multiple of 32); the actor's first-layer
  * weights use the same layout. Writes mu [B, A] (row stride ld_mu) and value [B]. 32 rows per
  * block, one block per CU; widths: actor input <= LGX_S8_ACT_MAXIN, hidden layers <=
- * LGX_S8_ACT_MAXH (actor, critic) / LGX_S8_ACT_MAXENC (encoders), <= LGX_S8_ACT_MAXL layers. */
+ * LGX_S8_ACT_MAXH (actor, critic) / LGX_S8_ACT_MAXENC (encoders), <= LGX_S8_ACT_MAXL layers.
+ * LGX_S8_ACT_MAXH = 512 is also the limit of EVERY layer's N, the chains' last layers included (mu
+ * without the act head, an encoder's output part): a block covers 32 tiles of 16 columns, and a
+ * wider layer is rejected (lgx_s8_act_last_error names the limit). `nets` 1 and 2 and the in-kernel
+ * encoder mode (n_est > 0) have no Python caller; tests/test_gpu_s8_act_ref.py covers them, and the
+ * rest of this ABI, against an fp64 reference. */
 #define LGX_S8_ACT_ROWS 32
 #define LGX_S8_ACT_MAXIN 640
 #define LGX_S8_ACT_MAXH 512

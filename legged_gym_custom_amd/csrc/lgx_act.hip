@@ -51,6 +51,7 @@ constexpr int XF = R * XP;                              // floats
 constexpr int YF = R * YP > 2 * R * SP ? R * YP : 2 * R * SP;
 constexpr int LDS_BYTES = (XF + YF) * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
+static_assert(LGX_S8_ACT_MAXH == 16 * 4 * NWV, "layer<4>: 4 tiles of 16 columns per wave is the widest layer");
 
 __device__ __forceinline__ float elu(float v) {  // lgx_mlp.hip's / lgx_s8.hip's ELU
   float q = fmaf(v, 1.f / 40320.f, 1.f / 5040.f);
@@ -510,6 +511,9 @@ static int check_chain(const lgx_s8_act_layer* L, int n, int k_in, int maxh, con
         (((uintptr_t)L[i].W) & 15))
       return afail(what);
     if (i < n - 1 && L[i].N > maxh) return afail(what);
+    // every layer, the last one too: a block covers 4 tiles per wave (layer<4>), 512 columns
+    if (L[i].N > LGX_S8_ACT_MAXH)
+      return afail("lgx_s8_act: a layer is wider than LGX_S8_ACT_MAXH = 512 columns (the 32 tiles a block covers)");
     k = L[i].N;
   }
   return 0;

@@ -3,7 +3,8 @@ the grouped launches (PPO.use_fused_act False), same parameters and injected noi
 24-step rollout of every learner case: actions, mu, sigma, log-probs and values in the storage
 (fp32: the same 3 x bf16 products; the actor's first layer sums its segmented input in a
 different order: rtol 1e-5, atol 1e-5 on values of order 1), and the observation rows it writes (bit for bit). Plus: the weights are refreshed at each rollout's first step
-(after an update the fused path follows the new weights), and the ABI rejects bad layouts."""
+(after an update the fused path follows the new weights), and the ABI rejects bad layouts.
+The kernel against an fp64 reference through its raw ABI, at its edge shapes: tests/test_gpu_s8_act_ref.py."""
 import pytest
 import torch
 
