@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 13
+#define LGX_ABI_VERSION 14
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -60,6 +60,9 @@ extern "C" {
 #define LGX_JOINT_COLS 16         /* per-env per-joint record columns (lgx_joint_buffers.joint) */
 #define LGX_JOINT_BODY_COLS 4     /* per-env record columns (lgx_joint_buffers.body) */
 #define LGX_JOINT_CELL_COLS 246   /* per-cell joint columns: 6 + LGX_MAX_DOF * 20 (lgx_joint_buffers.cells) */
+#define LGX_CONTACT_COLS 12       /* per-env per-body record columns (lgx_contact_buffers.body) */
+#define LGX_CONTACT_ENV_COLS 8    /* per-env record columns (lgx_contact_buffers.env) */
+#define LGX_CONTACT_CELL_COLS 320 /* per-cell contact columns: 8 + LGX_MAX_BODIES * 13 (lgx_contact_buffers.cells) */
 
 /* task flavour: which post_physics_step / compute_observations the step follows */
 enum lgx_task_kind {
@@ -252,7 +255,10 @@ typedef struct lgx_buffers {
   /* physics state (the reference's gym state tensors, legged_robot.py:640-646) */
   float* root_states;          /* [N,13] pos, quat xyzw, world lin vel, world ang vel */
   float* dof_state;            /* [N,D,2] pos, vel */
-  float* contact_forces;       /* [N,B,3] world-frame net contact force per body */
+  float* contact_forces;       /* [N,B,3] world-frame net contact force per body. A step which resets an env leaves
+                                  its contact_forces row as the physics of that step wrote it (the reset rewrites
+                                  the root and joint state only): at the step that ends an episode the row holds
+                                  the forces that ended it (lgx_contact_record's terminal columns rest on this) */
   float* rigid_body_states;    /* [N,B,13] */
   /* actuation */
   const float* actions_in;     /* [N,A] raw policy actions */
@@ -718,6 +724,96 @@ int lgx_joint_record(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream
  * hence exact. A cell outside the grid is never used as an index: such envs are counted in
  * *overflow, and cells are then left unwritten (the host backend fails the call instead). */
 int lgx_joint_reduce(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream);
+/* ABI 14. Contact record: where the robot touches the world: per body the contact share, onsets,
+ * impulse, peak force, hits on vertical faces, the height above the terrain and the terrain relief
+ * at contact onsets (footholds on an edge); per env the collision reward's raw count and, for an env
+ * that fell, which body ended the episode. For the env's FIRST episode since lgx_contact_begin (the
+ * rule of lgx_eval_buffers.status), then reduced per cell. Stand-alone like the gait and joint-load
+ * records: buffers and a status array of its own, one launch per step; lgx_eval_buffers and the step
+ * are untouched. The reference has no counterpart. Buffers are the caller's, in the env's memory
+ * space (device, or host for device < 0). */
+typedef struct lgx_contact_buffers {
+  float* body;       /* [N, LGX_MAX_BODIES, LGX_CONTACT_COLS] per-env per-body record, 16-byte aligned, columns below */
+  float* env;        /* [N, LGX_CONTACT_ENV_COLS] per-env record, 16-byte aligned */
+  uint8_t* status;   /* [N] 0 recording, 1 timed out, 2 fell, 3 blew up: the lgx_eval_buffers.status rule */
+  double* cells;     /* [cell_rows*cell_cols, LGX_CONTACT_CELL_COLS], written by lgx_contact_reduce */
+  uint32_t* overflow;/* [1] written by lgx_contact_reduce, as lgx_eval_buffers.overflow */
+  int32_t cell_rows, cell_cols;
+  const int32_t* cell_ids; /* [N] optional: the same meaning and range rule as lgx_gait_buffers.cell_ids */
+  float edge_tol;    /* m: an onset is "on an edge" when the terrain relief under the body exceeds it */
+} lgx_contact_buffers;
+int64_t lgx_sizeof_contact_buffers(void);
+/* All three are stream-ordered, never synchronise the host and can be captured in a hipGraph. Each
+ * refuses (naming the culprit) a NULL body, env, status or overflow (lgx_contact_reduce: also cells), a
+ * body or env that is not 16-byte aligned (the kernel moves a body's record as three 16-byte accesses
+ * and env as two), cell_rows or cell_cols < 1 or their product above 2^20, an edge_tol that is
+ * negative or not finite, an unbound contact_forces, rigid_body_states, reset or time_out, a
+ * num_bodies outside [0, LGX_MAX_BODIES], a feet_idx, termination_idx or penalised_idx outside the
+ * bodies (or an n_termination / n_penalised outside its array), and, for a mesh_type other than
+ * plane, an unbound height_samples or an hf_rows / hf_cols below 3; blew_up, terrain_levels and
+ * terrain_types are optional.
+ * lgx_contact_begin: zero body, status and overflow and set every env row to 0, 0, 0, 0, -1, 0, -1, 0
+ * (one fill launch, no memset). */
+int lgx_contact_begin(lgx_env* env, const lgx_contact_buffers* cb, void* hip_stream);
+/* After each lgx_step(_dev), on the bound buffers as that step left them. For every env e with
+ * status[e] == 0, in fp32 without contraction:
+ *   reset[e]: status[e] = 3 if blew_up is bound and set, else 1 if time_out[e], else 2; no sample. If
+ *   the new status is 2, the terminal env columns 4..7 below are written from contact_forces[e] as it
+ *   stands (see lgx_buffers.contact_forces); else they keep their lgx_contact_begin values.
+ *   else one sample. first = (env[e][0] == 0), read before anything is written; dt = params.dt. For
+ *   body b < num_bodies: F = contact_forces[e][b], (x, y, z) = rigid_body_states[e][b][0..2],
+ *     fn = sqrtf(F.x^2 + F.y^2 + F.z^2) (the step's own norm: the collision reward and the termination
+ *     check see the same bits), fh = sqrtf(F.x^2 + F.y^2), c = fn > 0.1f (the collision reward's
+ *     rule), hard = fn > 1.0f (the termination rule), r = body[e][b], onset = c && (first || r0 == 0).
+ *   Terrain under the body. mesh_type plane: h = 0, relief = 0. Else, hs = height_samples:
+ *     ix = (long)((x + border_size) / horizontal_scale) clamped to [0, hf_rows - 2], iy likewise from y
+ *     and hf_cols (the index arithmetic of the step's height scan), h = vertical_scale *
+ *     min(hs[ix][iy], hs[ix+1][iy], hs[ix][iy+1]); relief (evaluated only at an onset) = vertical_scale *
+ *     (max - min) of the nine samples hs[cx-1..cx+1][cy-1..cy+1], cx = clamp(ix, 1, hf_rows - 2), cy =
+ *     clamp(iy, 1, hf_cols - 2), the difference formed in int before the one float multiply.
+ *   Body columns:
+ *     0   = c                                  state: in contact at the last sample
+ *     1   += c                                 contact samples
+ *     2   += onset                             contact onsets
+ *     3   += c ? fn*dt : 0                     impulse, N s
+ *     4   = max(r4, fn)                        peak force
+ *     5   += c && fh > 5*fabsf(F.z)            samples hit on a vertical face (the feet_stumble rule)
+ *     6   += z - h                             for the mean height above the terrain
+ *     7   = first ? z - h : min(r7, z - h)     lowest height above the terrain
+ *     8   += onset && relief > edge_tol        onsets on an edge
+ *     9   += onset ? relief : 0                for the mean relief at onsets
+ *     10  = onset ? max(r10, relief) : r10     largest relief at an onset
+ *     11  += hard                              samples over the termination threshold
+ *   Body slots b >= num_bodies stay zero.
+ *   Env columns ("non-foot": a body not in feet_idx[0..num_feet)):
+ *     0   += 1                                 samples
+ *     1   += the number of entries i < n_penalised whose body penalised_idx[i] has c (the collision
+ *            reward's raw value)
+ *     2   += whether any non-foot body has c
+ *     3   = max(env3, fn of every non-foot body)
+ *     4   terminal: the termination_idx body with the largest fn among those with fn > 1.0f, the
+ *         lowest body index winning a tie; -1 if none (ended by orientation or by falling out)
+ *     5   terminal: that body's fn (0 if none)
+ *     6   terminal: the non-foot body with the largest fn among those with fn > 0, the lowest body
+ *         index winning a tie; -1 if none
+ *     7   terminal: the number of entries i < n_termination whose body has fn > 1.0f
+ *   (Larger fn first, then the lower index, is a total order: the result does not depend on the order
+ *   in which the bodies are compared.)
+ * Envs with status != 0 are never written again. */
+int lgx_contact_record(lgx_env* env, const lgx_contact_buffers* cb, void* hip_stream);
+/* cells[cell], over the cell's finished envs (status != 0), the cell being cell_ids[e] if set, else
+ * terrain_levels[e] * cell_cols + terrain_types[e] (cell 0 for an unbound one): [0] = the number of
+ * such envs, [1..3] = sums of env columns 0..2, [4] = max of env column 3, [5] = the number fallen
+ * (status 2), [6] = the fallen with env column 4 < 0, [7] = the sum of env column 7 over the fallen;
+ * per body b at [8 + 13 b + k]: k = 0..7 = sums of body columns 1, 2, 3, 5, 6, 8, 9, 11, k = 8, 9 = max
+ * of body columns 4 and 10, k = 10 = min of body column 7 over the envs with env column 0 > 0 (0 when
+ * there is none), k = 11 = the fallen with env column 4 == b, k = 12 = the fallen with env column
+ * 6 == b. A cell with no finished env is all zero. The sums: fp64, the fixed tree of lgx_eval_reduce,
+ * no floating-point atomics: two calls on the same records give bit-identical cells; the maxima and
+ * minima are order-independent, hence exact. A cell outside the grid is never used as an index: such
+ * envs are counted in *overflow, and cells are then left unwritten (the host backend fails the call
+ * instead). */
+int lgx_contact_reduce(lgx_env* env, const lgx_contact_buffers* cb, void* hip_stream);
 const char* lgx_last_error(const lgx_env* env);
 void lgx_destroy(lgx_env* env);
 

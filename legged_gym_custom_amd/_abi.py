@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -34,6 +34,9 @@ GAIT_CELL_COLS = 61  # per-cell gait columns: 1 + 12 + MAX_FEET * 12 (lgx_gait_b
 JOINT_COLS = 16      # per-env per-joint record columns (lgx_joint_buffers.joint)
 JOINT_BODY_COLS = 4  # per-env record columns (lgx_joint_buffers.body)
 JOINT_CELL_COLS = 246  # per-cell joint columns: 6 + MAX_DOF * 20 (lgx_joint_buffers.cells)
+CONTACT_COLS = 12      # per-env per-body record columns (lgx_contact_buffers.body)
+CONTACT_ENV_COLS = 8   # per-env record columns (lgx_contact_buffers.env)
+CONTACT_CELL_COLS = 320  # per-cell contact columns: 8 + MAX_BODIES * 13 (lgx_contact_buffers.cells)
 
 TASK_LEGGED = 0
 TASK_GO2 = 1
@@ -180,9 +183,15 @@ class JointBuffers(C.Structure):
                 ("cell_cols", i32), ("cell_ids", P)]
 
 
+class ContactBuffers(C.Structure):
+    """lgx_contact_buffers (ABI 14): the contact record's per-env per-body records and per-cell sums."""
+    _fields_ = [("body", P), ("env", P), ("status", P), ("cells", P), ("overflow", P), ("cell_rows", i32),
+                ("cell_cols", i32), ("cell_ids", P), ("edge_tol", f32)]
+
+
 STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buffers,
            "lgx_eval_buffers": EvalBuffers, "lgx_trace_buffers": TraceBuffers, "lgx_gait_buffers": GaitBuffers,
-           "lgx_joint_buffers": JointBuffers}
+           "lgx_joint_buffers": JointBuffers, "lgx_contact_buffers": ContactBuffers}
 SIZEOF = {"lgx_sizeof_" + name[len("lgx_"):]: name for name in STRUCTS}  # sizeof export -> typedef
 
 CONSTANTS = {
@@ -197,6 +206,8 @@ CONSTANTS = {
     "LGX_TRACE_COLS": TRACE_COLS,
     "LGX_GAIT_FOOT_COLS": GAIT_FOOT_COLS, "LGX_GAIT_BODY_COLS": GAIT_BODY_COLS, "LGX_GAIT_CELL_COLS": GAIT_CELL_COLS,
     "LGX_JOINT_COLS": JOINT_COLS, "LGX_JOINT_BODY_COLS": JOINT_BODY_COLS, "LGX_JOINT_CELL_COLS": JOINT_CELL_COLS,
+    "LGX_CONTACT_COLS": CONTACT_COLS, "LGX_CONTACT_ENV_COLS": CONTACT_ENV_COLS,
+    "LGX_CONTACT_CELL_COLS": CONTACT_CELL_COLS,
     "LGX_TASK_LEGGED": TASK_LEGGED, "LGX_TASK_GO2": TASK_GO2,
     "LGX_MESH_PLANE": MESH_PLANE, "LGX_MESH_HEIGHTFIELD": MESH_HEIGHTFIELD, "LGX_MESH_TRIMESH": MESH_TRIMESH,
     **{"LGX_CONTROL_" + name: v for name, v in CONTROL.items()},
@@ -230,6 +241,9 @@ SIGNATURES = {
     "lgx_joint_begin": (cint, (P, P, P)),
     "lgx_joint_record": (cint, (P, P, P)),
     "lgx_joint_reduce": (cint, (P, P, P)),
+    "lgx_contact_begin": (cint, (P, P, P)),
+    "lgx_contact_record": (cint, (P, P, P)),
+    "lgx_contact_reduce": (cint, (P, P, P)),
     "lgx_last_error": (C.c_char_p, (P,)),
     "lgx_destroy": (None, (P,)),
 }

@@ -256,6 +256,38 @@ class NativeEnv:
         """lgx_joint_reduce: records -> cells (and the out-of-grid count in jb.overflow)."""
         self._check(self._L.lgx_joint_reduce(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_reduce")
 
+    def contact_buffers(self, body, env, status, cells, overflow, cell_ids=None, edge_tol=0.0):
+        """lgx_contact_buffers (ABI 14) over the given tensors: body [N, 24, 12] fp32, env [N, 8] fp32,
+        status [N] uint8, cells [rows, cols, 320] float64, overflow [1] int32 and, optional, cell_ids
+        [N] int32 (the free cell key), all in the env's memory space; edge_tol: the relief (m) above
+        which a contact onset counts as on an edge."""
+        n = self.params.num_envs
+        if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.CONTACT_CELL_COLS):
+            raise LgxError(f"contact buffer cells must be [rows, cols, {_abi.CONTACT_CELL_COLS}]")
+        cb = _abi.ContactBuffers()
+        self._fill(cb, "contact buffer", [
+            ("body", body, (n, _abi.MAX_BODIES, _abi.CONTACT_COLS), "float32", True),
+            ("env", env, (n, _abi.CONTACT_ENV_COLS), "float32", True), ("status", status, (n,), "uint8", True),
+            ("cells", cells, None, "float64", True), ("overflow", overflow, (1,), "int32", True),
+            ("cell_ids", cell_ids, (n,), "int32", False)])
+        cb.cell_rows, cb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
+        cb.edge_tol = float(edge_tol)
+        cb._keep = (body, env, status, cells, overflow, cell_ids)
+        return cb
+
+    def contact_begin(self, cb, stream):
+        """lgx_contact_begin: zero the records, the statuses and the overflow count and set the env rows'
+        terminal columns to "none" (cb: contact_buffers(...))."""
+        self._check(self._L.lgx_contact_begin(self.handle, C.byref(cb), C.c_void_p(stream)), "lgx_contact_begin")
+
+    def contact_record(self, cb, stream):
+        """lgx_contact_record: one sample per recording env from the step just run."""
+        self._check(self._L.lgx_contact_record(self.handle, C.byref(cb), C.c_void_p(stream)), "lgx_contact_record")
+
+    def contact_reduce(self, cb, stream):
+        """lgx_contact_reduce: records -> cells (and the out-of-grid count in cb.overflow)."""
+        self._check(self._L.lgx_contact_reduce(self.handle, C.byref(cb), C.c_void_p(stream)), "lgx_contact_reduce")
+
     def __del__(self):
         try:
             if self.handle:

@@ -3299,6 +3299,298 @@ int lgx_joint_reduce(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream
   return 0;
 }
 
+// ------------------------------------------------------------------ contact record (ABI 14)
+namespace lgx {
+// lgx_contact_begin: body, status and overflow zero, every env row 0, 0, 0, 0, -1, 0, -1, 0 (the
+// terminal columns' "none"), in one grid-stride launch of 16-byte stores.
+__global__ __launch_bounds__(256) void contact_begin_kernel(float4* __restrict__ body, float4* __restrict__ envq,
+                                                            uint8_t* __restrict__ status,
+                                                            uint32_t* __restrict__ overflow, int N) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t nb = (size_t)N * (LGX_MAX_BODIES * LGX_CONTACT_COLS / 4), ne = (size_t)N * (LGX_CONTACT_ENV_COLS / 4);
+  for (size_t i = t; i < nb; i += stride) body[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (size_t i = t; i < ne; i += stride)
+    envq[i] = (i & 1) ? make_float4(-1.f, 0.f, -1.f, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+  for (size_t i = t; i < (size_t)N; i += stride) status[i] = 0;
+  if (t == 0) *overflow = 0;
+}
+
+// lgx_contact_record: 32 lanes per env (2 envs per wave, a group never straddles a wave), lane
+// q < num_bodies = body q; lanes from num_bodies on (24..31 at least) idle on the body part. Each
+// body lane moves its body's 12 record columns as three 16-byte accesses (48 contiguous bytes per
+// lane, the env's 1152 bytes without gaps), keeps them in registers across contact_body_sample, and
+// reads its force (12 B), its position (12 B) and three int16 terrain samples, nine more only at a
+// contact onset. The per-env part (contact_part: two counts and the two "largest fn, lowest index"
+// arg-maxima) is combined by five xor shuffles inside the group (offsets 1..16); contact_merge is a
+// total order and integer sums, so every lane ends with the same bits whatever the order. A group
+// whose env is reset in this step (and still recording) loads its forces too: the terminal columns
+// come from the same butterfly. status[e], reset[e] and env[e]'s first float4 (its column 0 is the
+// "first sample" test) are read by every lane of the group before the first store of the kernel,
+// and only lane 0 writes status and env (a sample: the first float4; a fall: the second): no lane
+// can see this launch's update. No early return before the shuffles. Per recording env: 1152 + 16 B
+// of records in and out, 24 x 24 B of sources, up to 24 x 3 (+ 9 at an onset) terrain samples and two
+// flags, about 2.4 KB. No LDS, no atomics; frozen envs store nothing, tail lanes load nothing.
+__global__ __launch_bounds__(256) void contact_record_kernel(const lgx_task_params* __restrict__ Pm,
+                                                             const lgx_buffers* __restrict__ Bd, float* body,
+                                                             float* envr, uint8_t* status, float edge_tol) {
+  const lgx_buffers& B = *Bd;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = t >> 5, q = t & 31;
+  // no early return: the shuffles below need every lane of a group
+  const bool live = e < Pm->num_envs;
+  const int st = live ? status[e] : 1;
+  const int rs = live ? B.reset[e] : 0;
+  const bool open = st == 0, sample = open && !rs;
+  const int NB = Pm->num_bodies;
+  const bool mine = open && q < NB;
+  float4* eq = reinterpret_cast<float4*>(envr + (size_t)e * LGX_CONTACT_ENV_COLS);
+  float4* bq = reinterpret_cast<float4*>(body + ((size_t)e * LGX_MAX_BODIES + q) * LGX_CONTACT_COLS);
+  float r[LGX_CONTACT_COLS], v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (sample) {
+    const float4 x = eq[0];
+    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+  }
+  contact_part p = contact_none();
+  if (mine) {
+    const size_t row = (size_t)e * NB + q;
+    const float* F = B.contact_forces + row * 3;
+    float fn;
+    if (sample) {
+      LGX_UNROLL
+      for (int i = 0; i < 3; ++i) {
+        const float4 x = bq[i];
+        r[4 * i] = x.x; r[4 * i + 1] = x.y; r[4 * i + 2] = x.z; r[4 * i + 3] = x.w;
+      }
+      const int16_t* hs = Pm->mesh_type == LGX_MESH_PLANE ? nullptr : B.height_samples;
+      fn = contact_body_sample(r, v[0] == 0.f, F, B.rigid_body_states + row * 13, Pm, hs, edge_tol);
+    } else {
+      fn = nrm3(F[0], F[1], F[2]);  // the step that ended the episode: the terminal columns
+    }
+    p = contact_body_part(Pm, q, fn);
+  }
+  LGX_UNROLL
+  for (int o = 1; o < 32; o <<= 1) {
+    contact_part other;
+    other.pen = __shfl_xor(p.pen, o, 64);
+    other.term = __shfl_xor(p.term, o, 64);
+    other.tb = __shfl_xor(p.tb, o, 64);
+    other.nb = __shfl_xor(p.nb, o, 64);
+    other.tn = __shfl_xor(p.tn, o, 64);
+    other.nn = __shfl_xor(p.nn, o, 64);
+    contact_merge(p, other);
+  }
+  if (!live || !open) return;
+  if (rs) {
+    if (q == 0) {
+      const int ns = episode_end_status(B, e);
+      status[e] = (uint8_t)ns;
+      if (ns == 2) {
+        float w[4];
+        contact_env_terminal(w, p);
+        eq[1] = make_float4(w[0], w[1], w[2], w[3]);
+      }
+    }
+    return;
+  }
+  if (mine) {
+    LGX_UNROLL
+    for (int i = 0; i < 3; ++i) bq[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+  }
+  if (q == 0) {
+    contact_env_sample(v, p);
+    eq[0] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// lgx_contact_reduce: cell_reduce (above: the block shape, the env order and the tree) in passes of
+// BP bodies. A body has 10 sums (body columns 1, 2, 3, 5, 6, 8, 9, 11 and the two fall histograms,
+// sums of (env column 4 == b) and (env column 6 == b) over the fallen, in the same scan), the env
+// part 7 (the count, env columns 0..2, the fallen, the fallen without a termination contact, env
+// column 7 over the fallen): a thread holds 10 BP + 7 fp64 partials, in one layout for every pass so
+// that they stay in registers; pass 0 stores the env part. joint_reduce_kernel's reasoning fixes BP:
+// there 35 partials fit (205 VGPRs, no spill) and 49 did not (256 VGPRs, spilling into AGPRs); three
+// bodies a pass would be 37 partials, at that edge, so BP = 2 (27 partials; VGPR count in DESIGN.md).
+// The maxima and minima ride the same scan in fp32 partials x (per body the maxima of columns 4, 10
+// and of -column 7, the last over the envs with samples only; the max of env column 3; 1 when an env
+// / an env with samples contributed), combined by fmaxf in cell_reduce's shape: order-independent,
+// hence exact; a cell without a contributing env gets zeros. Every pass scans every env's cell id in
+// the same order and forms the same out-of-grid count: no block writes its cell when there are any,
+// and block 0 publishes the count.
+__global__ __launch_bounds__(256) void contact_reduce_kernel(const float* __restrict__ body,
+                                                             const float* __restrict__ envr,
+                                                             const uint8_t* __restrict__ status,
+                                                             const int64_t* __restrict__ levels,
+                                                             const int64_t* __restrict__ types,
+                                                             const int32_t* __restrict__ cell_ids, int N, int rows,
+                                                             int cols, double* __restrict__ cells,
+                                                             uint32_t* __restrict__ overflow) {
+  constexpr int BP = 2, NS = 10, NE = 7, PER = 13, NC = NS * BP + NE, NX = 3 * BP + 3;
+  static_assert(LGX_MAX_BODIES % BP == 0, "every pass reduces BP bodies");
+  static_assert(LGX_CONTACT_CELL_COLS == 8 + LGX_MAX_BODIES * PER, "the cell layout of include/lgx.h");
+  static_assert(LGX_CONTACT_COLS == 12 && LGX_CONTACT_ENV_COLS == 8, "three and two float4");
+  __shared__ float xs[4][NX];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  double* c = cells + (size_t)blockIdx.x * LGX_CONTACT_CELL_COLS;
+  for (int pass = 0; pass < LGX_MAX_BODIES / BP; ++pass) {
+    if (pass) __syncthreads();  // the previous pass's readers are done with the exchanges
+    float x[NX];
+    LGX_UNROLL
+    for (int k = 0; k < NX; ++k) x[k] = -INFINITY;
+    const uint32_t nbad = cell_reduce<NC>(levels, types, cell_ids, N, rows, cols, [&](int e, auto& s) {
+      const int st = status[e];
+      if (st == 0) return;
+      const float4 e0 = *reinterpret_cast<const float4*>(envr + (size_t)e * LGX_CONTACT_ENV_COLS);
+      const float4 e1 = *reinterpret_cast<const float4*>(envr + (size_t)e * LGX_CONTACT_ENV_COLS + 4);
+      const bool fell = st == 2, sampled = e0.x > 0.f;
+      LGX_UNROLL
+      for (int jj = 0; jj < BP; ++jj) {
+        const int b = BP * pass + jj;
+        const float4* r4 = reinterpret_cast<const float4*>(body + ((size_t)e * LGX_MAX_BODIES + b) * LGX_CONTACT_COLS);
+        const float4 r0 = r4[0], r1 = r4[1], r2 = r4[2];
+        s[NS * jj] += (double)r0.y;       // column 1
+        s[NS * jj + 1] += (double)r0.z;   // 2
+        s[NS * jj + 2] += (double)r0.w;   // 3
+        s[NS * jj + 3] += (double)r1.y;   // 5
+        s[NS * jj + 4] += (double)r1.z;   // 6
+        s[NS * jj + 5] += (double)r2.x;   // 8
+        s[NS * jj + 6] += (double)r2.y;   // 9
+        s[NS * jj + 7] += (double)r2.w;   // 11
+        s[NS * jj + 8] += fell && e1.x == (float)b ? 1.0 : 0.0;
+        s[NS * jj + 9] += fell && e1.z == (float)b ? 1.0 : 0.0;
+        x[3 * jj] = fmaxf(x[3 * jj], r1.x);          // column 4
+        x[3 * jj + 1] = fmaxf(x[3 * jj + 1], r2.z);  // column 10
+        if (sampled) x[3 * jj + 2] = fmaxf(x[3 * jj + 2], -r1.w);  // column 7
+      }
+      s[NS * BP] += 1.0;
+      s[NS * BP + 1] += (double)e0.x;
+      s[NS * BP + 2] += (double)e0.y;
+      s[NS * BP + 3] += (double)e0.z;
+      s[NS * BP + 4] += fell ? 1.0 : 0.0;
+      s[NS * BP + 5] += fell && e1.x < 0.f ? 1.0 : 0.0;
+      s[NS * BP + 6] += fell ? (double)e1.w : 0.0;
+      x[3 * BP] = fmaxf(x[3 * BP], e0.w);
+      x[3 * BP + 1] = 1.0f;
+      if (sampled) x[3 * BP + 2] = 1.0f;
+    }, [=](int k, double v) {
+      if (k < NS * BP) {
+        const int kk = k % NS;
+        c[8 + PER * (BP * pass + k / NS) + (kk < 8 ? kk : kk + 3)] = v;
+      } else if (pass == 0) {
+        const int i = k - NS * BP;  // cells 0, 1, 2, 3, 5, 6, 7 (4 is the maximum below)
+        c[i < 4 ? i : i + 1] = v;
+      }
+    });
+    if (pass == 0 && tid == 0 && blockIdx.x == 0) *overflow = nbad;
+    if (nbad != 0) return;  // (uniform over the block)
+    for (int o = 32; o > 0; o >>= 1) {
+      LGX_UNROLL
+      for (int k = 0; k < NX; ++k) x[k] = fmaxf(x[k], __shfl_down(x[k], o, 64));
+    }
+    if (lane == 0) {
+      LGX_UNROLL
+      for (int k = 0; k < NX; ++k) xs[wv][k] = x[k];
+    }
+    __syncthreads();
+    if (tid < 3 * BP || (tid == 3 * BP && pass == 0)) {
+      const int flag = (tid < 3 * BP && tid % 3 == 2) ? NX - 1 : NX - 2;
+      const bool some = fmaxf(fmaxf(xs[0][flag], xs[1][flag]), fmaxf(xs[2][flag], xs[3][flag])) > 0.f;
+      const float m = fmaxf(fmaxf(xs[0][tid], xs[1][tid]), fmaxf(xs[2][tid], xs[3][tid]));
+      const double v = !some ? 0.0 : (double)(flag == NX - 1 ? -m : m);
+      if (tid < 3 * BP) c[8 + PER * (BP * pass + tid / 3) + 8 + tid % 3] = v;
+      else c[4] = v;
+    }
+  }
+}
+}  // namespace lgx
+
+// shared checks of the three lgx_contact_* calls
+static int contact_check(lgx_env* env, const lgx_contact_buffers* cb, const char* what, bool reduce) {
+  const std::string w(what);
+  if (int rc = check_call(env, cb, w, "contact")) return rc;
+  if (!cb->body) return fail(env, w + ": body is NULL");
+  if ((uintptr_t)cb->body % 16 != 0) return fail(env, w + ": body must be 16-byte aligned");
+  if (!cb->env) return fail(env, w + ": env is NULL");
+  if ((uintptr_t)cb->env % 16 != 0) return fail(env, w + ": env must be 16-byte aligned");
+  if (!cb->status) return fail(env, w + ": status is NULL");
+  if (!cb->overflow) return fail(env, w + ": overflow is NULL");
+  if (reduce && !cb->cells) return fail(env, w + ": cells is NULL");
+  if (cb->cell_rows < 1 || cb->cell_cols < 1 || (int64_t)cb->cell_rows * cb->cell_cols > (1 << 20))
+    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  if (!std::isfinite(cb->edge_tol) || cb->edge_tol < 0.f)
+    return fail(env, w + ": edge_tol must be finite and not negative");
+  const lgx_buffers& b = env->buffers;
+  if (int rc = check_bound(env, w, kNotBound, {{"contact_forces", b.contact_forces},
+                                               {"rigid_body_states", b.rigid_body_states},
+                                               {"reset", b.reset}, {"time_out", b.time_out}}))
+    return rc;
+  const lgx_task_params& p = env->params;
+  if (p.num_bodies < 0 || p.num_bodies > LGX_MAX_BODIES) return fail(env, w + ": num_bodies outside [0, LGX_MAX_BODIES]");
+  if (int rc = check_feet(env, w)) return rc;
+  if (p.n_termination < 0 || p.n_termination > LGX_MAX_TERMINATION)
+    return fail(env, w + ": n_termination outside termination_idx");
+  for (int i = 0; i < p.n_termination; ++i)
+    if (p.termination_idx[i] < 0 || p.termination_idx[i] >= p.num_bodies)
+      return fail(env, w + ": termination_idx outside the bodies");
+  if (p.n_penalised < 0 || p.n_penalised > LGX_MAX_PENALISED)
+    return fail(env, w + ": n_penalised outside penalised_idx");
+  for (int i = 0; i < p.n_penalised; ++i)
+    if (p.penalised_idx[i] < 0 || p.penalised_idx[i] >= p.num_bodies)
+      return fail(env, w + ": penalised_idx outside the bodies");
+  if (p.mesh_type != LGX_MESH_PLANE) {
+    if (!b.height_samples) return fail(env, w + kNotBound + "height_samples (the mesh is not a plane)");
+    if (p.hf_rows < 3 || p.hf_cols < 3) return fail(env, w + ": hf_rows and hf_cols must be >= 3");
+  }
+  return 0;
+}
+
+int64_t lgx_sizeof_contact_buffers(void) { return (int64_t)sizeof(lgx_contact_buffers); }
+
+int lgx_contact_begin(lgx_env* env, const lgx_contact_buffers* cb, void* hip_stream) {
+  if (int rc = contact_check(env, cb, "lgx_contact_begin", false)) return rc;
+  if (env->host) {
+    lgxh::contact_begin(&env->params, cb);
+    return 0;
+  }
+  const int N = env->params.num_envs;
+  const int64_t quads = (int64_t)N * (LGX_MAX_BODIES * LGX_CONTACT_COLS / 4);
+  const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((quads + 255) / 256, 1), 2048);
+  hipLaunchKernelGGL(lgx::contact_begin_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream,
+                     reinterpret_cast<float4*>(cb->body), reinterpret_cast<float4*>(cb->env), cb->status, cb->overflow, N);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int lgx_contact_record(lgx_env* env, const lgx_contact_buffers* cb, void* hip_stream) {
+  if (int rc = contact_check(env, cb, "lgx_contact_record", false)) return rc;
+  if (env->host) {
+    lgxh::contact_record(&env->params, &env->buffers, cb);
+    return 0;
+  }
+  const int64_t threads = (int64_t)env->params.num_envs * 32;
+  if (threads == 0) return 0;
+  hipLaunchKernelGGL(lgx::contact_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)hip_stream, env->d_params, env->d_buffers, cb->body, cb->env, cb->status,
+                     cb->edge_tol);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int lgx_contact_reduce(lgx_env* env, const lgx_contact_buffers* cb, void* hip_stream) {
+  if (int rc = contact_check(env, cb, "lgx_contact_reduce", true)) return rc;
+  if (env->host) {
+    const int bad = lgxh::contact_reduce(&env->params, &env->buffers, cb);
+    if (bad) return fail(env, "lgx_contact_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
+                              "outside the cell grid (cells not written)");
+    return 0;
+  }
+  const lgx_buffers& b = env->buffers;
+  hipLaunchKernelGGL(lgx::contact_reduce_kernel, dim3((unsigned)(cb->cell_rows * cb->cell_cols)), dim3(256), 0,
+                     (hipStream_t)hip_stream, cb->body, cb->env, cb->status, b.terrain_levels, b.terrain_types,
+                     cb->cell_ids, env->params.num_envs, cb->cell_rows, cb->cell_cols, cb->cells, cb->overflow);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 #ifdef LGX_PHASE_CLOCK
 // dev builds only: per-env phase cycle counters ([num_envs][16] uint32, device memory)
 int lgx_debug_phase_buffer(uint32_t* dev_ptr) {

@@ -492,6 +492,117 @@ LGX_HD void joint_body_sample(float* b, float P, bool sat, bool out) {
   b[3] += out ? 1.0f : 0.f;
 }
 
+// Contact record (lgx_contact_buffers, include/lgx.h ABI 14). The terrain height under (x, y): the
+// index arithmetic of the step's height scan (get_heights), every index clamped before use; ix, iy:
+// the clamped cell, for contact_relief. hs == nullptr (a plane): 0.
+LGX_HD float contact_terrain_height(const lgx_task_params* Pm, const int16_t* hs, float x, float y, long& ix,
+                                    long& iy) {
+  ix = iy = 0;
+  if (hs == nullptr) return 0.f;
+  const float px = x + Pm->border_size, py = y + Pm->border_size;
+  ix = (long)(px / Pm->horizontal_scale);
+  iy = (long)(py / Pm->horizontal_scale);
+  ix = ix < 0 ? 0 : (ix > Pm->hf_rows - 2 ? Pm->hf_rows - 2 : ix);
+  iy = iy < 0 ? 0 : (iy > Pm->hf_cols - 2 ? Pm->hf_cols - 2 : iy);
+  const int16_t h1 = hs[ix * Pm->hf_cols + iy];
+  const int16_t h2 = hs[(ix + 1) * Pm->hf_cols + iy];
+  const int16_t h3 = hs[ix * Pm->hf_cols + iy + 1];
+  int16_t h = h1 < h2 ? h1 : h2;
+  h = h < h3 ? h : h3;
+  return (float)h * Pm->vertical_scale;
+}
+// The terrain relief around the cell (ix, iy) of contact_terrain_height: max - min of the nine
+// samples around the cell moved into [1, rows - 2] x [1, cols - 2] (hf_rows, hf_cols >= 3: checked
+// by the calls), the difference in int before the one float multiply.
+LGX_HD float contact_relief(const lgx_task_params* Pm, const int16_t* hs, long ix, long iy) {
+  if (hs == nullptr) return 0.f;
+  const long cx = ix < 1 ? 1 : (ix > Pm->hf_rows - 2 ? Pm->hf_rows - 2 : ix);
+  const long cy = iy < 1 ? 1 : (iy > Pm->hf_cols - 2 ? Pm->hf_cols - 2 : iy);
+  int lo = 32767, hi = -32768;
+  LGX_UNROLL
+  for (int i = -1; i <= 1; ++i) {
+    LGX_UNROLL
+    for (int j = -1; j <= 1; ++j) {
+      const int v = hs[(cx + i) * Pm->hf_cols + (cy + j)];
+      lo = v < lo ? v : lo;
+      hi = v > hi ? v : hi;
+    }
+  }
+  return (float)(hi - lo) * Pm->vertical_scale;
+}
+// One sample of one body: the 12 record columns r (in registers in the kernel, in place on the
+// host) from its contact force F and its position X (rigid-body row columns 0-2); first: the env's
+// first sample; hs: height_samples, nullptr for a plane. Returns fn. The rule text of
+// lgx_contact_record.
+LGX_HD float contact_body_sample(float* r, bool first, const float* F, const float* X,
+                                 const lgx_task_params* Pm, const int16_t* hs, float edge_tol) {
+  const float fn = nrm3(F[0], F[1], F[2]), fh = nrm2(F[0], F[1]);
+  const bool c = fn > 0.1f, onset = c && (first || r[0] == 0.f);
+  long ix, iy;
+  const float dz = X[2] - contact_terrain_height(Pm, hs, X[0], X[1], ix, iy);
+  r[0] = c ? 1.0f : 0.f;
+  r[1] += c ? 1.0f : 0.f;
+  r[3] += c ? fn * Pm->dt : 0.f;
+  r[4] = fmaxf(r[4], fn);
+  r[5] += c && fh > 5.0f * fabsf(F[2]) ? 1.0f : 0.f;
+  r[6] += dz;
+  r[7] = first ? dz : fminf(r[7], dz);
+  if (onset) {
+    const float relief = contact_relief(Pm, hs, ix, iy);
+    r[2] += 1.0f;
+    r[8] += relief > edge_tol ? 1.0f : 0.f;
+    r[9] += relief;
+    r[10] = fmaxf(r[10], relief);
+  }
+  r[11] += fn > 1.0f ? 1.0f : 0.f;
+  return fn;
+}
+// What the bodies of an env contribute to its env columns: pen / term: the entries of penalised_idx
+// with c / of termination_idx with fn > 1; (tn, tb): the hardest-hit termination body over 1 N;
+// (nn, nb): the hardest-hit non-foot body with fn > 0; (0, -1): none. contact_merge is associative
+// and commutative (integer sums, trace_peak_merge's total order), so the kernel's xor butterfly and
+// the host's loop over the bodies agree.
+struct contact_part {
+  int pen, term, tb, nb;
+  float tn, nn;
+};
+LGX_HD contact_part contact_none() { return contact_part{0, 0, -1, -1, 0.f, 0.f}; }
+LGX_HD contact_part contact_body_part(const lgx_task_params* Pm, int b, float fn) {
+  contact_part p = contact_none();
+  bool term = false;
+  for (int i = 0; i < Pm->n_penalised; ++i) p.pen += (Pm->penalised_idx[i] == b && fn > 0.1f) ? 1 : 0;
+  for (int i = 0; i < Pm->n_termination; ++i) term = term || Pm->termination_idx[i] == b;
+  for (int i = 0; i < Pm->n_termination; ++i) p.term += (Pm->termination_idx[i] == b && fn > 1.0f) ? 1 : 0;
+  if (term && fn > 1.0f) {
+    p.tn = fn;
+    p.tb = b;
+  }
+  if (!trace_is_foot(Pm, b) && fn > 0.f) {
+    p.nn = fn;
+    p.nb = b;
+  }
+  return p;
+}
+LGX_HD void contact_merge(contact_part& a, const contact_part& o) {
+  a.pen += o.pen;
+  a.term += o.term;
+  trace_peak_merge(a.tn, a.tb, o.tn, o.tb);
+  trace_peak_merge(a.nn, a.nb, o.nn, o.nb);
+}
+// Env columns 0..3 after a sample, and the terminal columns 4..7 of an env that fell.
+LGX_HD void contact_env_sample(float* v, const contact_part& p) {
+  v[0] += 1.0f;
+  v[1] += (float)p.pen;
+  v[2] += p.nn > 0.1f ? 1.0f : 0.f;  // (the largest non-foot fn is over 0.1 iff any non-foot body has c)
+  v[3] = fmaxf(v[3], p.nn);
+}
+LGX_HD void contact_env_terminal(float* v, const contact_part& p) {
+  v[0] = (float)p.tb;
+  v[1] = p.tn;
+  v[2] = (float)p.nb;
+  v[3] = (float)p.term;
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];

@@ -1388,6 +1388,124 @@ int joint_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint
   return 0;
 }
 
+void contact_begin(const lgx_task_params* P, const lgx_contact_buffers* C) {
+  const size_t N = (size_t)P->num_envs;
+  std::fill(C->body, C->body + N * LGX_MAX_BODIES * LGX_CONTACT_COLS, 0.f);
+  for (size_t e = 0; e < N; ++e) {
+    float* v = C->env + e * LGX_CONTACT_ENV_COLS;
+    v[0] = v[1] = v[2] = v[3] = v[5] = v[7] = 0.f;
+    v[4] = v[6] = -1.0f;  // the terminal columns' "none"
+  }
+  std::fill(C->status, C->status + N, (uint8_t)0);
+  *C->overflow = 0;
+}
+
+// lgx_contact_record (include/lgx.h): the kernel's arithmetic (lgx_env.hip contact_record_kernel),
+// the bodies in order
+void contact_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_contact_buffers* C) {
+  const int N = P->num_envs, NB = P->num_bodies;
+  const int16_t* hs = P->mesh_type == LGX_MESH_PLANE ? nullptr : B->height_samples;
+#pragma omp parallel for schedule(static)
+  for (int e = 0; e < N; ++e) {
+    if (C->status[e] != 0) continue;
+    float* v = C->env + (size_t)e * LGX_CONTACT_ENV_COLS;
+    const bool rs = B->reset[e] != 0, first = v[0] == 0.f;
+    contact_part p = contact_none();
+    for (int b = 0; b < NB; ++b) {
+      const size_t row = (size_t)e * NB + b;
+      const float* F = B->contact_forces + row * 3;
+      const float fn = rs ? nrm3(F[0], F[1], F[2])
+                          : contact_body_sample(C->body + ((size_t)e * LGX_MAX_BODIES + b) * LGX_CONTACT_COLS, first, F,
+                                                B->rigid_body_states + row * 13, P, hs, C->edge_tol);
+      contact_merge(p, contact_body_part(P, b, fn));
+    }
+    if (rs) {
+      const int ns = episode_end_status(*B, e);
+      C->status[e] = (uint8_t)ns;
+      if (ns == 2) contact_env_terminal(v + 4, p);
+    } else {
+      contact_env_sample(v, p);
+    }
+  }
+}
+
+// lgx_contact_reduce; returns the number of envs outside the cell grid (cells are written only when
+// it is 0, overflow always is). The sums are formed by cell_reduce's tree (lgx_env.hip), so that both
+// backends give the same bits from the same records: "thread" t = e % 256 adds the cell's envs t,
+// t + 256, ... in increasing order into its own fp64 partials, the 64 partials of each "wave" are
+// folded by the shuffle-down steps 32, 16, ..., 1, and the four wave results are added in wave order.
+// The maxima and minima do not depend on the order.
+static double contact_tree(const double* part, int k) {
+  double w[4];
+  for (int wv = 0; wv < 4; ++wv) {
+    double s[64];
+    for (int l = 0; l < 64; ++l) s[l] = part[(size_t)(64 * wv + l) * LGX_CONTACT_CELL_COLS + k];
+    for (int o = 32; o > 0; o >>= 1)
+      for (int l = 0; l < o; ++l) s[l] += s[l + o];
+    w[wv] = s[0];
+  }
+  return ((w[0] + w[1]) + w[2]) + w[3];
+}
+
+int contact_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_contact_buffers* C) {
+  const int N = P->num_envs, rows = C->cell_rows, cols = C->cell_cols;
+  if (int bad = reduce_begin(B, C->cell_ids, N, rows, cols, C->overflow, {{C->cells, LGX_CONTACT_CELL_COLS}})) return bad;
+  constexpr int PER = 13, NCOL = LGX_CONTACT_CELL_COLS;
+  static const int kSum[8] = {1, 2, 3, 5, 6, 8, 9, 11};
+  // the finished envs by cell, in env order (a counting sort)
+  std::vector<int> cell(N, -1), start((size_t)rows * cols + 1, 0), order;
+  for (int e = 0; e < N; ++e) {
+    if (C->status[e] == 0) continue;
+    cell[e] = cell_of_env(B->terrain_levels, B->terrain_types, C->cell_ids, e, rows, cols);
+    ++start[cell[e] + 1];
+  }
+  for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
+  order.resize(start.back());
+  {
+    std::vector<int> at(start.begin(), start.end() - 1);
+    for (int e = 0; e < N; ++e)
+      if (cell[e] >= 0) order[at[cell[e]]++] = e;
+  }
+  std::vector<double> part((size_t)256 * NCOL);
+  for (int id = 0; id < rows * cols; ++id) {
+    if (start[id] == start[id + 1]) continue;  // (an empty cell stays all zero)
+    double* cl = C->cells + (size_t)id * NCOL;
+    std::fill(part.begin(), part.end(), 0.0);
+    bool init = true, init7 = true;  // the cell's first env / first env with samples sets the extremes
+    for (int i = start[id]; i < start[id + 1]; ++i) {
+      const int e = order[i], st = C->status[e];
+      const float* v = C->env + (size_t)e * LGX_CONTACT_ENV_COLS;
+      double* p = part.data() + (size_t)(e & 255) * NCOL;
+      const bool fell = st == 2, has = v[0] > 0.f;
+      const auto hi = [init](double& m, float x) { m = init ? (double)x : std::max(m, (double)x); };
+      p[0] += 1.0;
+      for (int k = 0; k < 3; ++k) p[1 + k] += (double)v[k];
+      hi(cl[4], v[3]);
+      p[5] += fell ? 1.0 : 0.0;
+      p[6] += fell && v[4] < 0.f ? 1.0 : 0.0;
+      p[7] += fell ? (double)v[7] : 0.0;
+      for (int b = 0; b < LGX_MAX_BODIES; ++b) {
+        const float* r = C->body + ((size_t)e * LGX_MAX_BODIES + b) * LGX_CONTACT_COLS;
+        double *pb = p + 8 + PER * b, *cb = cl + 8 + PER * b;
+        for (int k = 0; k < 8; ++k) pb[k] += (double)r[kSum[k]];
+        hi(cb[8], r[4]);
+        hi(cb[9], r[10]);
+        if (has) cb[10] = init7 ? (double)r[7] : std::min(cb[10], (double)r[7]);
+        pb[11] += fell && v[4] == (float)b ? 1.0 : 0.0;
+        pb[12] += fell && v[6] == (float)b ? 1.0 : 0.0;
+      }
+      init = false;
+      if (has) init7 = false;
+    }
+    for (int k = 0; k < NCOL; ++k) {
+      const int kb = k < 8 ? -1 : (k - 8) % PER;
+      if (k == 4 || (kb >= 8 && kb <= 10)) continue;  // the extremes, set above
+      cl[k] = contact_tree(part.data(), k);
+    }
+  }
+  return 0;
+}
+
 int threads() { return omp_get_max_threads(); }
 
 }  // namespace lgxh

@@ -49,6 +49,13 @@ int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_b
 void joint_begin(const lgx_task_params* P, const lgx_joint_buffers* J);
 void joint_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint_buffers* J);
 int joint_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_joint_buffers* J);
+// lgx_contact_begin / lgx_contact_record / lgx_contact_reduce on host buffers (OpenMP over envs; the
+// reduction by the kernel's tree, so both backends give the same cells bit for bit): the contact
+// record, include/lgx.h ABI 14. contact_reduce returns the number of envs outside the cell grid, as
+// eval_reduce does.
+void contact_begin(const lgx_task_params* P, const lgx_contact_buffers* C);
+void contact_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_contact_buffers* C);
+int contact_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_contact_buffers* C);
 // the worker threads the host backend uses (OpenMP)
 int threads();
 

@@ -384,6 +384,55 @@ class LeggedRobot(BaseTask):
         return self._reduced_cells("lgx_joint_reduce", self._joint_buffers(), self._joint_overflow,
                                    "a terrain level / type (or cell id)", self._joint_cells)[0]
 
+    # ------------------------------------------------------------------ contact record
+    def contact_buffers(self, rows=None, cols=None, cell_ids=None, edge_tol=0.05):
+        """The contact record's tensors (include/lgx.h lgx_contact_buffers, ABI 14), allocated once
+        per (rows, cols, cell_ids tensor, edge_tol) so a captured loop replays on fixed addresses:
+        contact_body [N, 24, 12] and contact_env [N, 8] (each env's first episode since
+        contact_begin), contact_status [N] (the eval_status rule) and the cells [rows, cols, 320].
+        rows, cols and cell_ids as in gait_buffers; edge_tol: the terrain relief (m) above which a
+        contact onset counts as on an edge. Every key asked for keeps its tensors, and the call makes
+        that set the current one, which contact_begin / contact_record / contact_cells and the three
+        attributes refer to."""
+        if rows is None or cols is None:
+            grid = getattr(self, "terrain_levels", None) is not None
+            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
+        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr(), float(edge_tol))
+        if not hasattr(self, "_contacts"):
+            self._contacts = {}  # key -> lgx_contact_buffers (which keeps its tensors, cell_ids included)
+        if key not in self._contacts:
+            z, n = self._zeros, self.num_envs
+            self._contacts[key] = self._native.contact_buffers(
+                z(n, _abi.MAX_BODIES, _abi.CONTACT_COLS), z(n, _abi.CONTACT_ENV_COLS), z(n, dtype=torch.uint8),
+                z(key[0], key[1], _abi.CONTACT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32),
+                cell_ids=cell_ids, edge_tol=key[3])
+        self._contact = self._contacts[key]
+        (self.contact_body, self.contact_env, self.contact_status, self._contact_cells,
+         self._contact_overflow) = self._contact._keep[:5]
+        return self._contact
+
+    def _contact_buffers(self):
+        if getattr(self, "_contact", None) is None:
+            raise RuntimeError("no contact record: call contact_buffers(...) first")
+        return self._contact
+
+    def contact_begin(self):
+        """lgx_contact_begin: reset the contact records and record every env's next (first) episode."""
+        self._native.contact_begin(self._contact_buffers(), self._stream())
+
+    def contact_record(self):
+        """lgx_contact_record for the step just run (call after every step(); stream-ordered, no host
+        sync, capturable)."""
+        self._native.contact_record(self._contact_buffers(), self._stream())
+
+    def contact_cells(self):
+        """lgx_contact_reduce, then the cells [rows, cols, 320] float64 on the host: the number of
+        finished envs, the sums and the peak of their env columns, the falls and, per body, the sums
+        of columns 1, 2, 3, 5, 6, 8, 9, 11, the extremes of columns 4, 10 and 7 and the two fall
+        histograms. Synchronises. An env whose cell lies outside the grid is an error."""
+        return self._reduced_cells("lgx_contact_reduce", self._contact_buffers(), self._contact_overflow,
+                                   "a terrain level / type (or cell id)", self._contact_cells)[0]
+
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""
         return torch.cuda.current_stream(self.device).cuda_stream if self.sim_device_id >= 0 else 0

@@ -9,7 +9,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
-         [--trace_falls M [--trace_s 2.0]] [--gait] [--joints]
+         [--trace_falls M [--trace_s 2.0]] [--gait] [--joints] [--contacts]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
 history the largest one needs); several values give one report each under "sweep", on one captured
@@ -51,6 +51,15 @@ power, the shares of samples with any joint saturated / out of range, and flags.
 is printed before the JSON ("joint total <name>: saturation share, RMS torque / limit, peak speed / limit, range
 margin, action rate, flags").
 
+--contacts: where the robot touches the world (PolicyEvaluator.run(contacts=True), contact_cell_report), valid in
+every mode, alone or with --gait, --joints and --trace_falls: a per-body record runs on the device after every
+step; every cell, bin and "total" of the JSON gains a "contacts" entry: per body the contact share, onsets per
+second, mean and peak force, the share of hits on vertical faces, the height above the terrain and the share of
+contact onsets on a terrain edge (relief above evaluator.EDGE_RELIEF_M); per cell the collision share, the falls,
+which termination body ended them ("fall_causes") and which body was hit hardest at that step. One line per cell
+or bin with data is printed before the JSON ("contacts <where>: falls 37: base 62 %, FR_thigh 22 %, no contact
+16 %; foot touchdowns on an edge 9 %").
+
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
 eval_<policy>_command.json)."""
@@ -74,7 +83,7 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
-             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False):
+             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False, contacts=False):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -110,21 +119,21 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         depth = min(max(int(round(float(trace_s) / float(env.dt))), 1), int(env.max_episode_length))
     if push_vel:
         report = dict(**head, **ev.run_push_test(push_vel, directions=push_dirs, at_s=push_at_s, num_steps=eval_steps,
-                                                 graph=graph, trace_depth=depth, gait=gait, joints=joints))
+                                                 graph=graph, trace_depth=depth, gait=gait, joints=joints, contacts=contacts))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_push.json")
     elif cmd_vx:
         report = dict(**head, **ev.run_command_test(cmd_vx, vy=cmd_vy or (0.0,), yaw=cmd_yaw or (0.0,), at_s=cmd_at_s,
                                                     start=cmd_start or (0.0, 0.0, 0.0), num_steps=eval_steps,
-                                                    graph=graph, trace_depth=depth, gait=gait, joints=joints))
+                                                    graph=graph, trace_depth=depth, gait=gait, joints=joints, contacts=contacts))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_command.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
-                                      trace_depth=depth, gait=gait, joints=joints)
+                                      trace_depth=depth, gait=gait, joints=joints, contacts=contacts)
         report = dict(**head, policy=policy, action_delay_ms=[1000.0 * d for d in delays_s], sweep=sweep)
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_latency.json")
     else:
         report = dict(**head, **ev.run(eval_steps, graph=graph, action_delay_s=delays_s[0] if delays_s else None,
-                                       motor_strength=motor_strength, trace_depth=depth, gait=gait, joints=joints))
+                                       motor_strength=motor_strength, trace_depth=depth, gait=gait, joints=joints, contacts=contacts))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}.json")
     if depth is not None:
         import numpy as np
@@ -150,6 +159,13 @@ def gait_summary(report):
                          f"{fmt(g['mean_duty_factor'], '.2f')}, slip {fmt(g['mean_slip_m_per_stance_s'], '.3f')} m/s, "
                          f"{g['envs']} envs")
 
+    _each_place(report, line)
+    return lines
+
+
+def _each_place(report, line):
+    """line(where, entry, always=False) for every cell or bin of a report (of every entry of a
+    latency sweep), then for its total with always=True."""
     for i, rep in enumerate(report.get("sweep", [report])):
         tag = f"delay {report['action_delay_ms'][i]:g} ms " if "sweep" in report else ""
         if "speeds" in rep:  # the push test
@@ -166,7 +182,6 @@ def gait_summary(report):
                 for c, cell in enumerate(row):
                     line(f"{tag}level {r} type {c}", cell)
         line(f"{tag}total", rep["total"], always=True)
-    return lines
 
 
 def joint_summary(report):
@@ -184,6 +199,25 @@ def joint_summary(report):
                          f"{fmt(j['max_peak_speed_over_limit'], '.2f')} of the limit, range margin "
                          f"{fmt(j['range_margin_rad'], '.3f')} rad, action rate {fmt(j['action_rate_rms'], '.3f')}, "
                          f"flags: {'; '.join(flags) or 'none'}")
+    return lines
+
+
+def contact_summary(report):
+    """The human-readable lines of a --contacts report: one per cell or bin with data, and the total:
+    which body ended the falls (the largest shares first) and how often the feet land on an edge."""
+    lines = []
+
+    def line(where, entry, always=False):
+        c = entry.get("contacts")
+        if not c or not (always or c["envs"] > 0):
+            return
+        causes = sorted((c["fall_causes"] or {}).items(), key=lambda kv: (kv[0] == "no_contact", -kv[1]))
+        who = ", ".join(f"{'no contact' if k == 'no_contact' else k} {100 * v:.0f} %" for k, v in causes if v > 0)
+        edge = c["foot_edge_onset_share"]
+        lines.append(f"contacts {where}: falls {c['falls']}{': ' + who if who else ''}; foot touchdowns on an edge "
+                     f"{'-' if edge is None else format(100 * edge, '.0f') + ' %'}")
+
+    _each_place(report, line)
     return lines
 
 
@@ -206,6 +240,7 @@ def main(argv=None):
     p.add_argument("--trace_s", type=float, default=2.0)
     p.add_argument("--gait", action="store_true")
     p.add_argument("--joints", action="store_true")
+    p.add_argument("--contacts", action="store_true")
     own, rest = p.parse_known_args(sys.argv[1:] if argv is None else argv)
     torch.set_float32_matmul_precision("high")
     report, _ = evaluate(get_args(rest), policy=own.policy, eval_steps=own.eval_steps,
@@ -213,8 +248,9 @@ def main(argv=None):
                          push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s,
                          cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
                          cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s,
-                         gait=own.gait, joints=own.joints)
-    for ln in (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []):
+                         gait=own.gait, joints=own.joints, contacts=own.contacts)
+    for ln in (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []) + \
+            (contact_summary(report) if own.contacts else []):
         print(ln)
     print(json.dumps(report))
     return report

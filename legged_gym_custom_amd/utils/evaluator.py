@@ -48,6 +48,13 @@ policy asks of each motor: torque saturation, RMS and peak torque, positive and 
 speed, use of the joint range, action rate and clipping, and a list of flags (joint_cell_report);
 the per-env records: joint_records().
 
+Contacts (contacts=True of the three runs): a per-body record runs on the device after each step
+(lgx_contact_record, include/lgx.h ABI 14) and is reduced per cell or bin of the run's mode: where
+the robot touches the world: per body the contact share, onsets, force, hits on vertical faces, the
+height above the terrain and the share of onsets on a terrain edge; per cell the collision share,
+which body ended the falls and which was hit hardest (contact_cell_report); the per-env records:
+contact_records().
+
 Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
@@ -287,6 +294,80 @@ def joint_cell_report(row, dt, joint_names, params):
             "flags": flags if n > 0 else None, "joints": joints}
 
 
+# The terrain relief (m) under a body above which a contact onset counts as "on an edge" (the
+# record's edge_tol): a rule, not a measurement.
+EDGE_RELIEF_M = 0.05
+_CONTACT_PER = 13   # columns of a body in a contact cell row: 8 sums, 3 extremes, 2 fall histograms
+_CONTACT_BASE = 8
+assert _CONTACT_BASE + _abi.MAX_BODIES * _CONTACT_PER == _abi.CONTACT_CELL_COLS
+
+
+def contact_total_row(cells):
+    """The contact cell row [320] of all cells [..., 320] together: the sums added, the maxima taken
+    over the cells that have an env and the minima (column 7's) over the cells that have samples;
+    all zero when every cell is empty."""
+    flat = torch.as_tensor(cells, dtype=torch.float64).reshape(-1, _abi.CONTACT_CELL_COLS)
+    total = flat.sum(0)
+    full, sampled = flat[flat[:, 0] > 0], flat[flat[:, 1] > 0]
+    hi = [4] + [_CONTACT_BASE + _CONTACT_PER * b + k for b in range(_abi.MAX_BODIES) for k in (8, 9)]
+    lo = [_CONTACT_BASE + _CONTACT_PER * b + 10 for b in range(_abi.MAX_BODIES)]
+    total[hi] = full[:, hi].max(0).values if len(full) else 0.0
+    total[lo] = sampled[:, lo].min(0).values if len(sampled) else 0.0
+    return total
+
+
+def contact_cell_report(row, dt, body_names, feet, termination, penalised):
+    """The contact entries of one contact cell row [320] (lgx_contact_reduce) for the bodies
+    body_names (env.body_names); feet, termination, penalised: the body indices of feet_idx,
+    termination_idx and penalised_idx. JSON-serialisable; None where there is no data, never NaN.
+
+    Per body ("bodies"[name]): contact_share (samples with a contact force over 0.1 N, the collision
+    reward's rule), onsets_per_s, mean_force_in_contact (impulse / contact time), peak_force,
+    face_hit_share (the share of its contact samples with a force more horizontal than 5 : 1, the
+    feet_stumble rule), hard_share (samples over the 1 N termination threshold),
+    mean_height_above_terrain_m, min_height_above_terrain_m, edge_onset_share (the share of its
+    onsets over a terrain relief above the record's edge_tol), mean_onset_relief_m,
+    max_onset_relief_m and roles (of "foot", "termination", "penalised").
+    Per cell: envs, samples, collision_share (samples with any non-foot body in contact),
+    mean_penalised_in_contact (the collision reward's raw value per sample), peak_nonfoot_force,
+    falls, mean_termination_bodies_at_fall, fall_causes ({name: share of the falls which that
+    termination body ended, "no_contact": the share ended by orientation or by falling out}; the
+    shares sum to 1), hardest_hit_at_fall (the same over the non-foot bodies: which one carried the
+    largest force at the step that ended the episode) and foot_edge_onset_share (the feet's onsets
+    together: the share of touchdowns on an edge)."""
+    c = [float(v) for v in row]
+    assert len(c) == _abi.CONTACT_CELL_COLS
+    div = lambda a, b: a / b if b > 0 else None  # noqa: E731
+    n, samples, falls = int(round(c[0])), c[1], c[5]
+    names = [str(x) for x in body_names][:_abi.MAX_BODIES]
+    feet, termination, penalised = ([int(i) for i in lst] for lst in (feet, termination, penalised))
+    blocks = [c[_CONTACT_BASE + _CONTACT_PER * b: _CONTACT_BASE + _CONTACT_PER * (b + 1)] for b in range(len(names))]
+    bodies = {}
+    for i, (name, b) in enumerate(zip(names, blocks)):
+        roles = [r for r, lst in (("foot", feet), ("termination", termination), ("penalised", penalised)) if i in lst]
+        bodies[name] = {
+            "contact_share": div(b[0], samples), "onsets_per_s": div(b[1], samples * dt),
+            "mean_force_in_contact": div(b[2], b[0] * dt), "peak_force": b[8] if n > 0 else None,
+            "face_hit_share": div(b[3], b[0]), "hard_share": div(b[7], samples),
+            "mean_height_above_terrain_m": div(b[4], samples),
+            "min_height_above_terrain_m": b[10] if samples > 0 else None,
+            "edge_onset_share": div(b[5], b[1]), "mean_onset_relief_m": div(b[6], b[1]),
+            "max_onset_relief_m": b[9] if b[1] > 0 else None, "roles": roles}
+    causes = hardest = None
+    if falls > 0:
+        causes = {names[i]: blocks[i][11] / falls for i in sorted(set(termination)) if i < len(names)}
+        causes["no_contact"] = c[6] / falls
+        nonfoot = [i for i in range(len(names)) if i not in feet]
+        hardest = {names[i]: blocks[i][12] / falls for i in nonfoot}
+        hardest["no_contact"] = (falls - sum(blocks[i][12] for i in nonfoot)) / falls
+    foot = [blocks[i] for i in feet if i < len(names)]
+    return {"envs": n, "samples": int(round(samples)), "collision_share": div(c[3], samples),
+            "mean_penalised_in_contact": div(c[2], samples), "peak_nonfoot_force": c[4] if n > 0 else None,
+            "falls": int(round(falls)), "mean_termination_bodies_at_fall": div(c[7], falls),
+            "fall_causes": causes, "hardest_hit_at_fall": hardest,
+            "foot_edge_onset_share": div(sum(b[5] for b in foot), sum(b[1] for b in foot)), "bodies": bodies}
+
+
 def _min_max(t, kind):
     return None if t is None else [kind(t.min()), kind(t.max())]
 
@@ -317,6 +398,8 @@ class PolicyEvaluator:
         self.last_gait_cells = None   # [rows, cols, 61] of the last finished run, None without gait=True
         self._joints = False          # whether the run under way keeps the joint-load record
         self.last_joint_cells = None  # [rows, cols, 246] of the last finished run, None without joints=True
+        self._contacts = False          # whether the run under way keeps the contact record
+        self.last_contact_cells = None  # [rows, cols, 320] of the last finished run, None without contacts=True
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -353,7 +436,7 @@ class PolicyEvaluator:
     def step(self, ev=None):
         """One eager iteration: act, env.step, eval_accumulate (ev: the eval buffers to record
         into; default: the plain evaluation's), gait_record in a gait run, joint_record in a joints
-        run and trace_record in a traced run."""
+        run, contact_record in a contacts run and trace_record in a traced run."""
         with torch.no_grad():
             self._body(ev)
 
@@ -366,6 +449,8 @@ class PolicyEvaluator:
             env.gait_record()
         if self._joints:
             env.joint_record()
+        if self._contacts:
+            env.contact_record()
         if self._trace_depth is not None:
             env.trace_record()
 
@@ -387,15 +472,18 @@ class PolicyEvaluator:
                 env.gait_begin()
             if self._joints:
                 env.joint_begin()
+            if self._contacts:
+                env.contact_begin()
             if self._trace_depth is not None:
                 env.trace_begin()
 
-    def _set_trace(self, trace_depth, gait=False, joints=False):
+    def _set_trace(self, trace_depth, gait=False, joints=False, contacts=False):
         """Start a run: the flight recorder's depth for it (None: off; else the env's rings of that
-        depth, allocated once per depth) and whether it keeps the gait record and the joint-load
-        record (the mode picks the env's gait / joint buffers: their cell key is the mode's)."""
-        self.last_trace_depth = self.last_gait_cells = self.last_joint_cells = None
-        self._gait, self._joints = bool(gait), bool(joints)
+        depth, allocated once per depth) and whether it keeps the gait record, the joint-load record
+        and the contact record (the mode picks the env's gait / joint / contact buffers: their cell
+        key is the mode's)."""
+        self.last_trace_depth = self.last_gait_cells = self.last_joint_cells = self.last_contact_cells = None
+        self._gait, self._joints, self._contacts = bool(gait), bool(joints), bool(contacts)
         self._trace_depth = None if trace_depth is None else int(trace_depth)
         if self._trace_depth is not None:
             self.env.trace_buffers(self._trace_depth)
@@ -417,7 +505,7 @@ class PolicyEvaluator:
 
     # ------------------------------------------------------------------ run
     def run(self, num_steps=None, graph=True, action_delay_s=None, motor_strength=None, trace_depth=None,
-            gait=False, joints=False):
+            gait=False, joints=False, contacts=False):
         """Evaluate: reset, num_steps x {act, step, accumulate}, reduce, one host read; returns the
         report (JSON-serialisable): per-cell and total entries REPORT_KEYS, None where a cell has
         no data (never NaN).
@@ -446,13 +534,19 @@ class PolicyEvaluator:
         joints: keep the joint-load record (the loop body gains lgx_joint_record, in a captured loop
         of its own; the cells are bit-identical to a run's without it): the report gains a "joints"
         entry (joint_cell_report) in every cell and in total; the per-env records: joint_records().
-        False: nothing changes."""
+        False: nothing changes.
+        contacts: keep the contact record (the loop body gains lgx_contact_record, in a captured loop
+        of its own; the cells are bit-identical to a run's without it): the report gains a "contacts"
+        entry (contact_cell_report) in every cell and in total; the per-env records:
+        contact_records(). False: nothing changes."""
         env = self.env
-        self._set_trace(trace_depth, gait, joints)
+        self._set_trace(trace_depth, gait, joints, contacts)
         if self._gait:
             env.gait_buffers()  # the terrain grid is the cell key
         if self._joints:
             env.joint_buffers()  # likewise
+        if self._contacts:
+            env.contact_buffers(edge_tol=EDGE_RELIEF_M)  # likewise
         saved = []  # (buffer, its values before this run)
         try:
             if action_delay_s is not None:
@@ -471,6 +565,7 @@ class PolicyEvaluator:
             bins = [cell for row in out["cells"] for cell in row]
             self._attach_gait(gcells, out["total"], bins)
             self._attach_joints(out["total"], bins)
+            self._attach_contacts(out["total"], bins)
             return out
         finally:
             for buf, old in saved:
@@ -479,18 +574,18 @@ class PolicyEvaluator:
     def _drive(self, slot, key, num_steps, graph, read_cells, prepare=None, started=None, cleanup=None):
         """The run of all three modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
         "_cmd_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
-        the trace depth, the gait flag and the joints flag are added: the loop is captured when there is no graph or
-        the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
+        the trace depth and the gait, joints and contacts flags are added: the loop is captured when
+        there is no graph or the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
         buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
         always, when the run ends or fails. read_cells(): the mode's reduce and host read
         (synchronises), one tensor or a tuple with the [rows, cols, 12] cells first.
         Returns (what read_cells returned, the gait cells or None, the report's common head, its
         wall_s / env_steps_per_s tail) and sets last_cells, last_trace_depth, last_gait_cells and
-        last_joint_cells (the joint cells of a joints run)."""
+        last_joint_cells / last_contact_cells (the cells of a joints / contacts run)."""
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
-        gkey = key + (self._trace_depth, self._gait, self._joints)
+        gkey = key + (self._trace_depth, self._gait, self._joints, self._contacts)
         try:
             ev = prepare() if prepare else None
             if use_graph and (getattr(self, slot) is None or getattr(self, slot + "_key") != gkey):
@@ -503,6 +598,7 @@ class PolicyEvaluator:
             cells = read_cells()
             gcells = env.gait_cells() if self._gait else None
             jcells = env.joint_cells() if self._joints else None
+            ccells = env.contact_cells() if self._contacts else None
             wall = time.perf_counter() - t0
         finally:
             if cleanup:
@@ -510,6 +606,7 @@ class PolicyEvaluator:
         self.last_cells = cells[0] if isinstance(cells, tuple) else cells  # as lgx_eval_reduce wrote them
         self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells  # ([rows, cols, 61] float64)
         self.last_joint_cells = jcells  # ([rows, cols, 246] float64)
+        self.last_contact_cells = ccells  # ([rows, cols, 320] float64)
         return cells, gcells, self._head(steps, use_graph), self._rates(steps, wall)
 
     def _head(self, steps, graph):
@@ -544,6 +641,20 @@ class PolicyEvaluator:
         for row, b in zip(flat, bins):
             b["joints"] = joint_cell_report(row, dt, names, params)
 
+    def _attach_contacts(self, total, bins):
+        """The "contacts" entry (contact_cell_report) of the total and of every bin, from the finished
+        run's last_contact_cells; bins as in _attach_gait. Nothing without a contact record."""
+        ccells = self.last_contact_cells
+        if ccells is None:
+            return
+        env = self.env
+        args = (float(env.dt), env.body_names, env.feet_indices.tolist(), env.termination_contact_indices.tolist(),
+                env.penalised_contact_indices.tolist())
+        flat = ccells.reshape(-1, ccells.shape[2])
+        total["contacts"] = contact_cell_report(contact_total_row(flat), *args)
+        for row, b in zip(flat, bins):
+            b["contacts"] = contact_cell_report(row, *args)
+
     def _switch_step(self, at_s, test):
         """at_s (seconds into the episode) as an episode step of the push / command test."""
         at, last = float(at_s), int(self.env.max_episode_length)
@@ -576,6 +687,16 @@ class PolicyEvaluator:
         return {"joint": env.joint_rec.cpu().numpy(), "body": env.joint_body.cpu().numpy(),
                 "status": env.joint_status.cpu().numpy()}
 
+    def contact_records(self):
+        """The per-env contact records of the last run (it must have been one with contacts=True),
+        numpy arrays on the host: body [N, 24, 12], env [N, 8] and status [N] (lgx_contact_buffers)."""
+        if self.last_contact_cells is None:
+            raise RuntimeError("contact_records(): the last run kept no contact record (pass contacts=True to run, "
+                               "run_push_test or run_command_test first)")
+        env = self.env
+        return {"body": env.contact_body.cpu().numpy(), "env": env.contact_env.cpu().numpy(),
+                "status": env.contact_status.cpu().numpy()}
+
     def _loop(self, steps, g, ev):
         """steps x the loop body (g: its captured graph, or None for the eager loop) recording
         into ev; returns the start time."""
@@ -594,7 +715,7 @@ class PolicyEvaluator:
 
     # ------------------------------------------------------------------ push recovery
     def run_push_test(self, speeds, directions=8, at_s=2.0, settle_tol=0.3, num_steps=None, graph=True,
-                      trace_depth=None, gait=False, joints=False):
+                      trace_depth=None, gait=False, joints=False, contacts=False):
         """How hard a shove does the policy survive, from which side, and how quickly does it
         settle: one run in which every env is pushed once, at episode step round(at_s / dt), by a
         velocity impulse of its bin (speed index s, direction index d): dvel = speeds[s] *
@@ -610,7 +731,8 @@ class PolicyEvaluator:
         The schedule is cleared in place when the run ends, so a following run() is the plain one.
 
         trace_depth: the flight recorder, as in run(). gait: the gait record, as in run(), per bin.
-        joints: the joint-load record, as in run(), per bin.
+        joints: the joint-load record, as in run(), per bin. contacts: the contact record, as in run(),
+        per bin.
 
         Returns the report: "bins"[s][d] with the REPORT_KEYS entries and pushed (finished envs
         with post-push samples), mean_peak_tilt_rad, mean_peak_lin_vel_err (m/s), survivors (timed
@@ -620,7 +742,7 @@ class PolicyEvaluator:
         ValueError: no speeds or directions, a negative or non-finite speed, a push step outside
         0 < step < max_episode_length."""
         env = self.env
-        self._set_trace(trace_depth, gait, joints)
+        self._set_trace(trace_depth, gait, joints, contacts)
         speeds = [float(v) for v in speeds]
         S, D = len(speeds), int(directions)
         if S < 1 or D < 1 or not all(math.isfinite(v) and v >= 0.0 for v in speeds):
@@ -642,6 +764,8 @@ class PolicyEvaluator:
                 env.gait_buffers(S, D, env.push_cell_ids)  # the bin is the cell key
             if self._joints:
                 env.joint_buffers(S, D, env.push_cell_ids)
+            if self._contacts:
+                env.contact_buffers(S, D, env.push_cell_ids, edge_tol=EDGE_RELIEF_M)
             return ev
 
         (cells, pcells), gcells, head, rates = self._drive(
@@ -658,12 +782,13 @@ class PolicyEvaluator:
         flat = [b for row in out["bins"] for b in row]
         self._attach_gait(gcells, out["total"], flat)
         self._attach_joints(out["total"], flat)
+        self._attach_contacts(out["total"], flat)
         return out
 
     # ------------------------------------------------------------------ command response
     def run_command_test(self, vx, vy=(0.0,), yaw=(0.0,), at_s=2.0, start=(0.0, 0.0, 0.0), steady_after_s=1.0,
                          settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None, gait=False,
-                         joints=False):
+                         joints=False, contacts=False):
         """What does the robot do when commanded, how fast does it get there, and does it stay up:
         one run in which every env holds the command `start` = (vx, vy, yaw rate), switches at
         episode step round(at_s / dt) to the command of its bin (vx[ix], vy[iy], yaw[iw]) and is
@@ -681,7 +806,8 @@ class PolicyEvaluator:
 
         trace_depth: the flight recorder, as in run(). gait: the gait record, as in run(), per bin
         (how the gait changes with the commanded speed). joints: the joint-load record, as in run(),
-        per bin (what each commanded speed asks of the motors).
+        per bin (what each commanded speed asks of the motors). contacts: the contact record, as in
+        run(), per bin.
 
         Returns the report: "bins"[ix][iy][iw] with the REPORT_KEYS entries and switched (finished
         envs with post-switch samples), survivors (timed out among them), mean_settle_s /
@@ -694,7 +820,7 @@ class PolicyEvaluator:
         ValueError: an empty list, a non-finite entry, a switch step outside 0 < step <
         max_episode_length, a negative or non-finite tolerance or steady_after_s."""
         env = self.env
-        self._set_trace(trace_depth, gait, joints)
+        self._set_trace(trace_depth, gait, joints, contacts)
         vx, vy, yaw, start = ([float(v) for v in lst] for lst in (vx, vy, yaw, start))
         if min(len(vx), len(vy), len(yaw)) < 1 or len(start) != 3 or \
                 not all(math.isfinite(v) for v in vx + vy + yaw + start):
@@ -721,6 +847,8 @@ class PolicyEvaluator:
                 env.gait_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
             if self._joints:
                 env.joint_buffers(nx, ny * nw, env.cmd_cell_ids)
+            if self._contacts:
+                env.contact_buffers(nx, ny * nw, env.cmd_cell_ids, edge_tol=EDGE_RELIEF_M)
             return ev
 
         (cells, ccells), gcells, head, rates = self._drive("_cmd_graph", key, num_steps, graph, env.eval_command_cells,
@@ -738,6 +866,7 @@ class PolicyEvaluator:
         flat = [b for plane in out["bins"] for row in plane for b in row]
         self._attach_gait(gcells, total, flat)
         self._attach_joints(total, flat)
+        self._attach_contacts(total, flat)
         return out
 
     # ------------------------------------------------------------------ flight recorder

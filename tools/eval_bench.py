@@ -6,6 +6,7 @@ networks (the timing does not depend on the weights), graph replay and the eager
   python tools/eval_bench.py --trace_depth 100 ...   # + the plain run with the flight recorder on, and traces()
   python tools/eval_bench.py --gait ...   # + the plain run with the gait record on (run(gait=True))
   python tools/eval_bench.py --joints ...   # + the plain run with the joint-load record on (run(joints=True))
+  python tools/eval_bench.py --contacts ...   # + the plain run with the contact record on (run(contacts=True))
   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/eval_bench.py --profile
   python tools/eval_bench.py --stats DIR/..._kernel_stats.csv --merge FILE   # kernel times into FILE
 
@@ -26,7 +27,9 @@ KERNELS = {"eval_accumulate_kernel": "eval_accumulate_us", "eval_reduce_kernel":
            "env_step_kernel": "env_step_us", "act_kernel(lgx_s8_act_args": "act_us",
            "trace_record_kernel": "trace_record_us", "trace_gather_kernel": "trace_gather_us",
            "gait_record_kernel": "gait_record_us", "gait_reduce_kernel": "gait_reduce_us",
-           "joint_record_kernel": "joint_record_us", "joint_reduce_kernel": "joint_reduce_us"}
+           "joint_record_kernel": "joint_record_us", "joint_reduce_kernel": "joint_reduce_us",
+           "contact_record_kernel": "contact_record_us", "contact_reduce_kernel": "contact_reduce_us",
+           "contact_begin_kernel": "contact_begin_us"}
 
 
 def merge_stats(stats_csv, out):
@@ -61,6 +64,7 @@ def main():
                    help="also time run(trace_depth=K), the flight recorder, and traces('falls', 16) after it")
     p.add_argument("--gait", action="store_true", help="also time run(gait=True), the gait record")
     p.add_argument("--joints", action="store_true", help="also time run(joints=True), the joint-load record")
+    p.add_argument("--contacts", action="store_true", help="also time run(contacts=True), the contact record")
     p.add_argument("--profile", action="store_true")
     p.add_argument("--stats")
     p.add_argument("--merge")
@@ -87,7 +91,8 @@ def main():
     runner, _ = task_registry.make_alg_runner(env, args=args, train_cfg=tcfg, log_root=None)
     ev = PolicyEvaluator(env, runner)
     if a.profile:
-        r = ev.run(a.steps or 200, graph=False, trace_depth=a.trace_depth, gait=a.gait, joints=a.joints)
+        r = ev.run(a.steps or 200, graph=False, trace_depth=a.trace_depth, gait=a.gait, joints=a.joints,
+                   contacts=a.contacts)
         if a.trace_depth:
             ev.traces("falls", 16)
         if a.cmd_vx:  # (the only run with eval_cmd_reduce_kernel)
@@ -117,20 +122,27 @@ def main():
         rates.update(joints_graph=[], joints_eager=[])
         jointed(20, True)
         jointed(20, False)
+    touched = (lambda steps, graph: ev.run(steps, graph, contacts=True))
+    if a.contacts:
+        rates.update(contacts_graph=[], contacts_eager=[])
+        touched(20, True)
+        touched(20, False)
     traced = (lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
     if a.trace_depth:  # (the last mode: traces() below reads the last timed run's rings)
         rates.update(trace_graph=[], trace_eager=[])
         traced(20, True)
         traced(20, False)
-    gr = jr = None
+    gr = jr = ctr = None
     for _ in range(a.repeats):
         for mode in rates:
             graph = mode.endswith("graph")
             r = (push if mode.startswith("push") else cmd if mode.startswith("cmd") else
                  traced if mode.startswith("trace") else gaited if mode.startswith("gait") else
-                 jointed if mode.startswith("joints") else ev.run)(a.steps, graph)
+                 jointed if mode.startswith("joints") else touched if mode.startswith("contacts") else
+                 ev.run)(a.steps, graph)
             gr = r if mode.startswith("gait") else gr
             jr = r if mode.startswith("joints") else jr
+            ctr = r if mode.startswith("contacts") else ctr
             assert a.device == "cpu" or r["graph"] == graph
             rates[mode].append(r["env_steps_per_s"])
     trace_doc = None
@@ -147,7 +159,7 @@ def main():
                      "record_bytes_in_per_step": n * (8 + 69 * 4 + env.num_bodies * 12 + 4 + 1 + 1),
                      "record_bytes_out_per_step": n * (304 + 4)}
     pr, cr = r if a.push_vel else None, r if a.cmd_vx else None
-    r = ev.run(a.steps) if pr or cr or a.trace_depth or a.gait or a.joints else r
+    r = ev.run(a.steps) if pr or cr or a.trace_depth or a.gait or a.joints or a.contacts else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
                                for m, v in rates.items()},
@@ -170,6 +182,15 @@ def main():
                          # the status and reset flags
                          "record_bytes_in_per_step": n * (768 + 16 + 12 * 16 + 2),
                          "record_bytes_out_per_step": n * (768 + 16)}
+    if ctr:
+        n, nb = a.num_envs, env.num_bodies
+        doc["contacts"] = {"total": ctr["total"]["contacts"],
+                           # what lgx_contact_record moves per step when every env records: the body and
+                           # env records in and out (the env row's first float4), per body its force and
+                           # position, the status and reset flags; the terrain samples (3 int16 per body,
+                           # 9 more at an onset) come on top on a heightfield
+                           "record_bytes_in_per_step": n * (nb * 48 + 16 + nb * 24 + 2),
+                           "record_bytes_out_per_step": n * (nb * 48 + 16)}
     if pr:
         doc["push_test"] = {k: pr[k] for k in ("speeds", "directions_deg", "push_step", "settle_tol", "total")}
         doc["push_test"]["per_speed"] = [
