@@ -194,6 +194,16 @@ STRUCTS = {"lgx_model": Model, "lgx_task_params": TaskParams, "lgx_buffers": Buf
            "lgx_joint_buffers": JointBuffers, "lgx_contact_buffers": ContactBuffers}
 SIZEOF = {"lgx_sizeof_" + name[len("lgx_"):]: name for name in STRUCTS}  # sizeof export -> typedef
 
+# The record families of the evaluation (lgx_<kind>_begin / _record / _reduce): kind -> (the struct,
+# its two record members with their per-env shapes, the columns of a cell row, the extra scalar
+# members). All share status, cells, overflow, cell_rows, cell_cols and cell_ids.
+RECORD_KINDS = {
+    "gait": (GaitBuffers, (("foot", (MAX_FEET, GAIT_FOOT_COLS)), ("body", (GAIT_BODY_COLS,))), GAIT_CELL_COLS, ()),
+    "joint": (JointBuffers, (("joint", (MAX_DOF, JOINT_COLS)), ("body", (JOINT_BODY_COLS,))), JOINT_CELL_COLS, ()),
+    "contact": (ContactBuffers, (("body", (MAX_BODIES, CONTACT_COLS)), ("env", (CONTACT_ENV_COLS,))), CONTACT_CELL_COLS,
+                ("edge_tol",)),
+}
+
 CONSTANTS = {
     "LGX_ABI_VERSION": ABI_VERSION, "LGX_MAX_DOF": MAX_DOF, "LGX_MAX_LINKS": MAX_LINKS,
     "LGX_MAX_BODIES": MAX_BODIES, "LGX_MAX_FEET": MAX_FEET, "LGX_MAX_PROPRIO": MAX_PROPRIO,

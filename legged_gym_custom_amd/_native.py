@@ -198,95 +198,83 @@ class NativeEnv:
                                              C.c_void_p(out.data_ptr()), C.c_void_p(out_len.data_ptr()),
                                              C.c_void_p(stream)), "lgx_trace_gather")
 
+    def _record_buffers(self, kind, records, status, cells, overflow, cell_ids, **scalars):
+        """The buffers struct of a record family (_abi.RECORD_KINDS[kind]) over the given tensors:
+        records are its two record tensors in member order, scalars its extra scalar members."""
+        cls, members, cell_cols, extra = _abi.RECORD_KINDS[kind]
+        n = self.params.num_envs
+        if cells is not None and (cells.dim() != 3 or cells.shape[2] != cell_cols):
+            raise LgxError(f"{kind} buffer cells must be [rows, cols, {cell_cols}]")
+        b = cls()
+        self._fill(b, kind + " buffer", [
+            *((name, t, (n,) + shape, "float32", True) for (name, shape), t in zip(members, records)),
+            ("status", status, (n,), "uint8", True), ("cells", cells, None, "float64", True),
+            ("overflow", overflow, (1,), "int32", True), ("cell_ids", cell_ids, (n,), "int32", False)])
+        b.cell_rows, b.cell_cols = int(cells.shape[0]), int(cells.shape[1])
+        for name in extra:
+            setattr(b, name, float(scalars[name]))
+        b._keep = (*records, status, cells, overflow, cell_ids)
+        return b
+
+    def _record_call(self, symbol, bufs, stream):
+        """One lgx_<kind>_begin / _record / _reduce call on a family's buffers."""
+        self._check(getattr(self._L, symbol)(self.handle, C.byref(bufs), C.c_void_p(stream)), symbol)
+
     def gait_buffers(self, foot, body, status, cells, overflow, cell_ids=None):
         """lgx_gait_buffers (ABI 12) over the given tensors: foot [N, 4, 16] fp32, body [N, 12] fp32,
         status [N] uint8, cells [rows, cols, 61] float64, overflow [1] int32 and, optional, cell_ids
         [N] int32 (the free cell key), all in the env's memory space."""
-        n = self.params.num_envs
-        if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.GAIT_CELL_COLS):
-            raise LgxError(f"gait buffer cells must be [rows, cols, {_abi.GAIT_CELL_COLS}]")
-        gb = _abi.GaitBuffers()
-        self._fill(gb, "gait buffer", [
-            ("foot", foot, (n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS), "float32", True),
-            ("body", body, (n, _abi.GAIT_BODY_COLS), "float32", True), ("status", status, (n,), "uint8", True),
-            ("cells", cells, None, "float64", True), ("overflow", overflow, (1,), "int32", True),
-            ("cell_ids", cell_ids, (n,), "int32", False)])
-        gb.cell_rows, gb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
-        gb._keep = (foot, body, status, cells, overflow, cell_ids)
-        return gb
+        return self._record_buffers("gait", (foot, body), status, cells, overflow, cell_ids)
 
     def gait_begin(self, gb, stream):
         """lgx_gait_begin: zero the records, the statuses and the overflow count (gb: gait_buffers(...))."""
-        self._check(self._L.lgx_gait_begin(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_begin")
+        self._record_call("lgx_gait_begin", gb, stream)
 
     def gait_record(self, gb, stream):
         """lgx_gait_record: one sample per recording env from the step just run."""
-        self._check(self._L.lgx_gait_record(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_record")
+        self._record_call("lgx_gait_record", gb, stream)
 
     def gait_reduce(self, gb, stream):
         """lgx_gait_reduce: records -> cells (and the out-of-grid count in gb.overflow)."""
-        self._check(self._L.lgx_gait_reduce(self.handle, C.byref(gb), C.c_void_p(stream)), "lgx_gait_reduce")
+        self._record_call("lgx_gait_reduce", gb, stream)
 
     def joint_buffers(self, joint, body, status, cells, overflow, cell_ids=None):
         """lgx_joint_buffers (ABI 13) over the given tensors: joint [N, 12, 16] fp32, body [N, 4] fp32,
         status [N] uint8, cells [rows, cols, 246] float64, overflow [1] int32 and, optional, cell_ids
         [N] int32 (the free cell key), all in the env's memory space."""
-        n = self.params.num_envs
-        if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.JOINT_CELL_COLS):
-            raise LgxError(f"joint buffer cells must be [rows, cols, {_abi.JOINT_CELL_COLS}]")
-        jb = _abi.JointBuffers()
-        self._fill(jb, "joint buffer", [
-            ("joint", joint, (n, _abi.MAX_DOF, _abi.JOINT_COLS), "float32", True),
-            ("body", body, (n, _abi.JOINT_BODY_COLS), "float32", True), ("status", status, (n,), "uint8", True),
-            ("cells", cells, None, "float64", True), ("overflow", overflow, (1,), "int32", True),
-            ("cell_ids", cell_ids, (n,), "int32", False)])
-        jb.cell_rows, jb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
-        jb._keep = (joint, body, status, cells, overflow, cell_ids)
-        return jb
+        return self._record_buffers("joint", (joint, body), status, cells, overflow, cell_ids)
 
     def joint_begin(self, jb, stream):
         """lgx_joint_begin: zero the records, the statuses and the overflow count (jb: joint_buffers(...))."""
-        self._check(self._L.lgx_joint_begin(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_begin")
+        self._record_call("lgx_joint_begin", jb, stream)
 
     def joint_record(self, jb, stream):
         """lgx_joint_record: one sample per recording env from the step just run."""
-        self._check(self._L.lgx_joint_record(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_record")
+        self._record_call("lgx_joint_record", jb, stream)
 
     def joint_reduce(self, jb, stream):
         """lgx_joint_reduce: records -> cells (and the out-of-grid count in jb.overflow)."""
-        self._check(self._L.lgx_joint_reduce(self.handle, C.byref(jb), C.c_void_p(stream)), "lgx_joint_reduce")
+        self._record_call("lgx_joint_reduce", jb, stream)
 
     def contact_buffers(self, body, env, status, cells, overflow, cell_ids=None, edge_tol=0.0):
         """lgx_contact_buffers (ABI 14) over the given tensors: body [N, 24, 12] fp32, env [N, 8] fp32,
         status [N] uint8, cells [rows, cols, 320] float64, overflow [1] int32 and, optional, cell_ids
         [N] int32 (the free cell key), all in the env's memory space; edge_tol: the relief (m) above
         which a contact onset counts as on an edge."""
-        n = self.params.num_envs
-        if cells is not None and (cells.dim() != 3 or cells.shape[2] != _abi.CONTACT_CELL_COLS):
-            raise LgxError(f"contact buffer cells must be [rows, cols, {_abi.CONTACT_CELL_COLS}]")
-        cb = _abi.ContactBuffers()
-        self._fill(cb, "contact buffer", [
-            ("body", body, (n, _abi.MAX_BODIES, _abi.CONTACT_COLS), "float32", True),
-            ("env", env, (n, _abi.CONTACT_ENV_COLS), "float32", True), ("status", status, (n,), "uint8", True),
-            ("cells", cells, None, "float64", True), ("overflow", overflow, (1,), "int32", True),
-            ("cell_ids", cell_ids, (n,), "int32", False)])
-        cb.cell_rows, cb.cell_cols = int(cells.shape[0]), int(cells.shape[1])
-        cb.edge_tol = float(edge_tol)
-        cb._keep = (body, env, status, cells, overflow, cell_ids)
-        return cb
+        return self._record_buffers("contact", (body, env), status, cells, overflow, cell_ids, edge_tol=edge_tol)
 
     def contact_begin(self, cb, stream):
         """lgx_contact_begin: zero the records, the statuses and the overflow count and set the env rows'
         terminal columns to "none" (cb: contact_buffers(...))."""
-        self._check(self._L.lgx_contact_begin(self.handle, C.byref(cb), C.c_void_p(stream)), "lgx_contact_begin")
+        self._record_call("lgx_contact_begin", cb, stream)
 
     def contact_record(self, cb, stream):
         """lgx_contact_record: one sample per recording env from the step just run."""
-        self._check(self._L.lgx_contact_record(self.handle, C.byref(cb), C.c_void_p(stream)), "lgx_contact_record")
+        self._record_call("lgx_contact_record", cb, stream)
 
     def contact_reduce(self, cb, stream):
         """lgx_contact_reduce: records -> cells (and the out-of-grid count in cb.overflow)."""
-        self._check(self._L.lgx_contact_reduce(self.handle, C.byref(cb), C.c_void_p(stream)), "lgx_contact_reduce")
+        self._record_call("lgx_contact_reduce", cb, stream)
 
     def __del__(self):
         try:

@@ -2440,6 +2440,31 @@ struct EvalArgs {
   int steady_after;
 };
 
+extern "C++" {  // (templates and a struct return, inside the C ABI block)
+// The prologue of the per-step record kernels (a group of lanes per env): whether the group's env
+// exists, its record status and this step's reset flag, read by every lane of the group; tail lanes
+// load nothing (status 1: frozen).
+struct Recording { bool live; int st, rs; };
+__device__ __forceinline__ Recording recording(const uint8_t* status, const uint8_t* reset, int e, int N) {
+  const bool live = e < N;
+  return {live, live ? status[e] : 1, live ? reset[e] : 0};
+}
+// A record row of Q float4 (16-byte accesses) <-> registers.
+template <int Q>
+__device__ __forceinline__ void load_row(const float4* p, float (&r)[4 * Q]) {
+  LGX_UNROLL
+  for (int i = 0; i < Q; ++i) {
+    const float4 v = p[i];
+    r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
+  }
+}
+template <int Q>
+__device__ __forceinline__ void store_row(float4* p, const float (&r)[4 * Q]) {
+  LGX_UNROLL
+  for (int i = 0; i < Q; ++i) p[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+}
+}  // extern "C++"
+
 // lgx_eval_accumulate: four lanes per env (16 envs per wave). Lane q of an env reads a quarter of
 // the joints (consecutive lanes read consecutive addresses: 48 B of torques and 96 B of dof_state
 // per env, whole lines per wave) and foot q; two xor shuffles combine the quarters; lane q then
@@ -2455,9 +2480,7 @@ __global__ __launch_bounds__(256) void eval_accumulate_kernel(EvalArgs A) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 2, q = t & 3;
   // no early return: the shuffles below need every lane of a group; tail lanes load nothing
-  const bool live = e < A.N;
-  const int st = live ? A.status[e] : 1;
-  const int rs = live ? A.reset[e] : 0;
+  const auto [live, st, rs] = recording(A.status, A.reset, e, A.N);
   const bool sample = st == 0 && !rs;
   float en = 0.f, t2 = 0.f, fmax_ = 0.f;
   if (sample) {
@@ -2565,6 +2588,29 @@ __device__ __forceinline__ uint32_t cell_reduce(const int64_t* __restrict__ leve
   if (nbad == 0 && tid < NC) store(tid, ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]);
   return nbad;
 }
+
+// The maxima that ride a cell_reduce scan (lgx_joint_reduce, lgx_contact_reduce): every thread's NX
+// fp32 partials x (a minimum as the maximum of the negated column, a "some env contributed" flag as
+// the maximum of 0 / 1) are combined by fmaxf in cell_reduce's shape, shuffle-down inside each wave,
+// then the four wave results, which folded(k) of the returned accessor forms for partial k after the
+// barrier in here. A maximum does not depend on the order, so the result is exact. Called by every
+// thread of the block, after cell_reduce (the caller's barrier between passes covers this exchange
+// too).
+template <int NX>
+__device__ __forceinline__ auto cell_max(float (&x)[NX]) {
+  __shared__ float xs[4][NX];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int o = 32; o > 0; o >>= 1) {
+    LGX_UNROLL
+    for (int k = 0; k < NX; ++k) x[k] = fmaxf(x[k], __shfl_down(x[k], o, 64));
+  }
+  if (lane == 0) {
+    LGX_UNROLL
+    for (int k = 0; k < NX; ++k) xs[wv][k] = x[k];
+  }
+  __syncthreads();
+  return [](int k) { return fmaxf(fmaxf(xs[0][k], xs[1][k]), fmaxf(xs[2][k], xs[3][k])); };
+}
 }  // extern "C++"
 
 // lgx_eval_reduce: cell_reduce over the records of the cell's finished envs; block 0 publishes the
@@ -2657,6 +2703,37 @@ static int check_feet(lgx_env* env, const std::string& w) {
 }
 static const char* const kNotBound = ": required buffer not bound: ";
 
+// The common prefix of the checks of the record families (lgx_gait_* / lgx_joint_* / lgx_contact_*):
+// check_call, the family's record buffers in declaration order (NULL, then the alignment of those the
+// kernels move as 16-byte accesses), status, overflow, cells (for the reduce) and the grid bound. The
+// family goes on with its own scalars, bound buffers and params.
+extern "C++" {  // (templates, inside the C ABI block)
+template <class Bufs> struct RecordMember { const char* name; float* Bufs::*ptr; bool aligned; };
+template <class Bufs>
+static int record_buffers_check(lgx_env* env, const Bufs* b, const std::string& w, const char* kind,
+                                std::initializer_list<RecordMember<Bufs>> records, bool reduce) {
+  if (int rc = check_call(env, b, w, kind)) return rc;
+  for (const RecordMember<Bufs>& r : records) {
+    if (!(b->*r.ptr)) return fail(env, w + ": " + r.name + " is NULL");
+    if (r.aligned && (uintptr_t)(b->*r.ptr) % 16 != 0) return fail(env, w + ": " + r.name + " must be 16-byte aligned");
+  }
+  if (!b->status) return fail(env, w + ": status is NULL");
+  if (!b->overflow) return fail(env, w + ": overflow is NULL");
+  if (reduce && !b->cells) return fail(env, w + ": cells is NULL");
+  if (b->cell_rows < 1 || b->cell_cols < 1 || (int64_t)b->cell_rows * b->cell_cols > (1 << 20))
+    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  return 0;
+}
+}  // extern "C++"
+// The host backend's reduce found `bad` envs outside the cell grid.
+static int reduce_failed(lgx_env* env, const char* name, int bad) {
+  return fail(env, std::string(name) + ": " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
+                   "outside the cell grid (cells not written)");
+}
+// Launch geometry, blocks of 256 threads: `lanes` threads per env; one block per cell.
+static dim3 lane_blocks(int lanes, int N) { return dim3((unsigned)(((int64_t)lanes * N + 255) / 256)); }
+static dim3 cell_blocks(int32_t rows, int32_t cols) { return dim3((unsigned)(rows * cols)); }
+
 // shared checks of the three lgx_eval_* calls
 static int eval_check(lgx_env* env, const lgx_eval_buffers* ev, const char* what, bool reduce) {
   const std::string w(what);
@@ -2728,9 +2805,7 @@ int lgx_eval_accumulate(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stre
   A.steady_after = ev->steady_after;
   A.N = p.num_envs; A.D = p.num_dof; A.NB = p.num_bodies; A.nfeet = p.num_feet; A.dt = p.dt;
   for (int f = 0; f < LGX_MAX_FEET; ++f) A.feet[f] = f < p.num_feet ? p.feet_idx[f] : 0;
-  const int64_t threads = (int64_t)p.num_envs * 4;
-  hipLaunchKernelGGL(lgx::eval_accumulate_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)hip_stream, A);
+  hipLaunchKernelGGL(lgx::eval_accumulate_kernel, lane_blocks(4, p.num_envs), dim3(256), 0, (hipStream_t)hip_stream, A);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -2739,18 +2814,16 @@ int lgx_eval_reduce(lgx_env* env, const lgx_eval_buffers* ev, void* hip_stream) 
   if (int rc = eval_check(env, ev, "lgx_eval_reduce", true)) return rc;
   if (env->host) {
     const int bad = lgxh::eval_reduce(&env->params, &env->buffers, ev);
-    if (bad) return fail(env, "lgx_eval_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
-                              "outside the cell grid (cells not written)");
-    return 0;
+    return bad ? reduce_failed(env, "lgx_eval_reduce", bad) : 0;
   }
   const lgx_buffers& b = env->buffers;
-  hipLaunchKernelGGL(lgx::eval_reduce_kernel, dim3((unsigned)(ev->cell_rows * ev->cell_cols)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::eval_reduce_kernel, cell_blocks(ev->cell_rows, ev->cell_cols), dim3(256), 0,
                      (hipStream_t)hip_stream, ev->acc, ev->status, b.terrain_levels, b.terrain_types, ev->cell_ids,
                      ev->push_rec, env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cells, ev->push_cells,
                      ev->overflow);
   HIP_OK(hipGetLastError());
   if (ev->cmd_cells) {
-    hipLaunchKernelGGL(lgx::eval_cmd_reduce_kernel, dim3((unsigned)(ev->cell_rows * ev->cell_cols)), dim3(256), 0,
+    hipLaunchKernelGGL(lgx::eval_cmd_reduce_kernel, cell_blocks(ev->cell_rows, ev->cell_cols), dim3(256), 0,
                        (hipStream_t)hip_stream, ev->cmd_rec, ev->status, b.terrain_levels, b.terrain_types,
                        ev->cell_ids, env->params.num_envs, ev->cell_rows, ev->cell_cols, ev->cmd_cells);
     HIP_OK(hipGetLastError());
@@ -2777,9 +2850,7 @@ __global__ __launch_bounds__(256) void trace_record_kernel(const lgx_task_params
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 4, l = t & 15;
   // no early return: the shuffles below need every lane of a group; tail lanes load nothing
-  const bool live = e < Pm->num_envs;
-  const int st = live ? status[e] : 1;
-  const int rs = live ? B.reset[e] : 0;
+  const auto [live, st, rs] = recording(status, B.reset, e, Pm->num_envs);
   const int cnt = live ? count[e] : 0;
   const bool row = st == 0 && !rs;
   float pn = 0.f;
@@ -2884,8 +2955,7 @@ int lgx_trace_record(lgx_env* env, const lgx_trace_buffers* tb, void* hip_stream
     lgxh::trace_record(&env->params, &env->buffers, tb);
     return 0;
   }
-  const int64_t threads = (int64_t)env->params.num_envs * 16;
-  hipLaunchKernelGGL(lgx::trace_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::trace_record_kernel, lane_blocks(16, env->params.num_envs), dim3(256), 0,
                      (hipStream_t)hip_stream, env->d_params, env->d_buffers, tb->ring, tb->count, tb->status, tb->depth);
   HIP_OK(hipGetLastError());
   return 0;
@@ -2930,9 +3000,7 @@ __global__ __launch_bounds__(256) void gait_record_kernel(const lgx_task_params*
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 2, q = t & 3;
   // no early return: the shuffles below need every lane of a group
-  const bool live = e < Pm->num_envs;
-  const int st = live ? status[e] : 1;
-  const int rs = live ? B.reset[e] : 0;
+  const auto [live, st, rs] = recording(status, B.reset, e, Pm->num_envs);
   const bool sample = st == 0 && !rs;
   const int nfeet = Pm->num_feet;
   const bool mine = sample && q < nfeet;
@@ -2947,11 +3015,7 @@ __global__ __launch_bounds__(256) void gait_record_kernel(const lgx_task_params*
     b2 = bq[2];
   }
   if (mine) {
-    LGX_UNROLL
-    for (int i = 0; i < 4; ++i) {
-      const float4 v = fq[i];
-      r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
-    }
+    load_row<4>(fq, r);
     const size_t row = (size_t)e * Pm->num_bodies + Pm->feet_idx[q];
     const float* cf = B.contact_forces + row * 3;
     const float* rb = B.rigid_body_states + row * 13;
@@ -2968,8 +3032,7 @@ __global__ __launch_bounds__(256) void gait_record_kernel(const lgx_task_params*
   }
   if (mine) {
     gait_foot_sample(r, first, F, R, Pm->dt);
-    LGX_UNROLL
-    for (int i = 0; i < 4; ++i) fq[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
+    store_row<4>(fq, r);
   }
   bq[0] = gait_body_col(3 * q, b0, bits, nfeet);
   bq[1] = gait_body_col(3 * q + 1, b1, bits, nfeet);
@@ -3014,15 +3077,9 @@ __global__ __launch_bounds__(256) void gait_reduce_kernel(const float* __restric
 // shared checks of the three lgx_gait_* calls
 static int gait_check(lgx_env* env, const lgx_gait_buffers* gb, const char* what, bool reduce) {
   const std::string w(what);
-  if (int rc = check_call(env, gb, w, "gait")) return rc;
-  if (!gb->foot) return fail(env, w + ": foot is NULL");
-  if ((uintptr_t)gb->foot % 16 != 0) return fail(env, w + ": foot must be 16-byte aligned");
-  if (!gb->body) return fail(env, w + ": body is NULL");
-  if (!gb->status) return fail(env, w + ": status is NULL");
-  if (!gb->overflow) return fail(env, w + ": overflow is NULL");
-  if (reduce && !gb->cells) return fail(env, w + ": cells is NULL");
-  if (gb->cell_rows < 1 || gb->cell_cols < 1 || (int64_t)gb->cell_rows * gb->cell_cols > (1 << 20))
-    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  if (int rc = record_buffers_check(env, gb, w, "gait", {{"foot", &lgx_gait_buffers::foot, true},
+                                                         {"body", &lgx_gait_buffers::body, false}}, reduce))
+    return rc;
   const lgx_buffers& b = env->buffers;
   if (int rc = check_bound(env, w, kNotBound, {{"contact_forces", b.contact_forces},
                                                {"rigid_body_states", b.rigid_body_states}, {"reset", b.reset},
@@ -3056,8 +3113,7 @@ int lgx_gait_record(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream) 
     lgxh::gait_record(&env->params, &env->buffers, gb);
     return 0;
   }
-  const int64_t threads = (int64_t)env->params.num_envs * 4;
-  hipLaunchKernelGGL(lgx::gait_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::gait_record_kernel, lane_blocks(4, env->params.num_envs), dim3(256), 0,
                      (hipStream_t)hip_stream, env->d_params, env->d_buffers, gb->foot, gb->body, gb->status);
   HIP_OK(hipGetLastError());
   return 0;
@@ -3067,12 +3123,10 @@ int lgx_gait_reduce(lgx_env* env, const lgx_gait_buffers* gb, void* hip_stream) 
   if (int rc = gait_check(env, gb, "lgx_gait_reduce", true)) return rc;
   if (env->host) {
     const int bad = lgxh::gait_reduce(&env->params, &env->buffers, gb);
-    if (bad) return fail(env, "lgx_gait_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
-                              "outside the cell grid (cells not written)");
-    return 0;
+    return bad ? reduce_failed(env, "lgx_gait_reduce", bad) : 0;
   }
   const lgx_buffers& b = env->buffers;
-  hipLaunchKernelGGL(lgx::gait_reduce_kernel, dim3((unsigned)(gb->cell_rows * gb->cell_cols)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::gait_reduce_kernel, cell_blocks(gb->cell_rows, gb->cell_cols), dim3(256), 0,
                      (hipStream_t)hip_stream, gb->foot, gb->body, gb->status, b.terrain_levels, b.terrain_types,
                      gb->cell_ids, env->params.num_envs, gb->cell_rows, gb->cell_cols, gb->cells, gb->overflow);
   HIP_OK(hipGetLastError());
@@ -3100,9 +3154,7 @@ __global__ __launch_bounds__(256) void joint_record_kernel(const lgx_task_params
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 4, q = t & 15;
   // no early return: the shuffles below need every lane of a group
-  const bool live = e < Pm->num_envs;
-  const int st = live ? status[e] : 1;
-  const int rs = live ? B.reset[e] : 0;
+  const auto [live, st, rs] = recording(status, B.reset, e, Pm->num_envs);
   const bool sample = st == 0 && !rs;
   const int D = Pm->num_dof;
   const bool mine = sample && q < D;
@@ -3110,16 +3162,9 @@ __global__ __launch_bounds__(256) void joint_record_kernel(const lgx_task_params
   float4* jq = reinterpret_cast<float4*>(joint + ((size_t)e * LGX_MAX_DOF + q) * LGX_JOINT_COLS);
   float r[LGX_JOINT_COLS], b[LGX_JOINT_BODY_COLS] = {0.f, 0.f, 0.f, 0.f}, ap = 0.f;
   bool sat = false, out = false;
-  if (sample) {
-    const float4 v = *bq;
-    b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
-  }
+  if (sample) load_row<1>(bq, b);
   if (mine) {
-    LGX_UNROLL
-    for (int i = 0; i < 4; ++i) {
-      const float4 v = jq[i];
-      r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
-    }
+    load_row<4>(jq, r);
     const size_t j = (size_t)e * D + q;
     const float a = q < Pm->num_actions ? B.actions[(size_t)e * Pm->num_actions + q] : 0.f;
     ap = joint_sample(r, b[0] == 0.f, B.torques[j], B.dof_state[2 * j], B.dof_state[2 * j + 1], a,
@@ -3136,13 +3181,10 @@ __global__ __launch_bounds__(256) void joint_record_kernel(const lgx_task_params
     if (q == 0) status[e] = episode_end_status(B, e);
     return;
   }
-  if (mine) {
-    LGX_UNROLL
-    for (int i = 0; i < 4; ++i) jq[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-  }
+  if (mine) store_row<4>(jq, r);
   if (q == 0) {
     joint_body_sample(b, P, any & 1, any & 2);
-    *bq = make_float4(b[0], b[1], b[2], b[3]);
+    store_row<1>(bq, b);
   }
 }
 
@@ -3153,11 +3195,10 @@ __global__ __launch_bounds__(256) void joint_record_kernel(const lgx_task_params
 // count; three joints a pass take 256 VGPRs and spill into AGPRs, two take 205 and spill nothing).
 // The maxima and minima ride the same scan in 12 fp32 partials x (per joint the maxima of
 // columns 3, 6, 7, of -column 10 and of column 11; the max of body 1; 1 when an env contributed),
-// combined by fmaxf in cell_reduce's shape: shuffle-down inside each wave, then the four wave
-// results. A maximum does not depend on the order, so they are exact; a cell without an env gets
-// zeros. Every pass scans every env's cell id in the same order, so the result depends only on the
-// records (and every pass forms the same out-of-grid count): no block writes its cell when there
-// are any, and block 0 publishes the count.
+// combined by cell_max (above: exact); a cell without an env gets zeros. Every pass scans every
+// env's cell id in the same order, so the result depends only on the records (and every pass forms
+// the same out-of-grid count): no block writes its cell when there are any, and block 0 publishes
+// the count.
 __global__ __launch_bounds__(256) void joint_reduce_kernel(const float* __restrict__ joint,
                                                            const float* __restrict__ body,
                                                            const uint8_t* __restrict__ status,
@@ -3169,8 +3210,7 @@ __global__ __launch_bounds__(256) void joint_reduce_kernel(const float* __restri
   constexpr int JP = 2, NS = LGX_JOINT_COLS - 1, NB = LGX_JOINT_BODY_COLS, NC = NS * JP + NB + 1, NX = 5 * JP + 2;
   static_assert(LGX_MAX_DOF % JP == 0, "every pass reduces JP joints");
   static_assert(LGX_JOINT_CELL_COLS == 2 + NB + LGX_MAX_DOF * (NS + 5), "the cell layout of include/lgx.h");
-  __shared__ float xs[4][NX];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   double* c = cells + (size_t)blockIdx.x * LGX_JOINT_CELL_COLS;
   for (int pass = 0; pass < LGX_MAX_DOF / JP; ++pass) {
     if (pass) __syncthreads();  // the previous pass's readers are done with the exchanges
@@ -3184,11 +3224,7 @@ __global__ __launch_bounds__(256) void joint_reduce_kernel(const float* __restri
       for (int jj = 0; jj < JP; ++jj) {
         const float4* r4 = reinterpret_cast<const float4*>(joint + ((size_t)e * LGX_MAX_DOF + JP * pass + jj) * LGX_JOINT_COLS);
         float r[LGX_JOINT_COLS];
-        LGX_UNROLL
-        for (int i = 0; i < 4; ++i) {
-          const float4 v = r4[i];
-          r[4 * i] = v.x; r[4 * i + 1] = v.y; r[4 * i + 2] = v.z; r[4 * i + 3] = v.w;
-        }
+        load_row<4>(r4, r);
         LGX_UNROLL
         for (int k = 0; k < NS; ++k) s[NS * jj + k] += (double)r[1 + k];
         x[5 * jj] = fmaxf(x[5 * jj], r[3]);
@@ -3210,18 +3246,10 @@ __global__ __launch_bounds__(256) void joint_reduce_kernel(const float* __restri
     });
     if (pass == 0 && tid == 0 && blockIdx.x == 0) *overflow = nbad;
     if (nbad != 0) return;  // (uniform over the block)
-    for (int o = 32; o > 0; o >>= 1) {
-      LGX_UNROLL
-      for (int k = 0; k < NX; ++k) x[k] = fmaxf(x[k], __shfl_down(x[k], o, 64));
-    }
-    if (lane == 0) {
-      LGX_UNROLL
-      for (int k = 0; k < NX; ++k) xs[wv][k] = x[k];
-    }
-    __syncthreads();
+    const auto folded = cell_max<NX>(x);
     if (tid < NX - 1 && (tid < 5 * JP || pass == 0)) {
-      const bool some = fmaxf(fmaxf(xs[0][NX - 1], xs[1][NX - 1]), fmaxf(xs[2][NX - 1], xs[3][NX - 1])) > 0.f;
-      const float m = fmaxf(fmaxf(xs[0][tid], xs[1][tid]), fmaxf(xs[2][tid], xs[3][tid]));
+      const bool some = folded(NX - 1) > 0.f;
+      const float m = folded(tid);
       const double v = !some ? 0.0 : (double)(tid % 5 == 3 && tid < 5 * JP ? -m : m);
       if (tid < 5 * JP) c[2 + NB + (NS + 5) * (JP * pass + tid / 5) + NS + tid % 5] = v;
       else c[1 + NB] = v;
@@ -3233,16 +3261,9 @@ __global__ __launch_bounds__(256) void joint_reduce_kernel(const float* __restri
 // shared checks of the three lgx_joint_* calls
 static int joint_check(lgx_env* env, const lgx_joint_buffers* jb, const char* what, bool reduce) {
   const std::string w(what);
-  if (int rc = check_call(env, jb, w, "joint")) return rc;
-  if (!jb->joint) return fail(env, w + ": joint is NULL");
-  if ((uintptr_t)jb->joint % 16 != 0) return fail(env, w + ": joint must be 16-byte aligned");
-  if (!jb->body) return fail(env, w + ": body is NULL");
-  if ((uintptr_t)jb->body % 16 != 0) return fail(env, w + ": body must be 16-byte aligned");
-  if (!jb->status) return fail(env, w + ": status is NULL");
-  if (!jb->overflow) return fail(env, w + ": overflow is NULL");
-  if (reduce && !jb->cells) return fail(env, w + ": cells is NULL");
-  if (jb->cell_rows < 1 || jb->cell_cols < 1 || (int64_t)jb->cell_rows * jb->cell_cols > (1 << 20))
-    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  if (int rc = record_buffers_check(env, jb, w, "joint", {{"joint", &lgx_joint_buffers::joint, true},
+                                                          {"body", &lgx_joint_buffers::body, true}}, reduce))
+    return rc;
   const lgx_buffers& b = env->buffers;
   if (int rc = check_bound(env, w, kNotBound, {{"torques", b.torques}, {"dof_state", b.dof_state},
                                                {"actions", b.actions}, {"reset", b.reset},
@@ -3276,8 +3297,7 @@ int lgx_joint_record(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream
     lgxh::joint_record(&env->params, &env->buffers, jb);
     return 0;
   }
-  const int64_t threads = (int64_t)env->params.num_envs * 16;
-  hipLaunchKernelGGL(lgx::joint_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::joint_record_kernel, lane_blocks(16, env->params.num_envs), dim3(256), 0,
                      (hipStream_t)hip_stream, env->d_params, env->d_buffers, jb->joint, jb->body, jb->status);
   HIP_OK(hipGetLastError());
   return 0;
@@ -3287,12 +3307,10 @@ int lgx_joint_reduce(lgx_env* env, const lgx_joint_buffers* jb, void* hip_stream
   if (int rc = joint_check(env, jb, "lgx_joint_reduce", true)) return rc;
   if (env->host) {
     const int bad = lgxh::joint_reduce(&env->params, &env->buffers, jb);
-    if (bad) return fail(env, "lgx_joint_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
-                              "outside the cell grid (cells not written)");
-    return 0;
+    return bad ? reduce_failed(env, "lgx_joint_reduce", bad) : 0;
   }
   const lgx_buffers& b = env->buffers;
-  hipLaunchKernelGGL(lgx::joint_reduce_kernel, dim3((unsigned)(jb->cell_rows * jb->cell_cols)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::joint_reduce_kernel, cell_blocks(jb->cell_rows, jb->cell_cols), dim3(256), 0,
                      (hipStream_t)hip_stream, jb->joint, jb->body, jb->status, b.terrain_levels, b.terrain_types,
                      jb->cell_ids, env->params.num_envs, jb->cell_rows, jb->cell_cols, jb->cells, jb->overflow);
   HIP_OK(hipGetLastError());
@@ -3337,30 +3355,21 @@ __global__ __launch_bounds__(256) void contact_record_kernel(const lgx_task_para
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = t >> 5, q = t & 31;
   // no early return: the shuffles below need every lane of a group
-  const bool live = e < Pm->num_envs;
-  const int st = live ? status[e] : 1;
-  const int rs = live ? B.reset[e] : 0;
+  const auto [live, st, rs] = recording(status, B.reset, e, Pm->num_envs);
   const bool open = st == 0, sample = open && !rs;
   const int NB = Pm->num_bodies;
   const bool mine = open && q < NB;
   float4* eq = reinterpret_cast<float4*>(envr + (size_t)e * LGX_CONTACT_ENV_COLS);
   float4* bq = reinterpret_cast<float4*>(body + ((size_t)e * LGX_MAX_BODIES + q) * LGX_CONTACT_COLS);
   float r[LGX_CONTACT_COLS], v[4] = {0.f, 0.f, 0.f, 0.f};
-  if (sample) {
-    const float4 x = eq[0];
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  }
+  if (sample) load_row<1>(eq, v);
   contact_part p = contact_none();
   if (mine) {
     const size_t row = (size_t)e * NB + q;
     const float* F = B.contact_forces + row * 3;
     float fn;
     if (sample) {
-      LGX_UNROLL
-      for (int i = 0; i < 3; ++i) {
-        const float4 x = bq[i];
-        r[4 * i] = x.x; r[4 * i + 1] = x.y; r[4 * i + 2] = x.z; r[4 * i + 3] = x.w;
-      }
+      load_row<3>(bq, r);
       const int16_t* hs = Pm->mesh_type == LGX_MESH_PLANE ? nullptr : B.height_samples;
       fn = contact_body_sample(r, v[0] == 0.f, F, B.rigid_body_states + row * 13, Pm, hs, edge_tol);
     } else {
@@ -3387,18 +3396,15 @@ __global__ __launch_bounds__(256) void contact_record_kernel(const lgx_task_para
       if (ns == 2) {
         float w[4];
         contact_env_terminal(w, p);
-        eq[1] = make_float4(w[0], w[1], w[2], w[3]);
+        store_row<1>(eq + 1, w);
       }
     }
     return;
   }
-  if (mine) {
-    LGX_UNROLL
-    for (int i = 0; i < 3; ++i) bq[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
-  }
+  if (mine) store_row<3>(bq, r);
   if (q == 0) {
     contact_env_sample(v, p);
-    eq[0] = make_float4(v[0], v[1], v[2], v[3]);
+    store_row<1>(eq, v);
   }
 }
 
@@ -3412,8 +3418,8 @@ __global__ __launch_bounds__(256) void contact_record_kernel(const lgx_task_para
 // bodies a pass would be 37 partials, at that edge, so BP = 2 (27 partials; VGPR count in DESIGN.md).
 // The maxima and minima ride the same scan in fp32 partials x (per body the maxima of columns 4, 10
 // and of -column 7, the last over the envs with samples only; the max of env column 3; 1 when an env
-// / an env with samples contributed), combined by fmaxf in cell_reduce's shape: order-independent,
-// hence exact; a cell without a contributing env gets zeros. Every pass scans every env's cell id in
+// / an env with samples contributed), combined by cell_max (above: exact); a cell without a
+// contributing env gets zeros. Every pass scans every env's cell id in
 // the same order and forms the same out-of-grid count: no block writes its cell when there are any,
 // and block 0 publishes the count.
 __global__ __launch_bounds__(256) void contact_reduce_kernel(const float* __restrict__ body,
@@ -3428,8 +3434,7 @@ __global__ __launch_bounds__(256) void contact_reduce_kernel(const float* __rest
   static_assert(LGX_MAX_BODIES % BP == 0, "every pass reduces BP bodies");
   static_assert(LGX_CONTACT_CELL_COLS == 8 + LGX_MAX_BODIES * PER, "the cell layout of include/lgx.h");
   static_assert(LGX_CONTACT_COLS == 12 && LGX_CONTACT_ENV_COLS == 8, "three and two float4");
-  __shared__ float xs[4][NX];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   double* c = cells + (size_t)blockIdx.x * LGX_CONTACT_CELL_COLS;
   for (int pass = 0; pass < LGX_MAX_BODIES / BP; ++pass) {
     if (pass) __syncthreads();  // the previous pass's readers are done with the exchanges
@@ -3482,19 +3487,11 @@ __global__ __launch_bounds__(256) void contact_reduce_kernel(const float* __rest
     });
     if (pass == 0 && tid == 0 && blockIdx.x == 0) *overflow = nbad;
     if (nbad != 0) return;  // (uniform over the block)
-    for (int o = 32; o > 0; o >>= 1) {
-      LGX_UNROLL
-      for (int k = 0; k < NX; ++k) x[k] = fmaxf(x[k], __shfl_down(x[k], o, 64));
-    }
-    if (lane == 0) {
-      LGX_UNROLL
-      for (int k = 0; k < NX; ++k) xs[wv][k] = x[k];
-    }
-    __syncthreads();
+    const auto folded = cell_max<NX>(x);
     if (tid < 3 * BP || (tid == 3 * BP && pass == 0)) {
       const int flag = (tid < 3 * BP && tid % 3 == 2) ? NX - 1 : NX - 2;
-      const bool some = fmaxf(fmaxf(xs[0][flag], xs[1][flag]), fmaxf(xs[2][flag], xs[3][flag])) > 0.f;
-      const float m = fmaxf(fmaxf(xs[0][tid], xs[1][tid]), fmaxf(xs[2][tid], xs[3][tid]));
+      const bool some = folded(flag) > 0.f;
+      const float m = folded(tid);
       const double v = !some ? 0.0 : (double)(flag == NX - 1 ? -m : m);
       if (tid < 3 * BP) c[8 + PER * (BP * pass + tid / 3) + 8 + tid % 3] = v;
       else c[4] = v;
@@ -3506,16 +3503,9 @@ __global__ __launch_bounds__(256) void contact_reduce_kernel(const float* __rest
 // shared checks of the three lgx_contact_* calls
 static int contact_check(lgx_env* env, const lgx_contact_buffers* cb, const char* what, bool reduce) {
   const std::string w(what);
-  if (int rc = check_call(env, cb, w, "contact")) return rc;
-  if (!cb->body) return fail(env, w + ": body is NULL");
-  if ((uintptr_t)cb->body % 16 != 0) return fail(env, w + ": body must be 16-byte aligned");
-  if (!cb->env) return fail(env, w + ": env is NULL");
-  if ((uintptr_t)cb->env % 16 != 0) return fail(env, w + ": env must be 16-byte aligned");
-  if (!cb->status) return fail(env, w + ": status is NULL");
-  if (!cb->overflow) return fail(env, w + ": overflow is NULL");
-  if (reduce && !cb->cells) return fail(env, w + ": cells is NULL");
-  if (cb->cell_rows < 1 || cb->cell_cols < 1 || (int64_t)cb->cell_rows * cb->cell_cols > (1 << 20))
-    return fail(env, w + ": cell_rows and cell_cols must be >= 1 (and their product at most 2^20)");
+  if (int rc = record_buffers_check(env, cb, w, "contact", {{"body", &lgx_contact_buffers::body, true},
+                                                            {"env", &lgx_contact_buffers::env, true}}, reduce))
+    return rc;
   if (!std::isfinite(cb->edge_tol) || cb->edge_tol < 0.f)
     return fail(env, w + ": edge_tol must be finite and not negative");
   const lgx_buffers& b = env->buffers;
@@ -3566,9 +3556,8 @@ int lgx_contact_record(lgx_env* env, const lgx_contact_buffers* cb, void* hip_st
     lgxh::contact_record(&env->params, &env->buffers, cb);
     return 0;
   }
-  const int64_t threads = (int64_t)env->params.num_envs * 32;
-  if (threads == 0) return 0;
-  hipLaunchKernelGGL(lgx::contact_record_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
+  if (env->params.num_envs == 0) return 0;
+  hipLaunchKernelGGL(lgx::contact_record_kernel, lane_blocks(32, env->params.num_envs), dim3(256), 0,
                      (hipStream_t)hip_stream, env->d_params, env->d_buffers, cb->body, cb->env, cb->status,
                      cb->edge_tol);
   HIP_OK(hipGetLastError());
@@ -3579,12 +3568,10 @@ int lgx_contact_reduce(lgx_env* env, const lgx_contact_buffers* cb, void* hip_st
   if (int rc = contact_check(env, cb, "lgx_contact_reduce", true)) return rc;
   if (env->host) {
     const int bad = lgxh::contact_reduce(&env->params, &env->buffers, cb);
-    if (bad) return fail(env, "lgx_contact_reduce: " + std::to_string(bad) + " envs have a terrain level / type (or cell id) "
-                              "outside the cell grid (cells not written)");
-    return 0;
+    return bad ? reduce_failed(env, "lgx_contact_reduce", bad) : 0;
   }
   const lgx_buffers& b = env->buffers;
-  hipLaunchKernelGGL(lgx::contact_reduce_kernel, dim3((unsigned)(cb->cell_rows * cb->cell_cols)), dim3(256), 0,
+  hipLaunchKernelGGL(lgx::contact_reduce_kernel, cell_blocks(cb->cell_rows, cb->cell_cols), dim3(256), 0,
                      (hipStream_t)hip_stream, cb->body, cb->env, cb->status, b.terrain_levels, b.terrain_types,
                      cb->cell_ids, env->params.num_envs, cb->cell_rows, cb->cell_cols, cb->cells, cb->overflow);
   HIP_OK(hipGetLastError());

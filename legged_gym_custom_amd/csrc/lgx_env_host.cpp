@@ -1197,11 +1197,30 @@ int eval_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_eval_b
   return 0;
 }
 
+// The start of a per-step record (trace, gait, joint) for env e: false when the env is frozen
+// (status != 0), or when it is reset in this step, which latches episode_end_status and takes no
+// sample.
+static bool still_recording(uint8_t* status, const lgx_buffers& B, int e) {
+  if (status[e] != 0) return false;
+  if (B.reset[e]) {
+    status[e] = episode_end_status(B, e);
+    return false;
+  }
+  return true;
+}
+
+// The *_begin of the records that start all zero: two per-env arrays of na and nb 4-byte entries per
+// env, the statuses and, for a record with cells, the overflow count.
+static void zero_records(void* a, size_t na, void* b, size_t nb, uint8_t* status, uint32_t* overflow, size_t N) {
+  static_assert(sizeof(float) == 4 && sizeof(int32_t) == 4, "4-byte entries");
+  memset(a, 0, 4 * na * N);
+  memset(b, 0, 4 * nb * N);
+  memset(status, 0, N);
+  if (overflow) *overflow = 0;
+}
+
 void trace_begin(const lgx_task_params* P, const lgx_trace_buffers* T) {
-  const size_t N = (size_t)P->num_envs;
-  memset(T->ring, 0, sizeof(float) * LGX_TRACE_COLS * N * (size_t)T->depth);
-  memset(T->count, 0, sizeof(int32_t) * N);
-  memset(T->status, 0, N);
+  zero_records(T->ring, LGX_TRACE_COLS * (size_t)T->depth, T->count, 1, T->status, nullptr, (size_t)P->num_envs);
 }
 
 // lgx_trace_record (include/lgx.h): the kernel's arithmetic (lgx_env.hip trace_record_kernel), the
@@ -1210,11 +1229,7 @@ void trace_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_trac
   const int N = P->num_envs, NB = P->num_bodies, depth = T->depth;
 #pragma omp parallel for schedule(static)
   for (int e = 0; e < N; ++e) {
-    if (T->status[e] != 0) continue;
-    if (B->reset[e]) {
-      T->status[e] = episode_end_status(*B, e);
-      continue;
-    }
+    if (!still_recording(T->status, *B, e)) continue;
     const int cnt = T->count[e];
     float* dst = T->ring + ((size_t)e * depth + (size_t)(cnt % depth)) * LGX_TRACE_COLS;
     for (int col = 0; col < 74; ++col) dst[col] = trace_col(col, P, *B, e);
@@ -1254,11 +1269,8 @@ void trace_gather(const lgx_task_params* P, const lgx_trace_buffers* T, const in
 }
 
 void gait_begin(const lgx_task_params* P, const lgx_gait_buffers* G) {
-  const size_t N = (size_t)P->num_envs;
-  memset(G->foot, 0, sizeof(float) * LGX_GAIT_FOOT_COLS * LGX_MAX_FEET * N);
-  memset(G->body, 0, sizeof(float) * LGX_GAIT_BODY_COLS * N);
-  memset(G->status, 0, N);
-  *G->overflow = 0;
+  zero_records(G->foot, LGX_GAIT_FOOT_COLS * LGX_MAX_FEET, G->body, LGX_GAIT_BODY_COLS, G->status, G->overflow,
+               (size_t)P->num_envs);
 }
 
 // lgx_gait_record (include/lgx.h): the kernel's arithmetic (lgx_env.hip gait_record_kernel), the
@@ -1268,11 +1280,7 @@ void gait_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_
   const float dt = P->dt;
 #pragma omp parallel for schedule(static)
   for (int e = 0; e < N; ++e) {
-    if (G->status[e] != 0) continue;
-    if (B->reset[e]) {
-      G->status[e] = episode_end_status(*B, e);
-      continue;
-    }
+    if (!still_recording(G->status, *B, e)) continue;
     float* body = G->body + (size_t)e * LGX_GAIT_BODY_COLS;
     const bool first = body[0] == 0.f;
     int bits = 0;
@@ -1309,11 +1317,8 @@ int gait_reduce(const lgx_task_params* P, const lgx_buffers* B, const lgx_gait_b
 }
 
 void joint_begin(const lgx_task_params* P, const lgx_joint_buffers* J) {
-  const size_t N = (size_t)P->num_envs;
-  memset(J->joint, 0, sizeof(float) * LGX_JOINT_COLS * LGX_MAX_DOF * N);
-  memset(J->body, 0, sizeof(float) * LGX_JOINT_BODY_COLS * N);
-  memset(J->status, 0, N);
-  *J->overflow = 0;
+  zero_records(J->joint, LGX_JOINT_COLS * LGX_MAX_DOF, J->body, LGX_JOINT_BODY_COLS, J->status, J->overflow,
+               (size_t)P->num_envs);
 }
 
 // The kernel's 16-lane group as one value: joint_power_sum's butterfly on all 16 slots at once.
@@ -1330,11 +1335,7 @@ void joint_record(const lgx_task_params* P, const lgx_buffers* B, const lgx_join
   const int N = P->num_envs, D = P->num_dof, A = P->num_actions;
 #pragma omp parallel for schedule(static)
   for (int e = 0; e < N; ++e) {
-    if (J->status[e] != 0) continue;
-    if (B->reset[e]) {
-      J->status[e] = episode_end_status(*B, e);
-      continue;
-    }
+    if (!still_recording(J->status, *B, e)) continue;
     float* body = J->body + (size_t)e * LGX_JOINT_BODY_COLS;
     const bool first = body[0] == 0.f;
     Slots16 s = {};

@@ -293,7 +293,59 @@ class LeggedRobot(BaseTask):
         self._native.trace_gather(tb, ids, out, out_len, self._stream())
         return out, out_len
 
-    # ------------------------------------------------------------------ gait record
+    # ------------------------------------------------------------------ record families
+    # kind -> the attributes its current set is published under: the two records, the status, the
+    # cells, the overflow count (the set's tensors in this order) and the set itself
+    _RECORD_ATTRS = {
+        "gait": ("gait_foot", "gait_body", "gait_status", "_gait_cells", "_gait_overflow", "_gait"),
+        "joint": ("joint_rec", "joint_body", "joint_status", "_joint_cells", "_joint_overflow", "_joint"),
+        "contact": ("contact_body", "contact_env", "contact_status", "_contact_cells", "_contact_overflow", "_contact"),
+    }
+
+    def _record_set(self, kind, rows, cols, cell_ids, **scalars):
+        """The tensors of a record family (_abi.RECORD_KINDS[kind]), allocated once per (rows, cols,
+        cell_ids tensor, scalars) so a captured loop replays on fixed addresses. rows / cols None:
+        the terrain grid (1 x 1 without one). Every key asked for keeps its tensors (a loop captured
+        on one set never replays on freed memory); the call makes that set the current one and
+        publishes it under the kind's _RECORD_ATTRS."""
+        if rows is None or cols is None:
+            grid = getattr(self, "terrain_levels", None) is not None
+            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
+        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr(), *scalars.values())
+        if not hasattr(self, "_record_sets"):
+            self._record_sets = {}  # kind -> key -> the buffers struct (which keeps its tensors, cell_ids included)
+        sets = self._record_sets.setdefault(kind, {})
+        if key not in sets:
+            z, n = self._zeros, self.num_envs
+            _, members, cell_cols, _ = _abi.RECORD_KINDS[kind]
+            sets[key] = self._native._record_buffers(
+                kind, [z(n, *shape) for _, shape in members], z(n, dtype=torch.uint8),
+                z(key[0], key[1], cell_cols, dtype=torch.float64), z(1, dtype=torch.int32), cell_ids, **scalars)
+        cur = sets[key]
+        for attr, value in zip(self._RECORD_ATTRS[kind], (*cur._keep[:5], cur)):
+            setattr(self, attr, value)
+        return cur
+
+    def _record_current(self, kind):
+        cur = getattr(self, self._RECORD_ATTRS[kind][5], None)
+        if cur is None:
+            raise RuntimeError(f"no {kind} record: call {kind}_buffers(...) first")
+        return cur
+
+    def record_begin(self, kind):
+        """lgx_<kind>_begin on the kind's current set."""
+        self._native._record_call(f"lgx_{kind}_begin", self._record_current(kind), self._stream())
+
+    def record_step(self, kind):
+        """lgx_<kind>_record on the kind's current set, for the step just run."""
+        self._native._record_call(f"lgx_{kind}_record", self._record_current(kind), self._stream())
+
+    def record_cells(self, kind):
+        """lgx_<kind>_reduce on the kind's current set, then its cells float64 on the host."""
+        cur = self._record_current(kind)
+        return self._reduced_cells(f"lgx_{kind}_reduce", cur, cur._keep[4], "a terrain level / type (or cell id)",
+                                   cur._keep[3])[0]
+
     def gait_buffers(self, rows=None, cols=None, cell_ids=None):
         """The gait record's tensors (include/lgx.h lgx_gait_buffers, ABI 12), allocated once per
         (rows, cols, cell_ids tensor) so a captured loop replays on fixed addresses: gait_foot
@@ -303,43 +355,23 @@ class LeggedRobot(BaseTask):
         the caller), instead of terrain level x type. Every key asked for keeps its tensors (a loop
         captured on one set never replays on freed memory); the call makes that set the current
         one, which gait_begin / gait_record / gait_cells and the three attributes refer to."""
-        if rows is None or cols is None:
-            grid = getattr(self, "terrain_levels", None) is not None
-            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
-        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr())
-        if not hasattr(self, "_gaits"):
-            self._gaits = {}  # key -> lgx_gait_buffers (which keeps its tensors, cell_ids included)
-        if key not in self._gaits:
-            z, n = self._zeros, self.num_envs
-            self._gaits[key] = self._native.gait_buffers(
-                z(n, _abi.MAX_FEET, _abi.GAIT_FOOT_COLS), z(n, _abi.GAIT_BODY_COLS), z(n, dtype=torch.uint8),
-                z(key[0], key[1], _abi.GAIT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32), cell_ids=cell_ids)
-        self._gait = self._gaits[key]
-        self.gait_foot, self.gait_body, self.gait_status, self._gait_cells, self._gait_overflow = self._gait._keep[:5]
-        return self._gait
-
-    def _gait_buffers(self):
-        if getattr(self, "_gait", None) is None:
-            raise RuntimeError("no gait record: call gait_buffers(...) first")
-        return self._gait
+        return self._record_set("gait", rows, cols, cell_ids)
 
     def gait_begin(self):
         """lgx_gait_begin: zero the gait records and record every env's next (first) episode."""
-        self._native.gait_begin(self._gait_buffers(), self._stream())
+        self.record_begin("gait")
 
     def gait_record(self):
         """lgx_gait_record for the step just run (call after every step(); stream-ordered, no host
         sync, capturable)."""
-        self._native.gait_record(self._gait_buffers(), self._stream())
+        self.record_step("gait")
 
     def gait_cells(self):
         """lgx_gait_reduce, then the cells [rows, cols, 61] float64 on the host: the number of
         finished envs with samples, the sums of their 12 body columns and of columns 4..15 of each
         foot. Synchronises. An env whose cell lies outside the grid is an error."""
-        return self._reduced_cells("lgx_gait_reduce", self._gait_buffers(), self._gait_overflow,
-                                   "a terrain level / type (or cell id)", self._gait_cells)[0]
+        return self.record_cells("gait")
 
-    # ------------------------------------------------------------------ joint-load record
     def joint_buffers(self, rows=None, cols=None, cell_ids=None):
         """The joint-load record's tensors (include/lgx.h lgx_joint_buffers, ABI 13), allocated once
         per (rows, cols, cell_ids tensor) so a captured loop replays on fixed addresses: joint_rec
@@ -347,44 +379,24 @@ class LeggedRobot(BaseTask):
         [N] (the eval_status rule) and the cells [rows, cols, 246]. rows, cols and cell_ids as in
         gait_buffers; every key asked for keeps its tensors, and the call makes that set the current
         one, which joint_begin / joint_record / joint_cells and the three attributes refer to."""
-        if rows is None or cols is None:
-            grid = getattr(self, "terrain_levels", None) is not None
-            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
-        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr())
-        if not hasattr(self, "_joints"):
-            self._joints = {}  # key -> lgx_joint_buffers (which keeps its tensors, cell_ids included)
-        if key not in self._joints:
-            z, n = self._zeros, self.num_envs
-            self._joints[key] = self._native.joint_buffers(
-                z(n, _abi.MAX_DOF, _abi.JOINT_COLS), z(n, _abi.JOINT_BODY_COLS), z(n, dtype=torch.uint8),
-                z(key[0], key[1], _abi.JOINT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32), cell_ids=cell_ids)
-        self._joint = self._joints[key]
-        self.joint_rec, self.joint_body, self.joint_status, self._joint_cells, self._joint_overflow = self._joint._keep[:5]
-        return self._joint
-
-    def _joint_buffers(self):
-        if getattr(self, "_joint", None) is None:
-            raise RuntimeError("no joint record: call joint_buffers(...) first")
-        return self._joint
+        return self._record_set("joint", rows, cols, cell_ids)
 
     def joint_begin(self):
         """lgx_joint_begin: zero the joint records and record every env's next (first) episode."""
-        self._native.joint_begin(self._joint_buffers(), self._stream())
+        self.record_begin("joint")
 
     def joint_record(self):
         """lgx_joint_record for the step just run (call after every step(); stream-ordered, no host
         sync, capturable)."""
-        self._native.joint_record(self._joint_buffers(), self._stream())
+        self.record_step("joint")
 
     def joint_cells(self):
         """lgx_joint_reduce, then the cells [rows, cols, 246] float64 on the host: the number of
         finished envs with samples, the sums and the peak of their body columns and, per joint, the
         sums of columns 1..15 and the extremes of columns 3, 6, 7, 10 and 11. Synchronises. An env
         whose cell lies outside the grid is an error."""
-        return self._reduced_cells("lgx_joint_reduce", self._joint_buffers(), self._joint_overflow,
-                                   "a terrain level / type (or cell id)", self._joint_cells)[0]
+        return self.record_cells("joint")
 
-    # ------------------------------------------------------------------ contact record
     def contact_buffers(self, rows=None, cols=None, cell_ids=None, edge_tol=0.05):
         """The contact record's tensors (include/lgx.h lgx_contact_buffers, ABI 14), allocated once
         per (rows, cols, cell_ids tensor, edge_tol) so a captured loop replays on fixed addresses:
@@ -394,44 +406,23 @@ class LeggedRobot(BaseTask):
         contact onset counts as on an edge. Every key asked for keeps its tensors, and the call makes
         that set the current one, which contact_begin / contact_record / contact_cells and the three
         attributes refer to."""
-        if rows is None or cols is None:
-            grid = getattr(self, "terrain_levels", None) is not None
-            rows, cols = (int(self.cfg.terrain.num_rows), int(self.cfg.terrain.num_cols)) if grid else (1, 1)
-        key = (int(rows), int(cols), None if cell_ids is None else cell_ids.data_ptr(), float(edge_tol))
-        if not hasattr(self, "_contacts"):
-            self._contacts = {}  # key -> lgx_contact_buffers (which keeps its tensors, cell_ids included)
-        if key not in self._contacts:
-            z, n = self._zeros, self.num_envs
-            self._contacts[key] = self._native.contact_buffers(
-                z(n, _abi.MAX_BODIES, _abi.CONTACT_COLS), z(n, _abi.CONTACT_ENV_COLS), z(n, dtype=torch.uint8),
-                z(key[0], key[1], _abi.CONTACT_CELL_COLS, dtype=torch.float64), z(1, dtype=torch.int32),
-                cell_ids=cell_ids, edge_tol=key[3])
-        self._contact = self._contacts[key]
-        (self.contact_body, self.contact_env, self.contact_status, self._contact_cells,
-         self._contact_overflow) = self._contact._keep[:5]
-        return self._contact
-
-    def _contact_buffers(self):
-        if getattr(self, "_contact", None) is None:
-            raise RuntimeError("no contact record: call contact_buffers(...) first")
-        return self._contact
+        return self._record_set("contact", rows, cols, cell_ids, edge_tol=float(edge_tol))
 
     def contact_begin(self):
         """lgx_contact_begin: reset the contact records and record every env's next (first) episode."""
-        self._native.contact_begin(self._contact_buffers(), self._stream())
+        self.record_begin("contact")
 
     def contact_record(self):
         """lgx_contact_record for the step just run (call after every step(); stream-ordered, no host
         sync, capturable)."""
-        self._native.contact_record(self._contact_buffers(), self._stream())
+        self.record_step("contact")
 
     def contact_cells(self):
         """lgx_contact_reduce, then the cells [rows, cols, 320] float64 on the host: the number of
         finished envs, the sums and the peak of their env columns, the falls and, per body, the sums
         of columns 1, 2, 3, 5, 6, 8, 9, 11, the extremes of columns 4, 10 and 7 and the two fall
         histograms. Synchronises. An env whose cell lies outside the grid is an error."""
-        return self._reduced_cells("lgx_contact_reduce", self._contact_buffers(), self._contact_overflow,
-                                   "a terrain level / type (or cell id)", self._contact_cells)[0]
+        return self.record_cells("contact")
 
     def _stream(self):
         """The HIP stream the env's launches are ordered on (0 for the host backend)."""

@@ -59,6 +59,7 @@ Single process only: sharded evaluation (env shards over ranks) is out of scope.
 """
 import math
 import time
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -368,6 +369,25 @@ def contact_cell_report(row, dt, body_names, feet, termination, penalised):
             "foot_edge_onset_share": div(sum(b[5] for b in foot), sum(b[1] for b in foot)), "bodies": bodies}
 
 
+# The record families a run can keep, in the order the loop body records them. kind: the env's
+# <kind>_buffers / record_begin / record_step / record_cells; flag: the keyword of run, run_push_test
+# and run_command_test; key: the report entry; last: the evaluator attribute that holds the finished
+# run's cells ([rows, cols, 61 / 246 / 320] float64, None without the record); total: all cells'
+# rows [n, cols] -> the total's row; report(row, *args(env)): the entry of one cell row;
+# buffers: extra keywords of <kind>_buffers.
+Record = namedtuple("Record", "kind flag key last total report args buffers")
+RECORDS = (
+    Record("gait", "gait", "gait", "last_gait_cells", lambda flat: flat.sum(0), gait_cell_report,
+           lambda env: (float(env.dt), [env.body_names[i] for i in env.feet_indices.tolist()]), {}),
+    Record("joint", "joints", "joints", "last_joint_cells", joint_total_row, joint_cell_report,
+           lambda env: (float(env.dt), env.dof_names, env._native.params), {}),
+    Record("contact", "contacts", "contacts", "last_contact_cells", contact_total_row, contact_cell_report,
+           lambda env: (float(env.dt), env.body_names, env.feet_indices.tolist(),
+                        env.termination_contact_indices.tolist(), env.penalised_contact_indices.tolist()),
+           {"edge_tol": EDGE_RELIEF_M}),
+)
+
+
 def _min_max(t, kind):
     return None if t is None else [kind(t.min()), kind(t.max())]
 
@@ -394,12 +414,9 @@ class PolicyEvaluator:
         self.last_cmd_cells = self.last_cmd_bins = None
         self._trace_depth = None     # the flight recorder's depth in the run under way (None: off)
         self.last_trace_depth = None  # the depth of the last finished run, None when it was not traced
-        self._gait = False            # whether the run under way keeps the gait record
-        self.last_gait_cells = None   # [rows, cols, 61] of the last finished run, None without gait=True
-        self._joints = False          # whether the run under way keeps the joint-load record
-        self.last_joint_cells = None  # [rows, cols, 246] of the last finished run, None without joints=True
-        self._contacts = False          # whether the run under way keeps the contact record
-        self.last_contact_cells = None  # [rows, cols, 320] of the last finished run, None without contacts=True
+        self._records = ()           # the RECORDS the run under way keeps
+        for r in RECORDS:
+            setattr(self, r.last, None)  # last_gait_cells, last_joint_cells, last_contact_cells
         if self.on_gpu:
             from legged_gym_custom_amd.rsl_rl.algorithms.s8_act import S8Act
             if S8Act.supported(self.alg):
@@ -445,12 +462,8 @@ class PolicyEvaluator:
         env = self.env
         env.step(self.act())
         env.eval_accumulate(ev)
-        if self._gait:
-            env.gait_record()
-        if self._joints:
-            env.joint_record()
-        if self._contacts:
-            env.contact_record()
+        for r in self._records:
+            env.record_step(r.kind)
         if self._trace_depth is not None:
             env.trace_record()
 
@@ -468,12 +481,8 @@ class PolicyEvaluator:
             env.reset()
             env.episode_length_buf = torch.zeros_like(env.episode_length_buf)
             env.eval_begin(ev)
-            if self._gait:
-                env.gait_begin()
-            if self._joints:
-                env.joint_begin()
-            if self._contacts:
-                env.contact_begin()
+            for r in self._records:
+                env.record_begin(r.kind)
             if self._trace_depth is not None:
                 env.trace_begin()
 
@@ -482,11 +491,20 @@ class PolicyEvaluator:
         depth, allocated once per depth) and whether it keeps the gait record, the joint-load record
         and the contact record (the mode picks the env's gait / joint / contact buffers: their cell
         key is the mode's)."""
-        self.last_trace_depth = self.last_gait_cells = self.last_joint_cells = self.last_contact_cells = None
-        self._gait, self._joints, self._contacts = bool(gait), bool(joints), bool(contacts)
+        flags = {"gait": gait, "joints": joints, "contacts": contacts}
+        self.last_trace_depth = None
+        for r in RECORDS:
+            setattr(self, r.last, None)
+        self._records = tuple(r for r in RECORDS if flags[r.flag])
         self._trace_depth = None if trace_depth is None else int(trace_depth)
         if self._trace_depth is not None:
             self.env.trace_buffers(self._trace_depth)
+
+    def _record_buffers(self, *grid):
+        """Make the env's buffers of the run's records current: grid = (rows, cols, cell_ids) for a
+        mode whose bin is the cell key, nothing for the terrain grid."""
+        for r in self._records:
+            getattr(self.env, r.kind + "_buffers")(*grid, **r.buffers)
 
     def _capture(self, ev=None):
         """The loop body as one hipGraph (the runner's _capture_rollout is the model): one eager
@@ -541,12 +559,7 @@ class PolicyEvaluator:
         contact_records(). False: nothing changes."""
         env = self.env
         self._set_trace(trace_depth, gait, joints, contacts)
-        if self._gait:
-            env.gait_buffers()  # the terrain grid is the cell key
-        if self._joints:
-            env.joint_buffers()  # likewise
-        if self._contacts:
-            env.contact_buffers(edge_tol=EDGE_RELIEF_M)  # likewise
+        self._record_buffers()  # the terrain grid is the cell key
         saved = []  # (buffer, its values before this run)
         try:
             if action_delay_s is not None:
@@ -560,12 +573,9 @@ class PolicyEvaluator:
                 env.set_motor_strength(motor_strength)  # (the first one allocates: refused once a loop is captured)
                 if not had:
                     saved.append((env.motor_strengths, torch.ones_like(env.motor_strengths)))
-            cells, gcells, head, rates = self._drive("_graph", (), num_steps, graph, env.eval_cells)
+            cells, head, rates = self._drive("_graph", (), num_steps, graph, env.eval_cells)
             out = self.report(cells, head["num_steps"], rates["wall_s"], head["graph"])
-            bins = [cell for row in out["cells"] for cell in row]
-            self._attach_gait(gcells, out["total"], bins)
-            self._attach_joints(out["total"], bins)
-            self._attach_contacts(out["total"], bins)
+            self._attach_records(out["total"], [cell for row in out["cells"] for cell in row])
             return out
         finally:
             for buf, old in saved:
@@ -579,13 +589,13 @@ class PolicyEvaluator:
         buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
         always, when the run ends or fails. read_cells(): the mode's reduce and host read
         (synchronises), one tensor or a tuple with the [rows, cols, 12] cells first.
-        Returns (what read_cells returned, the gait cells or None, the report's common head, its
-        wall_s / env_steps_per_s tail) and sets last_cells, last_trace_depth, last_gait_cells and
-        last_joint_cells / last_contact_cells (the cells of a joints / contacts run)."""
+        Returns (what read_cells returned, the report's common head, its wall_s / env_steps_per_s
+        tail) and sets last_cells, last_trace_depth and the RECORDS' last_*_cells (the cells of the
+        records the run kept)."""
         env = self.env
         steps = int(env.max_episode_length) + 1 if num_steps is None else int(num_steps)
         use_graph = bool(graph) and self.on_gpu and getattr(env, "graph_capturable", False)
-        gkey = key + (self._trace_depth, self._gait, self._joints, self._contacts)
+        gkey = key + (self._trace_depth,) + tuple(r in self._records for r in RECORDS)
         try:
             ev = prepare() if prepare else None
             if use_graph and (getattr(self, slot) is None or getattr(self, slot + "_key") != gkey):
@@ -596,18 +606,16 @@ class PolicyEvaluator:
                 started()
             t0 = self._loop(steps, getattr(self, slot) if use_graph else None, ev)
             cells = read_cells()
-            gcells = env.gait_cells() if self._gait else None
-            jcells = env.joint_cells() if self._joints else None
-            ccells = env.contact_cells() if self._contacts else None
+            rcells = [env.record_cells(r.kind) for r in self._records]
             wall = time.perf_counter() - t0
         finally:
             if cleanup:
                 cleanup()
         self.last_cells = cells[0] if isinstance(cells, tuple) else cells  # as lgx_eval_reduce wrote them
-        self.last_trace_depth, self.last_gait_cells = self._trace_depth, gcells  # ([rows, cols, 61] float64)
-        self.last_joint_cells = jcells  # ([rows, cols, 246] float64)
-        self.last_contact_cells = ccells  # ([rows, cols, 320] float64)
-        return cells, gcells, self._head(steps, use_graph), self._rates(steps, wall)
+        self.last_trace_depth = self._trace_depth
+        for r, c in zip(self._records, rcells):
+            setattr(self, r.last, c)
+        return cells, self._head(steps, use_graph), self._rates(steps, wall)
 
     def _head(self, steps, graph):
         return {"policy": self.policy, "num_envs": int(self.env.num_envs), "num_steps": steps, "dt": float(self.env.dt),
@@ -616,44 +624,19 @@ class PolicyEvaluator:
     def _rates(self, steps, wall):
         return {"wall_s": wall, "env_steps_per_s": steps * self.env.num_envs / wall if wall > 0 else None}
 
-    def _attach_gait(self, gcells, total, bins):
-        """The "gait" entry (gait_cell_report) of the total and of every bin; bins: the report's cells
-        or bins flat, in the order of gcells' cells. Nothing without a gait record."""
-        if gcells is None:
-            return
-        env = self.env
-        dt, names = float(env.dt), [env.body_names[i] for i in env.feet_indices.tolist()]
-        flat = gcells.reshape(-1, gcells.shape[2])
-        total["gait"] = gait_cell_report(flat.sum(0), dt, names)
-        for row, b in zip(flat, bins):
-            b["gait"] = gait_cell_report(row, dt, names)
-
-    def _attach_joints(self, total, bins):
-        """The "joints" entry (joint_cell_report) of the total and of every bin, from the finished
-        run's last_joint_cells; bins as in _attach_gait. Nothing without a joint-load record."""
-        jcells = self.last_joint_cells
-        if jcells is None:
-            return
-        env = self.env
-        dt, names, params = float(env.dt), env.dof_names, env._native.params
-        flat = jcells.reshape(-1, jcells.shape[2])
-        total["joints"] = joint_cell_report(joint_total_row(flat), dt, names, params)
-        for row, b in zip(flat, bins):
-            b["joints"] = joint_cell_report(row, dt, names, params)
-
-    def _attach_contacts(self, total, bins):
-        """The "contacts" entry (contact_cell_report) of the total and of every bin, from the finished
-        run's last_contact_cells; bins as in _attach_gait. Nothing without a contact record."""
-        ccells = self.last_contact_cells
-        if ccells is None:
-            return
-        env = self.env
-        args = (float(env.dt), env.body_names, env.feet_indices.tolist(), env.termination_contact_indices.tolist(),
-                env.penalised_contact_indices.tolist())
-        flat = ccells.reshape(-1, ccells.shape[2])
-        total["contacts"] = contact_cell_report(contact_total_row(flat), *args)
-        for row, b in zip(flat, bins):
-            b["contacts"] = contact_cell_report(row, *args)
+    def _attach_records(self, total, bins):
+        """The report entry (Record.key, by Record.report) of every record the finished run kept, in
+        the total and in every bin, from its last_*_cells; bins: the report's cells or bins flat, in
+        the order of the record's cells. Nothing without a record."""
+        for r in RECORDS:
+            rcells = getattr(self, r.last)
+            if rcells is None:
+                continue
+            args = r.args(self.env)
+            flat = rcells.reshape(-1, rcells.shape[2])
+            total[r.key] = r.report(r.total(flat), *args)
+            for row, b in zip(flat, bins):
+                b[r.key] = r.report(row, *args)
 
     def _switch_step(self, at_s, test):
         """at_s (seconds into the episode) as an episode step of the push / command test."""
@@ -667,35 +650,29 @@ class PolicyEvaluator:
         """Each env's bin of `count`: randperm(num_envs, seeded with env.seed) % count."""
         return torch.randperm(self.env.num_envs, generator=torch.Generator().manual_seed(int(self.env.seed))) % count
 
+    def _records_of(self, r):
+        """The per-env records of RECORDS entry r of the last run, numpy arrays on the host under
+        their lgx_<kind>_buffers member names, and the status."""
+        if getattr(self, r.last) is None:
+            raise RuntimeError(f"{r.kind}_records(): the last run kept no {r.kind} record (pass {r.flag}=True to run, "
+                               "run_push_test or run_command_test first)")
+        names = [name for name, _ in _abi.RECORD_KINDS[r.kind][1]] + ["status"]
+        return {name: getattr(self.env, attr).cpu().numpy() for name, attr in zip(names, self.env._RECORD_ATTRS[r.kind])}
+
     def gait_records(self):
         """The per-env gait records of the last run (it must have been one with gait=True), numpy
         arrays on the host: foot [N, 4, 16], body [N, 12] and status [N] (lgx_gait_buffers)."""
-        if self.last_gait_cells is None:
-            raise RuntimeError("gait_records(): the last run kept no gait record (pass gait=True to run, "
-                               "run_push_test or run_command_test first)")
-        env = self.env
-        return {"foot": env.gait_foot.cpu().numpy(), "body": env.gait_body.cpu().numpy(),
-                "status": env.gait_status.cpu().numpy()}
+        return self._records_of(RECORDS[0])
 
     def joint_records(self):
         """The per-env joint-load records of the last run (it must have been one with joints=True),
         numpy arrays on the host: joint [N, 12, 16], body [N, 4] and status [N] (lgx_joint_buffers)."""
-        if self.last_joint_cells is None:
-            raise RuntimeError("joint_records(): the last run kept no joint record (pass joints=True to run, "
-                               "run_push_test or run_command_test first)")
-        env = self.env
-        return {"joint": env.joint_rec.cpu().numpy(), "body": env.joint_body.cpu().numpy(),
-                "status": env.joint_status.cpu().numpy()}
+        return self._records_of(RECORDS[1])
 
     def contact_records(self):
         """The per-env contact records of the last run (it must have been one with contacts=True),
         numpy arrays on the host: body [N, 24, 12], env [N, 8] and status [N] (lgx_contact_buffers)."""
-        if self.last_contact_cells is None:
-            raise RuntimeError("contact_records(): the last run kept no contact record (pass contacts=True to run, "
-                               "run_push_test or run_command_test first)")
-        env = self.env
-        return {"body": env.contact_body.cpu().numpy(), "env": env.contact_env.cpu().numpy(),
-                "status": env.contact_status.cpu().numpy()}
+        return self._records_of(RECORDS[2])
 
     def _loop(self, steps, g, ev):
         """steps x the loop body (g: its captured graph, or None for the eager loop) recording
@@ -760,15 +737,10 @@ class PolicyEvaluator:
             env.set_push_schedule(0, dvel)  # (the first one allocates: refused once a loop is captured)
             ev = env.push_eval_buffers(*key)
             env.push_cell_ids.copy_(bins.to(torch.int32))
-            if self._gait:
-                env.gait_buffers(S, D, env.push_cell_ids)  # the bin is the cell key
-            if self._joints:
-                env.joint_buffers(S, D, env.push_cell_ids)
-            if self._contacts:
-                env.contact_buffers(S, D, env.push_cell_ids, edge_tol=EDGE_RELIEF_M)
+            self._record_buffers(S, D, env.push_cell_ids)  # the bin is the cell key
             return ev
 
-        (cells, pcells), gcells, head, rates = self._drive(
+        (cells, pcells), head, rates = self._drive(
             "_push_graph", key, num_steps, graph, env.eval_push_cells, prepare,
             lambda: env.set_push_schedule(step, dvel),  # after begin: its reset ends with an env step of its own
             env.clear_push_schedule)
@@ -779,10 +751,7 @@ class PolicyEvaluator:
                "push_step": step, "push_at_s": step * dt, "settle_tol": float(settle_tol),
                "total": both(cells.reshape(-1, cells.shape[2]).sum(0), pcells.reshape(-1, pcells.shape[2]).sum(0)),
                "bins": [[both(cells[s, d], pcells[s, d]) for d in range(D)] for s in range(S)], **rates}
-        flat = [b for row in out["bins"] for b in row]
-        self._attach_gait(gcells, out["total"], flat)
-        self._attach_joints(out["total"], flat)
-        self._attach_contacts(out["total"], flat)
+        self._attach_records(out["total"], [b for row in out["bins"] for b in row])
         return out
 
     # ------------------------------------------------------------------ command response
@@ -843,16 +812,11 @@ class PolicyEvaluator:
             ev = env.cmd_eval_buffers(*key)
             env.cmd_cell_ids.copy_(bins.to(torch.int32))
             env.cmd_switch_step.fill_(step)
-            if self._gait:
-                env.gait_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
-            if self._joints:
-                env.joint_buffers(nx, ny * nw, env.cmd_cell_ids)
-            if self._contacts:
-                env.contact_buffers(nx, ny * nw, env.cmd_cell_ids, edge_tol=EDGE_RELIEF_M)
+            self._record_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
             return ev
 
-        (cells, ccells), gcells, head, rates = self._drive("_cmd_graph", key, num_steps, graph, env.eval_command_cells,
-                                                           prepare, cleanup=env.clear_command_schedule)
+        (cells, ccells), head, rates = self._drive("_cmd_graph", key, num_steps, graph, env.eval_command_cells,
+                                                   prepare, cleanup=env.clear_command_schedule)
         self.last_cmd_cells, self.last_cmd_bins = ccells, bins
         w = self.mass * self.gravity
         both = lambda c, p, cmd: {**cell_report(c, dt, w), **command_cell_report(p, dt, cmd)}  # noqa: E731
@@ -863,10 +827,7 @@ class PolicyEvaluator:
                "yaw_tol": float(yaw_tol), "total": total,
                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
                           for iw in range(nw)] for iy in range(ny)] for ix in range(nx)], **rates}
-        flat = [b for plane in out["bins"] for row in plane for b in row]
-        self._attach_gait(gcells, total, flat)
-        self._attach_joints(total, flat)
-        self._attach_contacts(total, flat)
+        self._attach_records(total, [b for plane in out["bins"] for row in plane for b in row])
         return out
 
     # ------------------------------------------------------------------ flight recorder

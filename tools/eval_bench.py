@@ -99,51 +99,32 @@ def main():
             ev.run_command_test(a.cmd_vx, vy=a.cmd_vy, yaw=a.cmd_yaw, num_steps=a.steps or 200, graph=False)
         print(json.dumps({"profiled_steps": r["num_steps"], "total": r["total"]}))
         return
-    ev.run(20)  # warm both paths (the capture included)
-    ev.run(20, graph=False)
     rates = {"graph": [], "eager": []}
-    push = (lambda steps, graph: ev.run_push_test(a.push_vel, directions=a.push_dirs, num_steps=steps, graph=graph))
-    cmd = (lambda steps, graph: ev.run_command_test(a.cmd_vx, vy=a.cmd_vy, yaw=a.cmd_yaw, num_steps=steps, graph=graph))
+    runs = {"": ev.run}  # mode prefix -> the run it times, called with (steps, graph)
+
+    def add(prefix, run):
+        runs[prefix] = run
+        rates.update({prefix + "_graph": [], prefix + "_eager": []})
+
     if a.push_vel:
-        rates.update(push_graph=[], push_eager=[])
-        push(20, True)
-        push(20, False)
+        add("push", lambda steps, graph: ev.run_push_test(a.push_vel, directions=a.push_dirs, num_steps=steps, graph=graph))
     if a.cmd_vx:
-        rates.update(cmd_graph=[], cmd_eager=[])
-        cmd(20, True)
-        cmd(20, False)
-    gaited = (lambda steps, graph: ev.run(steps, graph, gait=True))
-    if a.gait:
-        rates.update(gait_graph=[], gait_eager=[])
-        gaited(20, True)
-        gaited(20, False)
-    jointed = (lambda steps, graph: ev.run(steps, graph, joints=True))
-    if a.joints:
-        rates.update(joints_graph=[], joints_eager=[])
-        jointed(20, True)
-        jointed(20, False)
-    touched = (lambda steps, graph: ev.run(steps, graph, contacts=True))
-    if a.contacts:
-        rates.update(contacts_graph=[], contacts_eager=[])
-        touched(20, True)
-        touched(20, False)
-    traced = (lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
+        add("cmd", lambda steps, graph: ev.run_command_test(a.cmd_vx, vy=a.cmd_vy, yaw=a.cmd_yaw, num_steps=steps,
+                                                            graph=graph))
+    records = [flag for flag in ("gait", "joints", "contacts") if getattr(a, flag)]  # flag = mode prefix = report key
+    for flag in records:
+        add(flag, lambda steps, graph, flag=flag: ev.run(steps, graph, **{flag: True}))
     if a.trace_depth:  # (the last mode: traces() below reads the last timed run's rings)
-        rates.update(trace_graph=[], trace_eager=[])
-        traced(20, True)
-        traced(20, False)
-    gr = jr = ctr = None
+        add("trace", lambda steps, graph: ev.run(steps, graph, trace_depth=a.trace_depth))
+    for run in runs.values():  # warm both paths (the capture included)
+        run(20, True)
+        run(20, False)
+    last = {}  # mode prefix -> its last report
     for _ in range(a.repeats):
         for mode in rates:
-            graph = mode.endswith("graph")
-            r = (push if mode.startswith("push") else cmd if mode.startswith("cmd") else
-                 traced if mode.startswith("trace") else gaited if mode.startswith("gait") else
-                 jointed if mode.startswith("joints") else touched if mode.startswith("contacts") else
-                 ev.run)(a.steps, graph)
-            gr = r if mode.startswith("gait") else gr
-            jr = r if mode.startswith("joints") else jr
-            ctr = r if mode.startswith("contacts") else ctr
-            assert a.device == "cpu" or r["graph"] == graph
+            prefix, _, how = mode.rpartition("_")
+            r = last[prefix] = runs[prefix](a.steps, how == "graph")
+            assert a.device == "cpu" or r["graph"] == (how == "graph")
             rates[mode].append(r["env_steps_per_s"])
     trace_doc = None
     if a.trace_depth:  # (the last timed run was the traced eager one)
@@ -158,39 +139,26 @@ def main():
                      # count / status / reset flags) in, one 304-byte row and the count out
                      "record_bytes_in_per_step": n * (8 + 69 * 4 + env.num_bodies * 12 + 4 + 1 + 1),
                      "record_bytes_out_per_step": n * (304 + 4)}
-    pr, cr = r if a.push_vel else None, r if a.cmd_vx else None
-    r = ev.run(a.steps) if pr or cr or a.trace_depth or a.gait or a.joints or a.contacts else r
+    pr, cr = last.get("push"), last.get("cmd")
+    r = ev.run(a.steps) if len(runs) > 1 else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
                                for m, v in rates.items()},
            "total": r["total"]}
     if trace_doc:
         doc["flight_recorder"] = trace_doc
-    if gr:
-        n = a.num_envs
-        doc["gait"] = {"total": gr["total"]["gait"],
-                       # what lgx_gait_record moves per step when every env records: the foot and body
-                       # records in and out, per foot its force and three floats of its rigid-body row,
-                       # the status and reset flags
-                       "record_bytes_in_per_step": n * (256 + 48 + 4 * 24 + 2),
-                       "record_bytes_out_per_step": n * (256 + 48)}
-    if jr:
-        n = a.num_envs
-        doc["joints"] = {"total": jr["total"]["joints"],
-                         # what lgx_joint_record moves per step when every env records: the joint and
-                         # body records in and out, per joint its torque, dof_state pair and action,
-                         # the status and reset flags
-                         "record_bytes_in_per_step": n * (768 + 16 + 12 * 16 + 2),
-                         "record_bytes_out_per_step": n * (768 + 16)}
-    if ctr:
-        n, nb = a.num_envs, env.num_bodies
-        doc["contacts"] = {"total": ctr["total"]["contacts"],
-                           # what lgx_contact_record moves per step when every env records: the body and
-                           # env records in and out (the env row's first float4), per body its force and
-                           # position, the status and reset flags; the terrain samples (3 int16 per body,
-                           # 9 more at an onset) come on top on a heightfield
-                           "record_bytes_in_per_step": n * (nb * 48 + 16 + nb * 24 + 2),
-                           "record_bytes_out_per_step": n * (nb * 48 + 16)}
+    n, nb = a.num_envs, env.num_bodies
+    # What lgx_<kind>_record moves per step when every env records, (bytes in, bytes out): the two
+    # records in and out (contacts: the env row's first float4) and, in, the sources and the status
+    # and reset flags. gait: per foot its force and three floats of its rigid-body row; joints: per
+    # joint its torque, dof_state pair and action; contacts: per body its force and position (the
+    # terrain samples, 3 int16 per body and 9 more at an onset, come on top on a heightfield).
+    record_bytes = {"gait": (n * (256 + 48 + 4 * 24 + 2), n * (256 + 48)),
+                    "joints": (n * (768 + 16 + 12 * 16 + 2), n * (768 + 16)),
+                    "contacts": (n * (nb * 48 + 16 + nb * 24 + 2), n * (nb * 48 + 16))}
+    for flag in records:
+        doc[flag] = {"total": last[flag]["total"][flag], "record_bytes_in_per_step": record_bytes[flag][0],
+                     "record_bytes_out_per_step": record_bytes[flag][1]}
     if pr:
         doc["push_test"] = {k: pr[k] for k in ("speeds", "directions_deg", "push_step", "settle_tol", "total")}
         doc["push_test"]["per_speed"] = [
