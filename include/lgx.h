@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 14
+#define LGX_ABI_VERSION 15
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -48,6 +48,7 @@ extern "C" {
 #define LGX_EVAL_METRICS 8        /* per-env record columns (lgx_eval_buffers.acc) */
 #define LGX_EVAL_CELL_COLS 12     /* per-cell output columns (lgx_eval_buffers.cells) */
 #define LGX_MAX_ACTION_HISTORY 4  /* control steps of actuation latency (action_history rows) */
+#define LGX_MAX_SENSOR_HISTORY 4  /* control steps of sensing latency (sensor_history rows) */
 #define LGX_EVAL_PUSH_REC 4       /* per-env push-recovery record columns (lgx_eval_buffers.push_rec) */
 #define LGX_EVAL_PUSH_COLS 5      /* per-cell push-recovery columns (lgx_eval_buffers.push_cells) */
 #define LGX_CMD_SEGMENTS 4        /* segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val) */
@@ -248,6 +249,9 @@ typedef struct lgx_task_params {
   /* actuation latency (ABI v8): H, the rows of lgx_buffers.action_history = the largest latency
      in control steps; 0 = no latency support. lgx_create refuses H > LGX_MAX_ACTION_HISTORY. */
   int32_t action_history_len;
+  /* sensing latency (ABI v15): K, the rows of lgx_buffers.sensor_history = the largest sensing
+     latency in control steps; 0 = no latency support. lgx_create refuses K > LGX_MAX_SENSOR_HISTORY. */
+  int32_t sensor_history_len;
 } lgx_task_params;
 
 /* Every per-env buffer the step reads/writes. NULL = not present. */
@@ -388,6 +392,41 @@ typedef struct lgx_buffers {
      The step reads both buffers at kernel time: writing them between steps needs no re-bind. */
   const int32_t* cmd_step;     /* [N,LGX_CMD_SEGMENTS] first episode step of each segment; < 0: unused */
   const float* cmd_val;        /* [N,LGX_CMD_SEGMENTS,4] the segment's commands (vx, vy, yaw rate, heading) */
+  /* Sensor model (ABI v15; the reference has one global add_noise / noise_vec and nothing else).
+     All five optional; all NULL = the step of ABI 14, bit for bit. The model acts on the current
+     observation row only (P = num_proprio channels), where compute_observations forms it.
+     raw[i]: the value of channel i before the noise term. A sensor channel is a measured one:
+       Go2:    i < 5 (angular velocity, roll, pitch) and 8 <= i < 8 + 2D (joint positions, velocities);
+       LEGGED: i < 9 (linear, angular velocity, gravity), 12 <= i < 12 + 2D, and i >= 12 + 2D + A (heights).
+     Commands, last actions and the gait clock are not sensor channels.
+     Latency: K = params.sensor_history_len, c = sensor_count[e], d = min(clamp(obs_delay[e], 0, K), c)
+     (the step never indexes with an unclamped value). A sensor channel with d > 0 uses
+     sensor_history[e][(c - d) % K][i], the raw value of d steps ago in the same episode; every
+     other channel, and every channel when d = 0, uses raw[i].
+     Ring write: after that read the step writes all P values of raw to row c % K and sets
+     sensor_count[e] = c + 1 (one lane reads and then overwrites its own column, so d = K needs no
+     (K+1)-th row). Only the sensor columns of the ring are ever read; its other columns are
+     unspecified (lgx_command_curriculum rewrites the command slots of obs, critic and obs_history,
+     not those of the ring). An in-step reset, a NaN-guard reset and lgx_reset_envs set sensor_count[e] = 0;
+     the observation a resetting step forms afterwards is undelayed and becomes row 0 of the new
+     episode, so a delayed read never crosses a reset (and does not depend on episode_length).
+     Noise: the term exists iff params.add_noise; with obs_noise_scale bound its amplitude is
+     noise_vec[i] * obs_noise_scale[e] (one rounding). A scale of 1 gives the bits of the unbound
+     step, a scale of exactly 0 skips the term (the bits of add_noise = 0).
+     Bias: obs_bias[e][i] is added after the noise term as a rounding of its own, on whatever
+     channel the caller put it; an entry that is exactly 0 adds nothing (the value keeps its bits).
+     Order: delayed raw, then noise, then bias; the result is the current row, from which the
+     history, the clip, obs and the Go2 critic's copy follow unchanged. priv, est, scan and the
+     rewards are untouched. lgx_command_curriculum's rewrite of the command slots applies scale and
+     bias (commands are no sensor channels: no latency).
+     lgx_bind refuses obs_delay without sensor_history / sensor_count or with K = 0, sensor_history
+     without sensor_count and the reverse, and sensor_history with K = 0. The step reads the three
+     inputs at kernel time: writing them between steps needs no re-bind. */
+  const float* obs_noise_scale; /* [N]     multiplies the env's observation-noise amplitude            */
+  const float* obs_bias;        /* [N,P]   constant offset per env and proprio channel, P = num_proprio */
+  const int32_t* obs_delay;     /* [N]     sensing latency of env e in control steps                    */
+  float* sensor_history;        /* [N,K,P] state: the last K raw proprio rows of the current episode    */
+  int32_t* sensor_count;        /* [N]     state: raw rows written since env e's last reset             */
 } lgx_buffers;
 
 typedef struct lgx_env lgx_env;

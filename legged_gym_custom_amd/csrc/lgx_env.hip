@@ -1527,7 +1527,9 @@ LGX_DEV void get_heights(const lgx_task_params* Pm, const lgx_buffers& B, Sh& s,
 // and 2b' + 1 of the XCD-aware pair order b' = env_of_block). Each env has its own Sh and LDS arena.
 // Two envs per wave: LDS holds 2 x (Sh + arena) per block, so 8 blocks per CU (2 waves per
 // SIMD) are resident — the register budget is that of 2 waves per SIMD.
-template <bool PHYSICS, bool TERRAIN, bool ACTNET, int EPW>
+// SENSOR: the instances with the sensor model (include/lgx.h, ABI 15), launched when one of its
+// buffers is bound; the others hold none of its code.
+template <bool PHYSICS, bool TERRAIN, bool ACTNET, int EPW, bool SENSOR>
 __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) void env_step_kernel(const lgx_model* __restrict__ M,
                                                       const lgx_task_params* __restrict__ Pm,
                                                       const lgx_buffers* __restrict__ Bp, uint64_t seed,
@@ -1880,8 +1882,40 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
       else if (i < 12 + 2 * D + A) v = s.act[i - 12 - 2 * D];
       else v = clipf(s.root[2] - 0.5f - stg_heights(AR, Pm)[i - (12 + 2 * D + A)], -1.0f, 1.0f) * Pm->obs_scale_height;
     }
-    if (Pm->add_noise) v = v + (2.0f * stg_U(AR)[S_NOISE + i] - 1.0f) * Pm->noise_vec[i];
+    // (the SENSOR instances stage the raw row here and form the modelled one in the pass below)
+    if constexpr (!SENSOR)
+      if (Pm->add_noise) v = v + obs_noise_term(stg_U(AR)[S_NOISE + i], Pm->noise_vec[i]);
     stg_cur(AR, Pm)[i] = v;
+  }
+  // Sensor model (include/lgx.h, ABI 15), in the SENSOR instances only: latency on the sensor
+  // channels through the env's ring in global memory, then the noise term with the env's scale,
+  // then the env's bias. Lane i re-reads the raw value it staged (its own LDS word: no barrier),
+  // reads and then overwrites column i of the ring, consecutive lanes on consecutive words of a
+  // row. No LDS beyond the staged row. Count and latency are per env: every lane of the env loads
+  // the same word (a vector load; at two envs per wave uniform over a half-wave only). An env this
+  // step reset starts at count 0, so its latency clamps to 0 and the count needs no zeroing here.
+  if constexpr (SENSOR) {
+    // rows of this episode in the ring (0 for an env this step reset) and the env's clamped latency
+    int sens_c = 0, sens_d = 0;
+    if (B.sensor_count) {
+      sens_c = reset ? 0 : B.sensor_count[e];
+      if (B.obs_delay) sens_d = sensor_delay_clamp(B.obs_delay[e], Pm->sensor_history_len, sens_c);
+    }
+    for (int i = lane; i < Pp; i += WL) {
+      float v = stg_cur(AR, Pm)[i];
+      if (B.sensor_history) {
+        const int SK = Pm->sensor_history_len;
+        float* ring = B.sensor_history + (size_t)e * SK * Pp;
+        const float raw = v;
+        if (sens_d > 0 && sensor_channel(go2, i, D, A)) v = ring[(size_t)sensor_ring_read_row(sens_c, sens_d, SK) * Pp + i];
+        ring[(size_t)sensor_ring_write_row(sens_c, SK) * Pp + i] = raw;
+      }
+      v = sensor_noise_bias(v, Pm->add_noise != 0, Pm->add_noise ? stg_U(AR)[S_NOISE + i] : 0.f, Pm->noise_vec[i],
+                            B.obs_noise_scale ? B.obs_noise_scale + e : nullptr,
+                            B.obs_bias ? B.obs_bias + (size_t)e * Pp + i : nullptr);
+      stg_cur(AR, Pm)[i] = v;
+    }
+    if (B.sensor_count && lane == 0) B.sensor_count[e] = sens_c + 1;
   }
   // stage the old history (obs[0:H*P]) in LDS; a reset env's history was zeroed (go2.py:238)
   float* hist_g = B.obs_history + (size_t)e * H * Pp;
@@ -2027,6 +2061,7 @@ __global__ __launch_bounds__(64) void reset_kernel(const lgx_task_params* __rest
   // an external reset (BaseTask.reset -> reset_idx) only exists once the env is built,
   // i.e. with init_done set: the terrain curriculum applies (legged_robot.py:551-552)
   reset_env<64>(Pm, B, s, lgx_dyn, e, lane, true, true, false);
+  if (B.sensor_count && lane == 0) B.sensor_count[e] = 0;  // sensor model (ABI 15): the new episode's ring is empty
   if (lane < 13) B.root_states[(size_t)e * 13 + lane] = s.root[lane];
   if (lane < D) {
     B.dof_state[((size_t)e * D + lane) * 2] = s.th[lane];
@@ -2102,6 +2137,8 @@ int lgx_create(const lgx_model* model, const lgx_task_params* params, int32_t de
   if (params->num_reward_terms + 1 > 64) return fail(env, "too many reward terms");
   if (params->action_history_len < 0 || params->action_history_len > LGX_MAX_ACTION_HISTORY)
     return fail(env, "action_history_len outside 0..LGX_MAX_ACTION_HISTORY");
+  if (params->sensor_history_len < 0 || params->sensor_history_len > LGX_MAX_SENSOR_HISTORY)
+    return fail(env, "sensor_history_len outside 0..LGX_MAX_SENSOR_HISTORY");
   // observation layout the step writes (go2.py:467-574 / legged_robot.py:240-273): obs =
   // [history (H x P) | current (P)]; Go2 critic = [obs | priv | est (3) | scan]. A config whose
   // declared sizes disagree (the reference's anymal_c_flat: 48-wide obs, 235-wide proprio)
@@ -2171,6 +2208,12 @@ int lgx_bind(lgx_env* env, const lgx_buffers* b) {
     return fail(env, "lgx_bind: action_delay needs action_history and params.action_history_len > 0");
   if (b->action_history && env->params.action_history_len <= 0)
     return fail(env, "lgx_bind: action_history with params.action_history_len = 0");
+  if (b->obs_delay && (!b->sensor_history || !b->sensor_count || env->params.sensor_history_len <= 0))
+    return fail(env, "lgx_bind: obs_delay needs sensor_history, sensor_count and params.sensor_history_len > 0");
+  if (b->sensor_history && !b->sensor_count) return fail(env, "lgx_bind: sensor_history needs sensor_count");
+  if (b->sensor_count && !b->sensor_history) return fail(env, "lgx_bind: sensor_count needs sensor_history");
+  if (b->sensor_history && env->params.sensor_history_len <= 0)
+    return fail(env, "lgx_bind: sensor_history with params.sensor_history_len = 0");
   if (b->push_step && !b->push_dvel) return fail(env, "lgx_bind: push_step without push_dvel");
   if (b->push_dvel && !b->push_step) return fail(env, "lgx_bind: push_dvel without push_step");
   if (b->cmd_step && !b->cmd_val) return fail(env, "lgx_bind: cmd_step without cmd_val");
@@ -2220,12 +2263,21 @@ static int launch_step(lgx_env* env, uint64_t seed, uint64_t step, const uint64_
   }();
   const int want = env->epw ? env->epw : (terrain ? 1 : epw_env);
   const int epw = (!actnet && N % 2 == 0 && want == 2) ? 2 : 1;
-  auto kern = epw == 2 ? (!physics ? lgx::env_step_kernel<false, false, false, 2>
-                                   : (terrain ? lgx::env_step_kernel<true, true, false, 2>
-                                              : lgx::env_step_kernel<true, false, false, 2>))
-            : !physics ? lgx::env_step_kernel<false, false, false, 1>
-            : actnet   ? (terrain ? lgx::env_step_kernel<true, true, true, 1> : lgx::env_step_kernel<true, false, true, 1>)
-                       : (terrain ? lgx::env_step_kernel<true, true, false, 1> : lgx::env_step_kernel<true, false, false, 1>);
+  // the sensor model's code lives in instances of its own (SENSOR), chosen from the bound pointers:
+  // with none of them bound the step runs the code it ran before ABI 15
+  const lgx_buffers& hb = env->buffers;
+  const bool sensor = hb.obs_noise_scale || hb.obs_bias || hb.sensor_history;
+#define LGX_STEP_KERNEL(SENSOR)                                                                              \
+  (epw == 2 ? (!physics ? lgx::env_step_kernel<false, false, false, 2, SENSOR>                               \
+                        : (terrain ? lgx::env_step_kernel<true, true, false, 2, SENSOR>                      \
+                                   : lgx::env_step_kernel<true, false, false, 2, SENSOR>))                   \
+   : !physics ? lgx::env_step_kernel<false, false, false, 1, SENSOR>                                         \
+   : actnet   ? (terrain ? lgx::env_step_kernel<true, true, true, 1, SENSOR>                                 \
+                         : lgx::env_step_kernel<true, false, true, 1, SENSOR>)                               \
+              : (terrain ? lgx::env_step_kernel<true, true, false, 1, SENSOR>                                \
+                         : lgx::env_step_kernel<true, false, false, 1, SENSOR>))
+  auto kern = sensor ? LGX_STEP_KERNEL(true) : LGX_STEP_KERNEL(false);
+#undef LGX_STEP_KERNEL
   const size_t dyn = sizeof(float) * (size_t)lgx::arena_floats(env->params) * epw;
   hipLaunchKernelGGL(kern, dim3(N / epw), dim3(64), dyn, st, env->d_model, env->d_params, env->d_buffers, seed, step,
                      step_dev);

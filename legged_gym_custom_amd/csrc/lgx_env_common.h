@@ -603,6 +603,45 @@ LGX_HD void contact_env_terminal(float* v, const contact_part& p) {
   v[3] = (float)p.term;
 }
 
+// Sensor model (lgx_buffers.obs_noise_scale .. sensor_count, include/lgx.h, ABI 15).
+// A sensor channel of the proprio row is a measured one: Go2 angular velocity, roll, pitch and the
+// joint positions / velocities; LEGGED linear and angular velocity, gravity, joint positions /
+// velocities and the heights. Commands, last actions and the gait clock are not.
+LGX_HD bool sensor_channel(bool go2, int i, int D, int A) {
+  if (go2) return i < 5 || (i >= 8 && i < 8 + 2 * D);
+  return i < 9 || (i >= 12 && i < 12 + 2 * D) || i >= 12 + 2 * D + A;
+}
+// The sensing latency an env has in this step: obs_delay clamped into [0, K] and to the c rows its
+// episode has written so far, so a delayed read never crosses a reset.
+LGX_HD int sensor_delay_clamp(int d, int K, int c) {
+  d = d < 0 ? 0 : (d > K ? K : d);
+  return d < c ? d : c;
+}
+// Ring rows for K in 1..LGX_MAX_SENSOR_HISTORY: this step's raw row goes to c % K, the raw row of
+// d steps ago (0 < d <= min(K, c)) is read from (c - d) % K. With d = K both are the same row: the
+// caller reads before it writes.
+LGX_HD int sensor_ring_write_row(int c, int K) { return (int)((unsigned)c % (unsigned)K); }
+LGX_HD int sensor_ring_read_row(int c, int d, int K) { return (int)((unsigned)(c - d) % (unsigned)K); }
+// The observation-noise term of one channel: u the channel's uniform, amp its amplitude (noise_vec[i],
+// times the env's scale in the sensor model). Every site that forms the term calls this.
+LGX_HD float obs_noise_term(float u, float amp) { return (2.0f * u - 1.0f) * amp; }
+// The noise term and the bias on channel value v (the delayed raw value on a delayed sensor
+// channel), in this order, each a rounding of its own. u: the channel's uniform, nv: noise_vec[i],
+// scale: &obs_noise_scale[e] or NULL, bias: &obs_bias[e][i] or NULL. Unbound, scale 1 and bias 0
+// give the bits of `v + (2u - 1) * nv`; a scale of exactly 0 those of add_noise = 0.
+LGX_HD float sensor_noise_bias(float v, bool add_noise, float u, float nv, const float* scale, const float* bias) {
+  if (add_noise) {
+    const float sc = scale ? *scale : 1.0f;
+    if (!scale) v = v + obs_noise_term(u, nv);
+    else if (sc != 0.0f) v = v + obs_noise_term(u, nv * sc);
+  }
+  if (bias) {
+    const float b = *bias;
+    if (b != 0.0f) v = v + b;
+  }
+  return v;
+}
+
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).
 LGX_HD float step_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
   uint32_t o[4];
@@ -887,7 +926,10 @@ LGX_HD void curriculum_rewrite_env(const lgx_task_params* Pm, const lgx_buffers&
   for (int j = 0; j < 3; ++j) {
     const int i = c0 + j;
     float v = cmd[j] * Pm->commands_scale[j];
-    if (Pm->add_noise) v = v + (2.0f * step_uniform(seed, gid, step, S_NOISE + i) - 1.0f) * Pm->noise_vec[i];
+    // the sensor model's noise scale and bias (ABI 15; commands are no sensor channels: no latency)
+    v = sensor_noise_bias(v, Pm->add_noise != 0, Pm->add_noise ? step_uniform(seed, gid, step, S_NOISE + i) : 0.f,
+                          Pm->noise_vec[i], B.obs_noise_scale ? B.obs_noise_scale + e : nullptr,
+                          B.obs_bias ? B.obs_bias + (size_t)e * Pp + i : nullptr);
     const float vc = clipf(v, -co, co);
     obs[H * Pp + i] = vc;
     if (cr) cr[H * Pp + i] = vc;

@@ -584,6 +584,7 @@ static void reset_env(const lgx_task_params* P, const lgx_buffers* B, Env& s, in
     memset(B->last_actions + (size_t)e * A, 0, sizeof(float) * A);
     if (B->action_history)
       memset(B->action_history + (size_t)e * P->action_history_len * A, 0, sizeof(float) * P->action_history_len * A);
+    if (B->sensor_count) B->sensor_count[e] = 0;  // sensor model (ABI 15)
     memset(B->last_dof_vel + (size_t)e * D, 0, sizeof(float) * D);
     memset(B->last_torques + (size_t)e * D, 0, sizeof(float) * D);
     memset(B->last_root_vel + (size_t)e * 6, 0, sizeof(float) * 6);
@@ -875,6 +876,11 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     for (int i = 0; i < P->num_height_points; ++i) outl += fabsf(s.heights[i]) > 0.1f;
     s.x.jump = (float)(outl >= 8);
   }
+  int sens_c = 0, sens_d = 0;  // sensor model: this episode's rows in the ring, the clamped latency
+  if (B->sensor_count) {
+    sens_c = reset ? 0 : B->sensor_count[e];
+    if (B->obs_delay) sens_d = sensor_delay_clamp(B->obs_delay[e], P->sensor_history_len, sens_c);
+  }
   for (int i = 0; i < Pp; ++i) {
     float v;
     if (go2) {
@@ -901,9 +907,20 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
       else if (i < 12 + 2 * D + A) v = s.act[i - 12 - 2 * D];
       else v = clipf(s.root[2] - 0.5f - s.heights[i - (12 + 2 * D + A)], -1.0f, 1.0f) * P->obs_scale_height;
     }
-    if (P->add_noise) v = v + (2.0f * s.U[S_NOISE + i] - 1.0f) * P->noise_vec[i];
+    // sensor model (include/lgx.h, ABI 15): the kernel's rule
+    if (B->sensor_history) {
+      const int SK = P->sensor_history_len;
+      float* ring = B->sensor_history + (size_t)e * SK * Pp;
+      const float raw = v;
+      if (sens_d > 0 && sensor_channel(go2, i, D, A)) v = ring[(size_t)sensor_ring_read_row(sens_c, sens_d, SK) * Pp + i];
+      ring[(size_t)sensor_ring_write_row(sens_c, SK) * Pp + i] = raw;
+    }
+    v = sensor_noise_bias(v, P->add_noise != 0, P->add_noise ? s.U[S_NOISE + i] : 0.f, P->noise_vec[i],
+                          B->obs_noise_scale ? B->obs_noise_scale + e : nullptr,
+                          B->obs_bias ? B->obs_bias + (size_t)e * Pp + i : nullptr);
     s.cur[i] = v;
   }
+  if (B->sensor_count) B->sensor_count[e] = sens_c + 1;
   float* hist_g = B->obs_history + (size_t)e * H * Pp;
   for (int i = 0; i < H * Pp; ++i) s.hist[i] = reset ? 0.f : hist_g[i];  // go2.py:238
   const float co = P->clip_obs;

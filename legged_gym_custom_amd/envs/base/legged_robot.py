@@ -230,6 +230,32 @@ class LeggedRobot(BaseTask):
         return self._reduced_cells("lgx_eval_reduce", self._cmd_eval, self._cmd_eval_overflow, "a cell id",
                                    self._cmd_eval_cells, self._cmd_cells)
 
+    def sensor_eval_buffers(self, rows, cols):
+        """A set of evaluation tensors of its own for the sensor test (lgx_eval_buffers with the free
+        cell key cell_ids and the plain record, no per-env record of its own), allocated once per
+        (rows, cols) so a captured loop replays on fixed addresses: sensor_cell_ids [N] int32 (the
+        caller writes each env's bin in place), sensor_eval_acc [N, 8], sensor_eval_status [N] and,
+        after eval_sensor_cells, cells [rows, cols, 12]. Pass the result as `ev` to eval_begin /
+        eval_accumulate."""
+        key = (int(rows), int(cols))
+        if getattr(self, "_sensor_eval_key", None) != key:
+            z, n = self._zeros, self.num_envs
+            self.sensor_eval_acc, self.sensor_eval_status = z(n, _abi.EVAL_METRICS), z(n, dtype=torch.uint8)
+            self.sensor_cell_ids = z(n, dtype=torch.int32)
+            self._sensor_eval_cells = z(*key, _abi.EVAL_CELL_COLS, dtype=torch.float64)
+            self._sensor_eval_overflow = z(1, dtype=torch.int32)
+            self._sensor_eval = self._native.eval_buffers(self.sensor_eval_acc, self.sensor_eval_status,
+                                                          self._sensor_eval_cells, self._sensor_eval_overflow,
+                                                          cell_ids=self.sensor_cell_ids)
+            self._sensor_eval_key = key
+        return self._sensor_eval
+
+    def eval_sensor_cells(self):
+        """lgx_eval_reduce on the sensor test's buffers, then the cells [rows, cols, 12] float64 on
+        the host. Synchronises. A cell id outside the grid is an error."""
+        return self._reduced_cells("lgx_eval_reduce", self._sensor_eval, self._sensor_eval_overflow, "a cell id",
+                                   self._sensor_eval_cells)[0]
+
     def eval_cells(self):
         """lgx_eval_reduce, then the cells [rows, cols, 12] float64 on the host: n_envs, n_timeout,
         n_fall, n_blowup and the sums of the 8 record columns over each cell's finished envs.
@@ -636,6 +662,7 @@ class LeggedRobot(BaseTask):
         if not getattr(dr, "randomize_kp_kd", False):
             self.kp_kd_multipliers.fill_(1.0)
         self._init_actuator_randomisation()  # after every existing setup draw: those keep their values
+        self._init_sensor_model()  # after the actuator draws
         self.push_step = self.push_dvel = None  # scheduled pushes (ABI 9): no draw, off unless allocated
         if prm.scheduled_pushes(self.cfg):
             self._alloc_push_schedule()
@@ -723,6 +750,8 @@ class LeggedRobot(BaseTask):
             "motor_strength": self.motor_strengths,
             "push_step": self.push_step, "push_dvel": self.push_dvel,
             "cmd_step": self.cmd_step, "cmd_val": self.cmd_val,
+            "obs_noise_scale": self.obs_noise_scales, "obs_bias": self.obs_biases, "obs_delay": self.obs_delay_steps,
+            "sensor_history": self.sensor_history, "sensor_count": self.sensor_count,
             **self._sea_buffers,
         })
 
@@ -793,6 +822,128 @@ class LeggedRobot(BaseTask):
             self.motor_strengths = torch.ones(self.num_envs, self.num_dof, device=self.device)
             self._bind()
         self.motor_strengths.copy_(v.expand(self.num_envs, self.num_dof))
+
+    # ------------------------------------------------------------------ sensor model
+    def _init_sensor_model(self):
+        """Per-env observation noise level, bias and sensing latency (include/lgx.h ABI 15;
+        domain_rand keys of params.sensor_model). obs_delay_steps, sensor_history and sensor_count
+        exist, and are bound, when max_obs_delay_s gives K > 0 control steps; obs_noise_scales and
+        obs_biases when their randomisation or domain_rand.sensor_model is on (or after their
+        setter's first call). Otherwise the attributes are None and the step is that of ABI 14.
+        Draws only for an enabled feature, after the actuator draws, for all global envs and
+        sliced by rank, fixed per env: one scale U(lo, hi), one offset per sensor channel uniform in
+        +-level * sensor_amplitudes with level U(lo, hi) per env, one latency round(U(lo, hi) / dt)."""
+        n, p, dev = self.num_envs, int(self.cfg.env.num_proprio), self.device
+        total, sl = self.num_envs_total, slice(self.env_id_offset, self.env_id_offset + self.num_envs)
+        sm = prm.sensor_model(self.cfg, self.dt)
+        go2 = self.TASK_KIND == _abi.TASK_GO2
+        self._sensor_history_len = K = sm["history_len"]
+        self._obs_groups = prm.proprio_channel_groups(self.cfg, go2)
+        self.sensor_amplitudes = torch.from_numpy(prm.sensor_amplitudes(self.cfg, go2)).to(dev)
+        self.obs_noise_scales = self.obs_biases = self.obs_delay_steps = self.sensor_history = self.sensor_count = None
+        if sm["on"] or sm["scale_on"]:
+            self.obs_noise_scales = torch.ones(n, device=dev)
+        if sm["on"] or sm["bias_on"]:
+            self.obs_biases = torch.zeros(n, p, device=dev)
+        if K > 0:
+            self.obs_delay_steps = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.sensor_history = torch.zeros(n, K, p, device=dev)
+            self.sensor_count = torch.zeros(n, dtype=torch.int32, device=dev)
+        if sm["scale_on"]:
+            lo, hi = sm["scale_range"]
+            self.set_obs_noise_scale(((hi - lo) * torch.rand(total, device=dev) + lo)[sl])
+        if sm["bias_on"]:
+            lo, hi = sm["bias_level_range"]
+            level = (hi - lo) * torch.rand(total, 1, device=dev) + lo
+            r = 2.0 * torch.rand(total, p, device=dev) - 1.0
+            self.set_obs_bias((level * r * self.sensor_amplitudes)[sl])
+        if sm["delay_on"] and K > 0:  # (a range of [0, 0] s needs no ring: nothing to draw)
+            lo, hi = sm["delay_range_s"]
+            self.set_obs_delay(((hi - lo) * torch.rand(total, device=dev) + lo)[sl])
+
+    def _sensor_alloc(self, name, what, make):
+        """The first call of a sensor setter on an env built without its buffer: allocate, re-bind."""
+        if self._captured:
+            raise RuntimeError(f"{what}: this env has no {name} buffer and its step has been captured in a graph, "
+                               "which would go on replaying the old binding; build the env with "
+                               f"domain_rand.sensor_model or call {what} before the capture")
+        setattr(self, name, make())
+        self._bind()
+
+    def set_obs_noise_scale(self, value):
+        """Observation-noise level of every env: a number or a tensor [num_envs] that multiplies the
+        config's noise amplitude (noise.add_noise decides whether there is noise at all). Written in
+        place once the buffer exists; the first call on an env built without it allocates and
+        re-binds: RuntimeError once a step of this env has been captured. ValueError when negative
+        or not finite."""
+        v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        if v.dim() not in (0, 1) or (v.dim() == 1 and v.shape[0] != self.num_envs):
+            raise ValueError(f"obs noise scale: a number or a tensor [{self.num_envs}], got shape {list(v.shape)}")
+        if not bool(torch.isfinite(v).all()) or float(v.min()) < 0.0:
+            raise ValueError("obs noise scales must be finite and >= 0")
+        if self.obs_noise_scales is None:
+            self._sensor_alloc("obs_noise_scales", "set_obs_noise_scale", lambda: torch.ones(self.num_envs, device=self.device))
+        self.obs_noise_scales.copy_(v.expand(self.num_envs))
+
+    def set_obs_bias(self, bias):
+        """Constant observation offsets in observation units: a tensor [num_proprio] or
+        [num_envs, num_proprio] (obs_bias_from_physical builds one from physical units). Written in
+        place once the buffer exists; the first call on an env built without it allocates and
+        re-binds: RuntimeError once a step of this env has been captured. ValueError for a wrong
+        shape or a non-finite entry."""
+        n, p = self.num_envs, int(self.cfg.env.num_proprio)
+        b = torch.as_tensor(bias, dtype=torch.float32, device=self.device)
+        if tuple(b.shape) not in ((p,), (n, p)):
+            raise ValueError(f"obs bias: a tensor [{p}] or [{n}, {p}], got shape {list(b.shape)}")
+        if not bool(torch.isfinite(b).all()):
+            raise ValueError("obs bias must be finite")
+        if self.obs_biases is None:
+            self._sensor_alloc("obs_biases", "set_obs_bias", lambda: torch.zeros(n, p, device=self.device))
+        self.obs_biases.copy_(b.expand(n, p))
+
+    def set_obs_delay(self, seconds):
+        """Sensing latency of every env: a number of seconds or a tensor [num_envs] of seconds, rounded
+        to control steps (round(s / dt)). Written in place (a captured graph keeps replaying on the
+        same address). ValueError when negative, or beyond the capacity the env was built with
+        (domain_rand.max_obs_delay_s)."""
+        if self.obs_delay_steps is None:
+            raise ValueError("this env was built without sensing latency support: set "
+                             "domain_rand.max_obs_delay_s (or randomize_obs_delay) in its config")
+        s = torch.as_tensor(seconds, dtype=torch.float64, device=self.device)
+        if s.dim() not in (0, 1) or (s.dim() == 1 and s.shape[0] != self.num_envs):
+            raise ValueError(f"obs delay: a number or a tensor [{self.num_envs}], got shape {list(s.shape)}")
+        st = torch.round(s / float(self.dt))
+        lo, hi = float(st.min()), float(st.max())
+        if not (lo >= 0.0 and hi <= self._sensor_history_len):  # also refuses NaN
+            raise ValueError(f"obs delay of {lo:g}..{hi:g} control steps is outside 0..{self._sensor_history_len} "
+                             "(capacity: domain_rand.max_obs_delay_s)")
+        self.obs_delay_steps.copy_(st.to(torch.int32).expand(self.num_envs))
+
+    def obs_channel_groups(self):
+        """name -> slice of the current-observation (proprio) row, from the task's layout
+        (params.go2_proprio_layout / legged_proprio_layout)."""
+        return dict(self._obs_groups)
+
+    def obs_bias_from_physical(self, **groups):
+        """[num_envs, num_proprio] in observation units from physical offsets per sensor group
+        (ang_vel, roll_pitch, gravity, lin_vel, dof_pos, dof_vel, heights; those the task has): each a
+        number, a tensor [width] or [num_envs, width], times the group's observation scale.
+        ValueError for a group the task does not measure, a wrong shape or a non-finite entry."""
+        n, p = self.num_envs, int(self.cfg.env.num_proprio)
+        out = torch.zeros(n, p, device=self.device)
+        for name, value in groups.items():
+            if name not in prm.SENSOR_GROUPS or name not in self._obs_groups:
+                known = [g for g in self._obs_groups if g in prm.SENSOR_GROUPS]
+                raise ValueError(f"obs bias: '{name}' is not a sensor group of this task (it has {known})")
+            sl = self._obs_groups[name]
+            w = sl.stop - sl.start
+            v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+            if tuple(v.shape) not in ((), (w,), (n, w)):
+                raise ValueError(f"obs bias {name}: a number or a tensor [{w}] or [{n}, {w}], got shape {list(v.shape)}")
+            if not bool(torch.isfinite(v).all()):
+                raise ValueError(f"obs bias {name} must be finite")
+            out[:, sl] = v * prm.sensor_obs_scale(self.cfg, name)
+        return out
 
     # ------------------------------------------------------------------ scheduled pushes
     def _alloc_push_schedule(self):

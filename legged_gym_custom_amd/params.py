@@ -53,6 +53,91 @@ def go2_proprio_layout(num_dof=12):
 GO2_PHASE_LEGS = ("fr", "fl", "bl", "br")
 
 
+def legged_proprio_layout(num_dof=12, num_actions=12, num_heights=0):
+    """The LEGGED current-observation vector (legged_robot.py:240-273) as ordered (field, width)
+    slots, the order the env kernel writes; heights: the measured-height channels (0 without them)."""
+    return (("lin_vel", 3), ("ang_vel", 3), ("gravity", 3), ("command", 3), ("dof_pos", num_dof),
+            ("dof_vel", num_dof), ("actions", num_actions), ("heights", num_heights))
+
+
+# The measured groups of a proprio row (the sensor channels of include/lgx.h, ABI 15) -> the
+# noise_scales key and the obs_scales key (None: scale 1) of the group.
+SENSOR_GROUPS = {"lin_vel": ("lin_vel", "lin_vel"), "ang_vel": ("ang_vel", "ang_vel"), "roll_pitch": ("imu", None),
+                 "gravity": ("gravity", None), "dof_pos": ("dof_pos", "dof_pos"), "dof_vel": ("dof_vel", "dof_vel"),
+                 "heights": ("height_measurements", "height_measurements")}
+
+
+def proprio_layout(cfg, go2):
+    """The task's layout function applied to its config."""
+    D, A = cfg.env.num_actions, cfg.env.num_actions
+    if go2:
+        return go2_proprio_layout(D)
+    return legged_proprio_layout(D, A, max(int(cfg.env.num_proprio) - (12 + 2 * D + A), 0))
+
+
+def proprio_channel_groups(cfg, go2):
+    """name -> slice of the proprio row, from the layout (not from noise_vector: the Go2 noise
+    slots are shifted by one, go2.py:120-127)."""
+    out, at = {}, 0
+    for name, width in proprio_layout(cfg, go2):
+        if width > 0:
+            out[name] = slice(at, at + width)
+        at += width
+    return out
+
+
+def sensor_obs_scale(cfg, group):
+    """The observation scale of a sensor group (physical unit -> observation unit)."""
+    key = SENSOR_GROUPS[group][1]
+    return 1.0 if key is None else float(getattr(cfg.normalization.obs_scales, key))
+
+
+def sensor_amplitudes(cfg, go2):
+    """[num_proprio] float32: on each sensor channel the amplitude the config's own noise has for
+    its group, noise_level * noise_scales.<group> * obs scale, placed by the layout; 0 elsewhere."""
+    v = np.zeros(cfg.env.num_proprio, dtype=np.float32)
+    ns, lvl = cfg.noise.noise_scales, cfg.noise.noise_level
+    for name, sl in proprio_channel_groups(cfg, go2).items():
+        if name in SENSOR_GROUPS:
+            v[sl] = float(getattr(ns, SENSOR_GROUPS[name][0])) * lvl * sensor_obs_scale(cfg, name)
+    return v
+
+
+def sensor_model(cfg, dt):
+    """The sensor-model keys of cfg.domain_rand (all optional, read with getattr: the shipped config
+    classes do not carry them) -> dict:
+      on             sensor_model: allocate and bind all five buffers up front, with neutral values
+      scale_on / scale_range   randomize_obs_noise_scale, obs_noise_scale_range
+      bias_on / bias_level_range   randomize_obs_bias, obs_bias_level_range (multiples of sensor_amplitudes)
+      delay_on / delay_range_s / max_delay_s   randomize_obs_delay, obs_delay_range_s, max_obs_delay_s
+                                               (default: the range's upper end)
+      history_len    K = round(max_obs_delay_s / dt) control steps (lgx_task_params.sensor_history_len)
+    A ValueError when K exceeds LGX_MAX_SENSOR_HISTORY or a range is not 0 <= lo <= hi."""
+    dr = cfg.domain_rand
+    delay_on = bool(getattr(dr, "randomize_obs_delay", False))
+    lo, hi = (float(v) for v in getattr(dr, "obs_delay_range_s", [0.0, 0.0]))
+    max_s = float(getattr(dr, "max_obs_delay_s", hi if delay_on else 0.0))
+    if not (0.0 <= lo <= hi) or not max_s >= 0.0:
+        raise ValueError(f"domain_rand.obs_delay_range_s {[lo, hi]} / max_obs_delay_s {max_s}: need 0 <= lo <= hi")
+    K = int(round(max_s / dt))
+    if delay_on and int(round(hi / dt)) > K:
+        raise ValueError(f"domain_rand.obs_delay_range_s upper end {hi} s exceeds max_obs_delay_s {max_s} s")
+    if K > _abi.MAX_SENSOR_HISTORY:
+        raise ValueError(f"domain_rand.max_obs_delay_s = {max_s} s is {K} control steps of sensor history; "
+                         f"at most {_abi.MAX_SENSOR_HISTORY} (LGX_MAX_SENSOR_HISTORY)")
+    scale_on = bool(getattr(dr, "randomize_obs_noise_scale", False))
+    slo, shi = (float(v) for v in getattr(dr, "obs_noise_scale_range", [1.0, 1.0]))
+    if scale_on and not (0.0 <= slo <= shi):
+        raise ValueError(f"domain_rand.obs_noise_scale_range {[slo, shi]}: need 0 <= lo <= hi")
+    bias_on = bool(getattr(dr, "randomize_obs_bias", False))
+    blo, bhi = (float(v) for v in getattr(dr, "obs_bias_level_range", [0.0, 0.0]))
+    if bias_on and not (0.0 <= blo <= bhi):
+        raise ValueError(f"domain_rand.obs_bias_level_range {[blo, bhi]}: need 0 <= lo <= hi")
+    return dict(on=bool(getattr(dr, "sensor_model", False)), scale_on=scale_on, scale_range=[slo, shi],
+                bias_on=bias_on, bias_level_range=[blo, bhi], delay_on=delay_on, delay_range_s=[lo, hi],
+                max_delay_s=max_s, history_len=K)
+
+
 def noise_vector(cfg, go2):
     p = cfg.env.num_proprio
     v = np.zeros(p, dtype=np.float32)
@@ -165,6 +250,7 @@ def build_task_params(cfg, model, num_envs, num_envs_total=None, env_id_offset=0
     dr = cfg.domain_rand
     P.randomize_kp_kd = int(getattr(dr, "randomize_kp_kd", False))
     P.action_history_len = actuator_randomisation(cfg, sdt)["history_len"]
+    P.sensor_history_len = sensor_model(cfg, dt)["history_len"]
     links = model["links"][1:]
     for i, dn in enumerate(model["dof_names"]):
         P.default_dof_pos[i] = cfg.init_state.default_joint_angles[dn]

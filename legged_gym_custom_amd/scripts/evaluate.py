@@ -9,6 +9,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--eval_steps N] [--action_delay_ms a[,b,...]] [--motor_strength x]
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
+         [--obs_noise a[,b,...]] [--obs_bias a[,b,...]] [--obs_delay_ms a[,b,...]]
          [--trace_falls M [--trace_s 2.0]] [--gait] [--joints] [--contacts]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
@@ -26,6 +27,14 @@ scheduled push is the only disturbance.
 --cmd_at_s seconds into its episode to one command of the --cmd_vx x --cmd_vy x --cmd_yaw grid (m/s, m/s, rad/s;
 literal commands, the yaw entry is a yaw rate) and is recorded from the switch on: settle times, peak tilt,
 achieved velocities and gain per bin. The config's random pushes are switched off for this mode; not with --push_vel.
+
+--obs_noise / --obs_bias / --obs_delay_ms: the sensor test (PolicyEvaluator.run_sensor_test); any of the three
+selects it. Every env gets one cell of the noise x bias x latency grid through the step kernel's sensor model:
+--obs_noise in multiples of the config's own observation-noise amplitude (needs noise.add_noise for more than one
+level), --obs_bias in multiples of the same amplitudes as a constant random offset per env and sensor channel,
+--obs_delay_ms as a sensing latency in ms, rounded to control steps. A list that is not given is the neutral one
+(1 / 0 / 0). The env is built with domain_rand.sensor_model = True and the sensor history the largest latency needs;
+the rest of the config stays as trained. Not with --push_vel, --cmd_vx, --action_delay_ms or --motor_strength.
 
 --trace_falls M: the flight recorder (PolicyEvaluator.traces), valid in every mode: the last --trace_s seconds
 of every env's episode are kept in a ring buffer on the device (depth = round(trace_s / dt) steps, clipped to
@@ -62,7 +71,7 @@ or bin with data is printed before the JSON ("contacts <where>: falls 37: base 6
 
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
-eval_<policy>_command.json)."""
+eval_<policy>_command.json; the sensor test: eval_<policy>_sensors.json)."""
 import argparse
 import json
 import os
@@ -83,7 +92,8 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
-             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False, contacts=False):
+             cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False, contacts=False, obs_noise=None,
+             obs_bias=None, obs_delay_ms=None):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -102,6 +112,18 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
             raise ValueError("--cmd_vx is a mode of its own: not with --push_vel / --action_delay_ms / --motor_strength")
         env_cfg.commands.scheduled_commands = True  # the schedule buffers exist before any capture
         env_cfg.domain_rand.push_robots = False     # the command switch is the only disturbance
+    sensors = any(v is not None for v in (obs_noise, obs_bias, obs_delay_ms))
+    if sensors:
+        if push_vel or cmd_vx or delays_s or motor_strength is not None:
+            raise ValueError("--obs_noise / --obs_bias / --obs_delay_ms are a mode of their own: not with --push_vel / "
+                             "--cmd_vx / --action_delay_ms / --motor_strength")
+        obs_delay_s = [float(ms) / 1000.0 for ms in (obs_delay_ms or [0.0])]
+        dr = env_cfg.domain_rand
+        dr.sensor_model = True  # the three buffers exist before any capture
+        from legged_gym_custom_amd import params as prm
+        # the config's own capacity by the env's rule (a range counts only with its randomisation on)
+        own = prm.sensor_model(env_cfg, env_cfg.control.decimation * env_cfg.sim.dt)["max_delay_s"]
+        dr.max_obs_delay_s = max([own] + obs_delay_s)  # the capacity the largest latency needs
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
 
     train_cfg.runner.resume = True
@@ -126,6 +148,10 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
                                                     start=cmd_start or (0.0, 0.0, 0.0), num_steps=eval_steps,
                                                     graph=graph, trace_depth=depth, gait=gait, joints=joints, contacts=contacts))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_command.json")
+    elif sensors:
+        report = dict(**head, **ev.run_sensor_test(obs_noise or (1.0,), obs_bias or (0.0,), obs_delay_s, num_steps=eval_steps,
+                                                   graph=graph, trace_depth=depth, gait=gait, joints=joints, contacts=contacts))
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_sensors.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
                                       trace_depth=depth, gait=gait, joints=joints, contacts=contacts)
@@ -172,6 +198,12 @@ def _each_place(report, line):
             for s, row in enumerate(rep["bins"]):
                 for d, cell in enumerate(row):
                     line(f"{tag}push {rep['speeds'][s]:g} m/s from {rep['directions_deg'][d]:g} deg", cell)
+        elif "delay_steps" in rep:  # the sensor test
+            for i, a in enumerate(rep["bins"]):
+                for j, b in enumerate(a):
+                    for k, cell in enumerate(b):
+                        line(f"{tag}sensors noise {rep['noise'][i]:g} bias {rep['bias'][j]:g} delay "
+                             f"{1000.0 * rep['delay_s'][k]:g} ms", cell)
         elif "vx" in rep:  # the command test
             for ix, a in enumerate(rep["bins"]):
                 for iy, b in enumerate(a):
@@ -236,6 +268,9 @@ def main(argv=None):
     p.add_argument("--cmd_yaw", type=floats, default=None)
     p.add_argument("--cmd_at_s", type=float, default=2.0)
     p.add_argument("--cmd_start", type=floats, default=None)
+    p.add_argument("--obs_noise", type=floats, default=None)
+    p.add_argument("--obs_bias", type=floats, default=None)
+    p.add_argument("--obs_delay_ms", type=floats, default=None)
     p.add_argument("--trace_falls", type=int, default=None)
     p.add_argument("--trace_s", type=float, default=2.0)
     p.add_argument("--gait", action="store_true")
@@ -248,7 +283,8 @@ def main(argv=None):
                          push_vel=own.push_vel, push_dirs=own.push_dirs, push_at_s=own.push_at_s,
                          cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
                          cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s,
-                         gait=own.gait, joints=own.joints, contacts=own.contacts)
+                         gait=own.gait, joints=own.joints, contacts=own.contacts, obs_noise=own.obs_noise,
+                         obs_bias=own.obs_bias, obs_delay_ms=own.obs_delay_ms)
     for ln in (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []) + \
             (contact_summary(report) if own.contacts else []):
         print(ln)

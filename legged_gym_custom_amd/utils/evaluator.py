@@ -29,6 +29,11 @@ episode step, to the command of its bin of a commanded vx x vy x yaw-rate grid t
 kernel's command schedule (lgx_buffers.cmd_step / cmd_val, ABI 10), and a per-env step-response
 record (cmd_rec) is reduced per bin: one run gives the tracking envelope and the step response.
 
+Sensor model (run_sensor_test): every env gets the observation-noise level, the constant sensor
+offset and the sensing latency of its bin of a noise x bias x latency grid through the step
+kernel's sensor model (lgx_buffers.obs_noise_scale / obs_bias / obs_delay, ABI 15); the plain
+record is reduced per bin: one run gives the whole table.
+
 Flight recorder (trace_depth= of the three runs, then traces()): a ring buffer on the device for every
 env holds the last trace_depth control steps of the env's recorded episode (lgx_trace_record after
 each step, include/lgx.h ABI 11: state, commands, joints, torques, actions, foot forces, reward and
@@ -408,6 +413,8 @@ class PolicyEvaluator:
         self._graph = self._graph_key = None            # run's captured loop (key: the trace depth, gait, joints)
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
+        self._sensor_graph = self._sensor_graph_key = None  # run_sensor_test's own captured loop
+        self.last_sensor_bins = None
         self._fused = None
         self.last_cells = None
         self.last_push_cells = self.last_push_bins = None
@@ -437,7 +444,7 @@ class PolicyEvaluator:
         """Re-pack the fused act kernel's weights (after the runner loaded or trained them)."""
         if self._fused is not None:
             self._fused.refresh_weights()
-            self._graph = self._push_graph = self._cmd_graph = None
+            self._graph = self._push_graph = self._cmd_graph = self._sensor_graph = None
 
     # ------------------------------------------------------------------ one iteration
     def act(self):
@@ -582,8 +589,8 @@ class PolicyEvaluator:
                 buf.copy_(old)
 
     def _drive(self, slot, key, num_steps, graph, read_cells, prepare=None, started=None, cleanup=None):
-        """The run of all three modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
-        "_cmd_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
+        """The run of all four modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
+        "_cmd_graph", "_sensor_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
         the trace depth and the gait, joints and contacts flags are added: the loop is captured when
         there is no graph or the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
         buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
@@ -828,6 +835,93 @@ class PolicyEvaluator:
                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
                           for iw in range(nw)] for iy in range(ny)] for ix in range(nx)], **rates}
         self._attach_records(total, [b for plane in out["bins"] for row in plane for b in row])
+        return out
+
+    # ------------------------------------------------------------------ sensor model
+    def run_sensor_test(self, noise=(1.0,), bias=(0.0,), delay_s=(0.0,), num_steps=None, graph=True, trace_depth=None,
+                        gait=False, joints=False, contacts=False):
+        """How much observation noise, sensor offset and stale proprioception does the policy
+        survive: one run over a noise x bias x latency grid through the step kernel's sensor model
+        (lgx_buffers.obs_noise_scale / obs_bias / obs_delay, include/lgx.h ABI 15). Bin index
+        (in * |bias| + ib) * |delay_s| + id; envs get bins by randperm(num_envs, seeded with
+        env.seed) % bins. Env e of a bin gets the noise scale noise[in] (a multiple of the config's
+        own noise amplitude), the constant offset bias[ib] * env.sensor_amplitudes[i] * r[e, i] on
+        every sensor channel i (r uniform in [-1, 1], drawn once on the CPU from
+        torch.Generator().manual_seed(env.seed): the same for every level and on both backends) and
+        the sensing latency round(delay_s[id] / dt) control steps.
+
+        The records go to eval buffers of their own (env.sensor_eval_buffers: the bin is the cell
+        key), and this mode's captured loop is a graph of its own, captured once per grid shape and
+        flags: the three buffers are written in place, so other level values of the same shape
+        replay it. The env needs the buffers before any of its steps is captured
+        (domain_rand.sensor_model = True, or call this before run()) and, for a latency, the
+        capacity (domain_rand.max_obs_delay_s). The env's own per-env values are put back in place
+        when the run ends or fails.
+
+        trace_depth, gait, joints, contacts: as in run(), the records per bin.
+
+        Returns the report: "bins"[in][ib][id] with the REPORT_KEYS entries, "total", noise, bias,
+        delay_s, delay_steps. None where there is no data, never NaN.
+        ValueError: an empty list, a negative or non-finite entry, a latency beyond the capacity,
+        more than one noise level on an env whose config has noise.add_noise off (the levels could
+        not differ)."""
+        env = self.env
+        self._set_trace(trace_depth, gait, joints, contacts)
+        noise, bias, delay_s = ([float(v) for v in lst] for lst in (noise, bias, delay_s))
+        if min(len(noise), len(bias), len(delay_s)) < 1 or \
+                not all(math.isfinite(v) and v >= 0.0 for v in noise + bias + delay_s):
+            raise ValueError(f"sensor test: noise, bias and delay_s need at least one finite entry >= 0 each "
+                             f"(got {noise}, {bias}, {delay_s})")
+        dt = float(env.dt)
+        dsteps = [int(round(d / dt)) for d in delay_s]
+        cap = int(env._sensor_history_len) if env.obs_delay_steps is not None else 0
+        if max(dsteps) > cap:
+            raise ValueError(f"sensor test: a latency of {max(dsteps)} control steps is beyond the env's capacity of {cap} "
+                             "(domain_rand.max_obs_delay_s)")
+        if len(noise) > 1 and not env.cfg.noise.add_noise:
+            raise ValueError("sensor test: more than one noise level on an env whose config has noise.add_noise off "
+                             "(the levels could not differ)")
+        nn, nb, nd = len(noise), len(bias), len(delay_s)
+        n, p = env.num_envs, int(env.cfg.env.num_proprio)
+        bins = self._bins(nn * nb * nd)
+        r = 2.0 * torch.rand(n, p, generator=torch.Generator().manual_seed(int(env.seed))) - 1.0
+        scale = torch.tensor(noise, dtype=torch.float32)[bins // (nb * nd)]
+        level = torch.tensor(bias, dtype=torch.float32)[(bins // nd) % nb]
+        offsets = level.view(n, 1) * env.sensor_amplitudes.cpu().view(1, p) * r
+        steps = torch.tensor(dsteps, dtype=torch.float64)[bins % nd]
+        saved = []  # (buffer, its values before this run; neutral ones for a buffer this run allocates)
+
+        def prepare():
+            had_scale, had_bias = env.obs_noise_scales is not None, env.obs_biases is not None
+            for t in (env.obs_noise_scales, env.obs_biases, env.obs_delay_steps):
+                if t is not None:
+                    saved.append((t, t.clone()))
+            env.set_obs_noise_scale(scale.to(env.device))  # (a first call allocates: refused once a loop is captured)
+            if not had_scale:
+                saved.append((env.obs_noise_scales, torch.ones_like(env.obs_noise_scales)))
+            env.set_obs_bias(offsets.to(env.device))
+            if not had_bias:
+                saved.append((env.obs_biases, torch.zeros_like(env.obs_biases)))
+            if env.obs_delay_steps is not None:
+                env.set_obs_delay(steps.to(env.device) * dt)
+            ev = env.sensor_eval_buffers(nn, nb * nd)
+            env.sensor_cell_ids.copy_(bins.to(torch.int32))
+            self._record_buffers(nn, nb * nd, env.sensor_cell_ids)  # the bin is the cell key
+            return ev
+
+        def restore():
+            for buf, old in saved:
+                buf.copy_(old)
+
+        cells, head, rates = self._drive("_sensor_graph", (nn, nb, nd), num_steps, graph, env.eval_sensor_cells,
+                                         prepare, cleanup=restore)
+        self.last_sensor_bins = bins
+        w = self.mass * self.gravity
+        out = {**head, "noise": noise, "bias": bias, "delay_s": delay_s, "delay_steps": dsteps,
+               "total": cell_report(cells.reshape(-1, cells.shape[2]).sum(0), dt, w),
+               "bins": [[[cell_report(cells[i, j * nd + k], dt, w) for k in range(nd)] for j in range(nb)]
+                        for i in range(nn)], **rates}
+        self._attach_records(out["total"], [b for plane in out["bins"] for row in plane for b in row])
         return out
 
     # ------------------------------------------------------------------ flight recorder
