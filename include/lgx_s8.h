@@ -42,7 +42,7 @@ enum {
   LGX_S8_EPI_BIAS = 1,   /* FWD: + bias[n] */
   LGX_S8_EPI_ELU = 2,    /* FWD: then ELU(alpha = 1) */
   LGX_S8_EPI_DELU = 4,   /* DX: * ELU'(z) from the ELU output y = act (S8): y > 0 ? 1 : y + 1 */
-  LGX_S8_EPI_ACCUM = 8,  /* DW with split 1: C += result */
+  LGX_S8_EPI_ACCUM = 8,  /* DW with split 1: C += result (ignored with split > 1) */
   /* ABI 5, lgx_s8_heads_fwd only: the tile also runs the PPO loss head on its rows (below) */
   LGX_S8_EPI_HEAD_ACTOR = 16,  /* the actor's last hidden layer: policy half of the head */
   LGX_S8_EPI_HEAD_CRITIC = 32  /* the critic's last hidden layer: value half of the head */
@@ -55,7 +55,8 @@ typedef struct lgx_s8_gemm_args {
   int32_t epilogue;             /* LGX_S8_EPI_* */
   void* C; int64_t ldc;         /* FWD / DX: S8 output (optional if C32 is set) */
   float* C32; int64_t ldc32;    /* FWD / DX: fp32 copy of the output (optional); DW: fp32 output
-                                   (split 1) or the partial workspace [split][M][N] (split > 1) */
+                                   (split <= 1, pitch ldc32) or the dense partial workspace
+                                   [split][M][N] (split > 1; ldc32 unused) */
   const float* bias;            /* FWD, LGX_S8_EPI_BIAS: [N] */
   const void* act; int64_t ld_act;      /* DX, LGX_S8_EPI_DELU: Y_prev (S8) */
   const float* addend; int64_t ld_add;  /* DX (optional): + addend[m][n] for n < add_cols, after ELU' */
@@ -63,7 +64,11 @@ typedef struct lgx_s8_gemm_args {
   float* colsum_ws;             /* FWD / DX (optional): [ceil(M / LGX_S8_TILE_M)][N] fp32 column
                                    sums of the output over each 64-row half tile (the next weight
                                    gradient's bias gradient, reduced with lgx_s8_reduce) */
-  int32_t split;                /* DW: K split (>= 1); kchunk = round_up(ceil(K / split), 32) */
+  int32_t split;                /* DW: K split (>= 1); kchunk = round_up(ceil(K / split), 32). With
+                                   split > 1 all `split` slabs are written, whatever K: slab z
+                                   holds the K range [z kchunk, min(K, (z + 1) kchunk)), zeros
+                                   where that range is empty (whole 32-deep steps can leave fewer
+                                   chunks than slabs; lgx_s8_pick_split's splits never do) */
   int32_t pad0;
 } lgx_s8_gemm_args;
 

@@ -93,14 +93,15 @@ struct Prob {
   const char* A; const char* B;
   int64_t lda, ldb;            // bytes
   int M, N, K;
-  int tiles_m, tiles_n, tiles;  // tiles includes the split
+  int tiles_m, tiles_n, tiles;  // tiles includes the split (DW: the REQUESTED split)
   int kchunk, epi;
   char* C; int64_t ldc;         // bytes (S8)
   float* C32; int64_t ldc32;    // floats
   const float* bias;
   const char* act; int64_t ld_act;  // bytes (S8)
   const float* addend; int64_t ld_add;
-  int add_cols, pad;
+  int add_cols;
+  int part;                     // DW: C32 is the partial workspace [split][M][N] (split > 1 requested)
   float* colsum_ws;
 };
 
@@ -251,10 +252,11 @@ __device__ __forceinline__ void load_s8(const char* src, float (&v)[8]) {
 }
 
 // ---- epilogues over an fp32 LDS image [ROWS][CPI] of output rows m_base.., columns n_base..
-// DW: fp32 rows (float4): split partial slab z, or the output itself (split 1, optional accumulate)
+// DW: fp32 rows (float4): split partial slab z (every requested slab: one whose K range is empty
+// gets the zero tile of the kernel's nk == 0 path), or the output itself (split 1, optional accumulate)
 template <int NT, int ROWS, int COLS, int CPI>
 __device__ __forceinline__ void epi_dw(const Prob& P, const float* img, int m_base, int n_base, int z, int tid) {
-  const bool part = P.tiles > P.tiles_m * P.tiles_n;
+  const bool part = P.part != 0;
   float* dst = part ? P.C32 + (int64_t)z * P.M * P.N : P.C32;
   const int64_t ldd = part ? P.N : P.ldc32;
   const bool accum = !part && (P.epi & LGX_S8_EPI_ACCUM);
@@ -555,9 +557,10 @@ __global__ __launch_bounds__(Cfg::NT, 2) __attribute__((amdgpu_waves_per_eu(1, 2
 // no barrier): one tile per block, the blocks dispatched by the hardware as slots free up (a
 // static persistent tile list measured slower: it loses that dynamic balance).
 // The MFMA operands are swapped (weights as the MFMA's A operand, activations as its B operand):
-// the same three products per K step in the same accumulation order (lo*hi, hi*lo, hi*hi; bit-
-// identical outputs, tests/test_gpu_s8.py), but each lane then holds 4 CONSECUTIVE output columns
-// of one row (C/D map: column = 4 (lane >> 4) + r, row = lane & 15). Lanes l and l + 16 hold the
+// the same three products per K step in the same accumulation order (lo*hi, hi*lo, hi*hi; outputs
+// bit-identical to s8_gemm_kernel<FWD>'s when measured, profiles/r06_s8_levels.txt; no test holds
+// that identity: a product build cannot select the other kernel), but each lane then holds 4
+// CONSECUTIVE output columns of one row (C/D map: column = 4 (lane >> 4) + r, row = lane & 15). Lanes l and l + 16 hold the
 // two halves of one 8-column S8 group: after the bf16 hi / lo split one v_permlane16_swap per
 // dword gives lane l the group's 8 hi values and lane l + 16 its 8 lo values — one 16-B store
 // each, the 32-B group written whole. Column sums (optional for FWD) per 64-row half tile: the
@@ -1561,10 +1564,14 @@ static int32_t gemm_group(const lgx_s8_gemm_args* a, int32_t n, int32_t kind, co
         return fail("lgx_s8_gemm_group: ELU' epilogue needs an aligned S8 act");
       if (q.C32 && q.ldc32 < q.N) return fail("lgx_s8_gemm_group: ldc32 < N");
     }
+    // kchunk = round_up(ceil(K / split), 32). The requested split is kept: the caller reduces
+    // that many slabs [split][M][N], so the slabs past the last K chunk are launched too and
+    // written as zeros (lgx_s8_pick_split's splits leave none: ceil(K / chunk) chunks of whole steps)
     const int ksteps = cdiv(q.K, lgxs::BK);
-    const int per = std::max(1, cdiv(ksteps, split));
-    p.kchunk = per * lgxs::BK;
-    split = std::max(1, cdiv(ksteps, per));
+    p.kchunk = std::max(1, cdiv(ksteps, split)) * lgxs::BK;
+    p.part = split > 1;
+    if ((int64_t)p.tiles_m * p.tiles_n * split >= (1ll << 31) || (int64_t)split * p.kchunk >= (1ll << 31))
+      return fail("lgx_s8_gemm_group: split too large (tile count / K offsets are 32-bit)");
     p.tiles = p.tiles_m * p.tiles_n * split;
     acc += cdiv(p.tiles, 8);
     g.start[++np] = acc;
