@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 15
+#define LGX_ABI_VERSION 16
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -427,6 +427,32 @@ typedef struct lgx_buffers {
   const int32_t* obs_delay;     /* [N]     sensing latency of env e in control steps                    */
   float* sensor_history;        /* [N,K,P] state: the last K raw proprio rows of the current episode    */
   int32_t* sensor_count;        /* [N]     state: raw rows written since env e's last reset             */
+  /* External force (ABI v16; the reference ecosystem's "apply an external force / torque to the
+     base" event term): a force that lasts, on the base link, inside the physics. Both optional;
+     both NULL = the step of ABI 15, bit for bit. lgx_bind refuses one without the other.
+     Window: (start, steps, period) = force_window[e][0..2] in episode steps. With ep =
+     episode_length[e] as the step finds it, plus 1 (the value the step will write: the step
+     numbering of push_step and cmd_switch_step) and k = ep - start, the force acts in all substeps
+     of this step iff start >= 1 && steps >= 1 && k >= 0 && (period >= 1 ? k % period < steps :
+     k < steps). start + steps is never formed: steps = INT32_MAX means "to the end of the
+     episode". An in-step reset, a NaN-guard reset and lgx_reset_envs return the episode length to
+     0, so the next episode sees the same window (no state, no code at the reset).
+     Frame: once per control step the force (forward, left, up) = force_vec[e][0..2] in N becomes a
+     world vector from the root quaternion the step starts from: forward and left along the robot's
+     heading (the normalised xy projection of its x axis; (1, 0) when that projection is shorter
+     than 1e-6: the rule of the scheduled push), up along world z. The world vector stays fixed
+     over the step's substeps. The application point force_vec[e][3..5] (m, base link frame) moves
+     with the base: in each substep it is a = P0 + R0 * point.
+     Where it enters: the bias pass of the kinematics, link 0 only: F0 -= f and N0 -= cross(a - C0,
+     f), C0 the base link's COM (mass_params' shift included). The 16 base sums, the joint biases,
+     the contact solve and the integration follow unchanged. The same rule holds in lgx_step and
+     lgx_step_dev on both backends.
+     Identity: an env whose window is off in this step, or whose force (forward, left, up) is
+     exactly zero, keeps the bits of the unbound step. A non-finite row is the caller's error; the
+     NaN guard handles such an env like any other blow-up. The step reads both buffers at kernel
+     time: writing them between steps needs no re-bind. */
+  const int32_t* force_window; /* [N,3] start, steps, period (episode steps) */
+  const float* force_vec;      /* [N,6] forward, left, up in N; application point x, y, z in m, base link frame */
 } lgx_buffers;
 
 typedef struct lgx_env lgx_env;

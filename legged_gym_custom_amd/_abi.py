@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -154,6 +154,7 @@ class Buffers(C.Structure):
         "blew_up", "blowup_count", "command_ranges", "curriculum_vals", "command_range_log",
         "action_delay", "action_history", "motor_strength", "push_step", "push_dvel", "cmd_step", "cmd_val",
         "obs_noise_scale", "obs_bias", "obs_delay", "sensor_history", "sensor_count",
+        "force_window", "force_vec",
     ]]
 
 

@@ -81,11 +81,17 @@ __host__ __device__ inline int64_t arena_floats(const lgx_task_params& p) {
   return post > ROWS_FLOATS ? post : ROWS_FLOATS;
 }
 
+constexpr int FRC_ON = 0, FRC_F = 1, FRC_PT = 4;  // the external force's words of Sh::rterm
 struct Sh {
   // --- post-physics per-env scalars (written by lane 0, read by all lanes)
   Scratch x;
   float root[13], cmd[4], fat[4], lch[4];
   int lc[4];
+  // rterm: the reward terms, first written after the physics. During the physics its first words
+  // hold the external force (include/lgx.h, ABI 16) that the FORCE instances stage once per step and
+  // the substeps read: [FRC_ON] 1 when it acts in this step, else 0, [FRC_F..+2] the world vector,
+  // [FRC_PT..+2] the application point in the base link frame. So Sh keeps its layout and the
+  // instances without the force their code.
   float rterm[64];
   float jsum[16];  // per-env joint / height-point sums the reward terms share (joint_sums)
   // post-physics inputs read at kernel start (their HBM latency hides behind the physics)
@@ -254,7 +260,8 @@ LGX_DEV float from_prev_lane(float x) { return dpp_shr_t<0x111>(x); }
 // link arrays the later phases read (R, P, Ax, W, V, C, I, m). With BIAS, the same lanes
 // also form the per-link COM wrench (Fw, Nw) and return the 16 base sums about p0 (mass,
 // first moment, inertia, wrench), reduced across lanes 0..15 by DPP (see dynamics).
-template <bool BIAS>
+// FORCE (with BIAS): the external force of ABI 16 on the base link, staged in s.rterm (FRC_*).
+template <bool BIAS, bool FORCE = false>
 LGX_DEV void kinematics(Sh& s, float* A, const lgx_model* M, const lgx_task_params* Pm, int lane) {
   const int j = lane < NJ ? lane : NJ - 1;
   const bool base = lane == NJ;  // the base rides the chain as a fixed joint at the root
@@ -357,8 +364,16 @@ LGX_DEV void kinematics(Sh& s, float* A, const lgx_model* M, const lgx_task_para
     const f3 g = ld3(Pm->gravity);
     const f3 rl = C - P;
     const f3 acc = Ao + cross(Al, rl) + cross(W, cross(W, rl));
-    const f3 F = (acc - g) * m;
-    const f3 N = symv(Iw, Al) + cross(W, symv(Iw, W));
+    f3 F = (acc - g) * m;
+    f3 N = symv(Iw, Al) + cross(W, symv(Iw, W));
+    // external force (include/lgx.h, ABI 16): on the base link, at a = P0 + R0 * point
+    if constexpr (FORCE) {
+      if (base && s.rterm[FRC_ON] != 0.f) {
+        const f3 f = ld3(s.rterm + FRC_F);
+        F = F - f;
+        N = N - cross(P + mv(R, ld3(s.rterm + FRC_PT)) - C, f);
+      }
+    }
     if (lane <= NJ) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) s.I[k][q] = Iw[q];
@@ -1059,7 +1074,7 @@ LGX_DEV void solve_rows(Sh& s, float* A, const lgx_task_params* Pm, int lane, in
 // one physics substep (legged_robot.py:80-85 loop body) of the group's env. WL = the env's lanes
 // (see grp_of_lane); with two envs per wave, S0 / A0 / astride locate both envs' Sh and arenas
 // for the wide constraint solve (an env with more than 32 rows: each env in turn on all 64 lanes).
-template <bool TERRAIN, bool ACTNET, int WL>
+template <bool TERRAIN, bool ACTNET, int WL, bool FORCE>
 LGX_DEV void substep(Sh& s, float* A, Sh* S0, float* A0, int astride, const lgx_model* M_,
                      const lgx_task_params* Pm_, const lgx_buffers& B, int lane_, int e, int sub, bool last) {
   // The model and task tables are re-read each substep (L1 / scalar-cache hits) rather than
@@ -1095,7 +1110,7 @@ LGX_DEV void substep(Sh& s, float* A, Sh* S0, float* A0, int astride, const lgx_
     }
   }
   PH(1);
-  kinematics<true>(s, A, M, Pm, lane);
+  kinematics<true, FORCE>(s, A, M, Pm, lane);
   PH(2);
   DynOut dy;
   dynamics(s, A, lane, dy);
@@ -1529,7 +1544,9 @@ LGX_DEV void get_heights(const lgx_task_params* Pm, const lgx_buffers& B, Sh& s,
 // SIMD) are resident — the register budget is that of 2 waves per SIMD.
 // SENSOR: the instances with the sensor model (include/lgx.h, ABI 15), launched when one of its
 // buffers is bound; the others hold none of its code.
-template <bool PHYSICS, bool TERRAIN, bool ACTNET, int EPW, bool SENSOR>
+// FORCE: likewise the instances with the external force (include/lgx.h, ABI 16), launched when its
+// buffers are bound.
+template <bool PHYSICS, bool TERRAIN, bool ACTNET, int EPW, bool SENSOR, bool FORCE>
 __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) void env_step_kernel(const lgx_model* __restrict__ M,
                                                       const lgx_task_params* __restrict__ Pm,
                                                       const lgx_buffers* __restrict__ Bp, uint64_t seed,
@@ -1611,6 +1628,20 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
       f3 rc = mv(R, mk(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
       f3 vo = ld3(s.root + 7) - cross(ld3(s.wb), rc);  // COM velocity -> origin velocity
       st3(s.vo, vo);
+      // external force (include/lgx.h, ABI 16): the window at the episode length this step will
+      // write, the world vector from the quaternion the step starts from; the substeps read LDS only
+      if constexpr (FORCE) {
+        s.rterm[FRC_ON] = 0.f;
+        if (B.force_window) {
+          const int32_t* fwin = B.force_window + (size_t)e * 3;
+          const float* fv = B.force_vec + (size_t)e * 6;
+          if (force_window_on(fwin[0], fwin[1], fwin[2], s.ep_prev + 1) && (fv[0] != 0.f || fv[1] != 0.f || fv[2] != 0.f)) {
+            s.rterm[FRC_ON] = 1.f;
+            force_to_world(s.root + 3, fv, s.rterm + FRC_F);
+            for (int i = 0; i < 3; ++i) s.rterm[FRC_PT + i] = fv[3 + i];
+          }
+        }
+      }
     }
     __syncthreads();
     PH(0);
@@ -1619,7 +1650,7 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
         stage_actuator_action(s, Pm, B, e, lane, sub);
         __syncthreads();
       }
-      substep<TERRAIN, ACTNET, WL>(s, AR, S_, lgx_dyn, astride, M, Pm, B, lane, e, sub, sub == Pm->decimation - 1);
+      substep<TERRAIN, ACTNET, WL, FORCE>(s, AR, S_, lgx_dyn, astride, M, Pm, B, lane, e, sub, sub == Pm->decimation - 1);
     }
     // the rest of the step (guard, observation, last_actions, rewards) sees this step's action
     if (!ACTNET && B.action_delay) {
@@ -2214,6 +2245,8 @@ int lgx_bind(lgx_env* env, const lgx_buffers* b) {
   if (b->sensor_count && !b->sensor_history) return fail(env, "lgx_bind: sensor_count needs sensor_history");
   if (b->sensor_history && env->params.sensor_history_len <= 0)
     return fail(env, "lgx_bind: sensor_history with params.sensor_history_len = 0");
+  if (b->force_window && !b->force_vec) return fail(env, "lgx_bind: force_window without force_vec");
+  if (b->force_vec && !b->force_window) return fail(env, "lgx_bind: force_vec without force_window");
   if (b->push_step && !b->push_dvel) return fail(env, "lgx_bind: push_step without push_dvel");
   if (b->push_dvel && !b->push_step) return fail(env, "lgx_bind: push_dvel without push_step");
   if (b->cmd_step && !b->cmd_val) return fail(env, "lgx_bind: cmd_step without cmd_val");
@@ -2267,16 +2300,19 @@ static int launch_step(lgx_env* env, uint64_t seed, uint64_t step, const uint64_
   // with none of them bound the step runs the code it ran before ABI 15
   const lgx_buffers& hb = env->buffers;
   const bool sensor = hb.obs_noise_scale || hb.obs_bias || hb.sensor_history;
-#define LGX_STEP_KERNEL(SENSOR)                                                                              \
-  (epw == 2 ? (!physics ? lgx::env_step_kernel<false, false, false, 2, SENSOR>                               \
-                        : (terrain ? lgx::env_step_kernel<true, true, false, 2, SENSOR>                      \
-                                   : lgx::env_step_kernel<true, false, false, 2, SENSOR>))                   \
-   : !physics ? lgx::env_step_kernel<false, false, false, 1, SENSOR>                                         \
-   : actnet   ? (terrain ? lgx::env_step_kernel<true, true, true, 1, SENSOR>                                 \
-                         : lgx::env_step_kernel<true, false, true, 1, SENSOR>)                               \
-              : (terrain ? lgx::env_step_kernel<true, true, false, 1, SENSOR>                                \
-                         : lgx::env_step_kernel<true, false, false, 1, SENSOR>))
-  auto kern = sensor ? LGX_STEP_KERNEL(true) : LGX_STEP_KERNEL(false);
+  // and so does the external force's (FORCE; it acts in the physics: the other instances have none)
+  const bool force = hb.force_window != nullptr;
+#define LGX_STEP_KERNEL(SENSOR, FORCE)                                                                       \
+  (epw == 2 ? (!physics ? lgx::env_step_kernel<false, false, false, 2, SENSOR, false>                        \
+                        : (terrain ? lgx::env_step_kernel<true, true, false, 2, SENSOR, FORCE>               \
+                                   : lgx::env_step_kernel<true, false, false, 2, SENSOR, FORCE>))            \
+   : !physics ? lgx::env_step_kernel<false, false, false, 1, SENSOR, false>                                  \
+   : actnet   ? (terrain ? lgx::env_step_kernel<true, true, true, 1, SENSOR, FORCE>                          \
+                         : lgx::env_step_kernel<true, false, true, 1, SENSOR, FORCE>)                        \
+              : (terrain ? lgx::env_step_kernel<true, true, false, 1, SENSOR, FORCE>                         \
+                         : lgx::env_step_kernel<true, false, false, 1, SENSOR, FORCE>))
+  auto kern = sensor ? (force ? LGX_STEP_KERNEL(true, true) : LGX_STEP_KERNEL(true, false))
+                     : (force ? LGX_STEP_KERNEL(false, true) : LGX_STEP_KERNEL(false, false));
 #undef LGX_STEP_KERNEL
   const size_t dyn = sizeof(float) * (size_t)lgx::arena_floats(env->params) * epw;
   hipLaunchKernelGGL(kern, dim3(N / epw), dim3(64), dyn, st, env->d_model, env->d_params, env->d_buffers, seed, step,

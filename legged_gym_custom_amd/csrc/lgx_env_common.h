@@ -277,6 +277,29 @@ LGX_HD void scheduled_push(float* root, const float* dv) {
   root[12] = root[12] + dv[2];
 }
 
+// External force (lgx_buffers.force_window / force_vec, include/lgx.h ABI 16). The window: is the
+// force of an env with the row (start, steps, period) on in the step that writes episode length
+// ep? start + steps is never formed (steps = INT32_MAX: to the end of the episode).
+LGX_HD bool force_window_on(int32_t start, int32_t steps, int32_t period, long long ep) {
+  if (start < 1 || steps < 1) return false;
+  const long long k = ep - (long long)start;
+  if (k < 0) return false;
+  return (period >= 1 ? k % (long long)period : k) < (long long)steps;
+}
+// The frame: fv = (forward, left, up) in the heading frame of the root quaternion q (x, y, z, w)
+// to the world vector out, with the heading rule of scheduled_push; up goes along world z.
+LGX_HD void force_to_world(const float* q, const float* fv, float* out) {
+  const float fwd[3] = {1.f, 0.f, 0.f};
+  float f[3];
+  quat_apply(q, fwd, f);
+  const float n = nrm2(f[0], f[1]);
+  const bool ok = n > 1e-6f;
+  const float hx = ok ? f[0] / n : 1.0f, hy = ok ? f[1] / n : 0.0f;
+  out[0] = fv[0] * hx - fv[1] * hy;
+  out[1] = fv[0] * hy + fv[1] * hx;
+  out[2] = fv[2];
+}
+
 // Push recovery (lgx_eval_buffers.push_rec, include/lgx.h ABI 9): one post-push sample of an env,
 // k > 0 steps after its push. The new value of record column col (0..3) from its old value x; pg:
 // projected gravity, c / v: commands and base_lin_vel. (The kernel gives one column to each of an

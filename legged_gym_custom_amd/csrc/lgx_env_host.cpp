@@ -39,6 +39,8 @@ struct Env {
   float qb[4], pb[3], vo[3], wb[3];
   float th[NJ], thd[NJ], tau[NJ], act[NJ], kpm[NJ], kdm[NJ], ldv[NJ];
   float madd, cadd[3], mu;
+  int fon;                                     // external force (ABI 16): on in this step,
+  float fw[3], fpt[3];                         // world vector, application point (base link frame)
   Link lk[NL];
   float tot[16];                               // base sums about p0: m, h(3), Ip(6), F(3), N(3)
   float hj[NJ], Bc[NJ][6], Dl[4][6], Dinv[4][6], X[NJ][6], Sinv[6][6], hb[6];
@@ -125,7 +127,13 @@ static void kinematics(Env& s, const lgx_model* M, const lgx_task_params* P) {
       c.m = m;
       const f3 W = ld3(c.W), al = ld3(Al[k]), rl = C - ld3(c.P);
       const f3 acc = ld3(Ao[k]) + cross(al, rl) + cross(W, cross(W, rl));
-      const f3 F = (acc - g) * m, N = symv(Iw, al) + cross(W, symv(Iw, W));
+      f3 F = (acc - g) * m, N = symv(Iw, al) + cross(W, symv(Iw, W));
+      // external force (include/lgx.h, ABI 16): on the base link, at a = P0 + R0 * point
+      if (k == 0 && s.fon) {
+        const f3 f = ld3(s.fw);
+        F = F - f;
+        N = N - cross(ld3(c.P) + mv(R, ld3(s.fpt)) - C, f);
+      }
       st3(c.F, F);
       st3(c.N, N);
       const f3 r = C - p0;
@@ -731,6 +739,17 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     quat_to_R(s.qb, R);
     const f3 rc = mv(R, mk(M->link_com[0][0] + s.cadd[0], M->link_com[0][1] + s.cadd[1], M->link_com[0][2] + s.cadd[2]));
     st3(s.vo, ld3(r0 + 7) - cross(ld3(s.wb), rc));  // COM velocity -> origin velocity
+    // external force (include/lgx.h, ABI 16): the kernel's rule
+    s.fon = 0;
+    if (B->force_window) {
+      const int32_t* fwin = B->force_window + (size_t)e * 3;
+      const float* fv = B->force_vec + (size_t)e * 6;
+      if (force_window_on(fwin[0], fwin[1], fwin[2], ep_prev + 1) && (fv[0] != 0.f || fv[1] != 0.f || fv[2] != 0.f)) {
+        s.fon = 1;
+        force_to_world(r0 + 3, fv, s.fw);
+        for (int i = 0; i < 3; ++i) s.fpt[i] = fv[3 + i];
+      }
+    }
     for (int sub = 0; sub < P->decimation; ++sub) substep(s, M, P, B, e, sub, sub == P->decimation - 1);
     // NaN/Inf guard (the kernel's rule, lgx_env.hip): a non-finite state after the substeps
     // becomes a finite stand-in and the env is reset below

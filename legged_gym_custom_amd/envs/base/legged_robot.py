@@ -7,6 +7,7 @@ reference, env-major), builds the model/params once, binds the buffers to the na
 env, and keeps the reference's Python-visible surface: step/reset/reset_idx, the
 8-tuple return, extras['time_outs'/'episode'], common_step_counter, buffer attributes.
 """
+import math
 import os
 
 import numpy as np
@@ -669,6 +670,7 @@ class LeggedRobot(BaseTask):
         self.cmd_step = self.cmd_val = None  # command schedule (ABI 10): no draw, off unless allocated
         if prm.scheduled_commands(self.cfg):
             self._alloc_command_schedule()
+        self._init_external_force()  # after every existing setup draw: those keep their values
         self.default_dof_pos = torch.tensor([self.cfg.init_state.default_joint_angles[nm] for nm in self.dof_names],
                                             device=dev).unsqueeze(0)
         self._dof_state3[..., 0] = self.default_dof_pos
@@ -752,6 +754,7 @@ class LeggedRobot(BaseTask):
             "cmd_step": self.cmd_step, "cmd_val": self.cmd_val,
             "obs_noise_scale": self.obs_noise_scales, "obs_bias": self.obs_biases, "obs_delay": self.obs_delay_steps,
             "sensor_history": self.sensor_history, "sensor_count": self.sensor_count,
+            "force_window": self.force_window, "force_vec": self.force_vec,
             **self._sea_buffers,
         })
 
@@ -1034,6 +1037,89 @@ class LeggedRobot(BaseTask):
         buffers). The commands an env holds stay until its next resample or reset."""
         if self.cmd_step is not None:
             self.cmd_step.fill_(-1)
+
+    # ------------------------------------------------------------------ external force
+    def _init_external_force(self):
+        """Sustained external force on the base (include/lgx.h ABI 16; domain_rand keys of
+        params.external_force). The buffers exist, and are bound, when scheduled_forces or
+        randomize_external_force is on (or after set_force_schedule's first call); otherwise both
+        attributes are None and the step is that of ABI 15. The randomisation draws after every
+        other setup draw, for all global envs and sliced by rank, fixed per env: a horizontal
+        direction uniform on the circle, a magnitude U(lo, hi) N at the base origin, lasting `steps`
+        of every `period` control steps from the start 1 + floor(U * period), so the envs are out
+        of phase."""
+        dev = self.device
+        total, sl = self.num_envs_total, slice(self.env_id_offset, self.env_id_offset + self.num_envs)
+        ef = prm.external_force(self.cfg, self.dt)
+        self.force_window = self.force_vec = None
+        if ef["alloc"]:
+            self._alloc_force_schedule()
+        if ef["on"]:
+            lo, hi = ef["range_n"]
+            theta = 2.0 * math.pi * torch.rand(total, device=dev)
+            mag = (hi - lo) * torch.rand(total, device=dev) + lo
+            start = 1 + torch.floor(torch.rand(total, device=dev) * ef["period"]).to(torch.int64).clamp_(max=ef["period"] - 1)
+            force = torch.stack([mag * torch.cos(theta), mag * torch.sin(theta), torch.zeros_like(mag)], dim=1)
+            self.set_force_schedule(start[sl], force[sl], steps=ef["steps"], period=ef["period"])
+
+    def _alloc_force_schedule(self):
+        self.force_window = torch.zeros(self.num_envs, 3, dtype=torch.int32, device=self.device)
+        self.force_vec = torch.zeros(self.num_envs, 6, device=self.device)
+
+    def set_force_schedule(self, start, force, steps=None, period=0, point=(0.0, 0.0, 0.0)):
+        """External force on the base (include/lgx.h ABI 16): from the step in which its episode
+        length becomes start[e], env e's base link takes force[e] = (forward, left in its heading
+        frame, up along world z) in N at point[e] (m, base link frame) in every substep of `steps`
+        control steps (None: to the end of the episode); with period >= 1 the window repeats every
+        `period` steps. A start <= 0 means never. start, steps, period: ints or int tensors
+        [num_envs]; force, point: [3] or [num_envs, 3]. Written in place once the buffers exist; the
+        first call on an env built without domain_rand.scheduled_forces allocates them and re-binds,
+        which a captured graph of this env's step would not see: RuntimeError once a step of this
+        env has been captured. ValueError for wrong shapes, non-finite values, steps < 1,
+        period < 0 or a start beyond max_episode_length."""
+        n, i32max = self.num_envs, 2 ** 31 - 1
+
+        def ints(v, what):
+            t = torch.as_tensor(v, device=self.device)
+            if t.dtype.is_floating_point or t.dtype == torch.bool or t.dim() not in (0, 1) or \
+                    (t.dim() == 1 and t.shape[0] != n):
+                raise ValueError(f"force {what}: an int or an int tensor [{n}], got {t.dtype} of shape {list(t.shape)}")
+            return t.to(torch.int64)
+
+        def vec3(v, what):
+            t = torch.as_tensor(v, dtype=torch.float32, device=self.device)
+            if tuple(t.shape) not in ((3,), (n, 3)):
+                raise ValueError(f"force {what}: a tensor [3] or [{n}, 3], got shape {list(t.shape)}")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"force {what} must be finite")
+            return t
+
+        st, pe = ints(start, "start"), ints(period, "period")
+        sp = ints(i32max if steps is None else steps, "steps")
+        fv, pt = vec3(force, "vector"), vec3(point, "point")
+        if int(sp.min()) < 1 or int(sp.max()) > i32max:
+            raise ValueError(f"force steps must lie in 1..{i32max} (None: to the end of the episode)")
+        if int(pe.min()) < 0 or int(pe.max()) > i32max:
+            raise ValueError(f"force period must lie in 0..{i32max} (0: the window does not repeat)")
+        if int(st.max()) > int(self.max_episode_length) or int(st.min()) < -i32max:
+            raise ValueError(f"force start {int(st.max())} is beyond max_episode_length = {int(self.max_episode_length)}")
+        if self.force_window is None:
+            if self._captured:
+                raise RuntimeError("set_force_schedule: this env has no force buffers and its step has been captured in "
+                                   "a graph, which would go on replaying the old binding; build the env with "
+                                   "domain_rand.scheduled_forces or set a schedule before the capture")
+            self._alloc_force_schedule()
+            self._bind()
+        self.force_window[:, 0].copy_(st.to(torch.int32).expand(n))
+        self.force_window[:, 1].copy_(sp.to(torch.int32).expand(n))
+        self.force_window[:, 2].copy_(pe.to(torch.int32).expand(n))
+        self.force_vec[:, :3].copy_(fv.expand(n, 3))
+        self.force_vec[:, 3:].copy_(pt.expand(n, 3))
+
+    def clear_force_schedule(self):
+        """No env is forced: the starts zeroed in place (a no-op on an env without the buffers)."""
+        if self.force_window is not None:
+            self.force_window[:, 0].zero_()
 
     @property
     def physics_blowups(self):

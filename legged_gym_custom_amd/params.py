@@ -211,6 +211,31 @@ def scheduled_pushes(cfg):
     return bool(getattr(cfg.domain_rand, "scheduled_pushes", False))
 
 
+def external_force(cfg, dt):
+    """The external-force keys of cfg.domain_rand (all optional, read with getattr: the shipped
+    config classes do not carry them; set them on a config instance) -> dict:
+      alloc      scheduled_forces or randomize_external_force: allocate and bind the force buffers
+                 (lgx_buffers.force_window / force_vec, include/lgx.h ABI 16) when the env is built,
+                 so that env.set_force_schedule never has to re-bind
+      on / range_n [lo, hi]   randomize_external_force, external_force_range (N, the magnitude)
+      steps      round(external_force_duration_s / dt) control steps the force lasts, at least 1
+      period     round(external_force_interval_s / dt) control steps from one onset to the next
+    A ValueError when the randomisation is on and the range is not 0 <= lo <= hi, the duration is
+    not positive or the interval is shorter than one control step."""
+    dr = cfg.domain_rand
+    on = bool(getattr(dr, "randomize_external_force", False))
+    lo, hi = (float(v) for v in getattr(dr, "external_force_range", [0.0, 0.0]))
+    dur = float(getattr(dr, "external_force_duration_s", 1.0))
+    itv = float(getattr(dr, "external_force_interval_s", 5.0))
+    steps, period = max(int(round(dur / dt)), 1), int(round(itv / dt))
+    if on and (not (0.0 <= lo <= hi) or not dur > 0.0 or period < 1):
+        raise ValueError(f"domain_rand.external_force_range {[lo, hi]} N / external_force_duration_s {dur} / "
+                         f"external_force_interval_s {itv}: need 0 <= lo <= hi, a positive duration and an interval "
+                         "of at least one control step")
+    return {"alloc": on or bool(getattr(dr, "scheduled_forces", False)), "on": on, "range_n": (lo, hi),
+            "steps": steps, "period": period}
+
+
 def scheduled_commands(cfg):
     """cfg.commands.scheduled_commands (optional, read with getattr as scheduled_pushes is): allocate
     and bind the command schedule buffers (lgx_buffers.cmd_step / cmd_val, include/lgx.h ABI 10) when

@@ -10,6 +10,8 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
          [--obs_noise a[,b,...]] [--obs_bias a[,b,...]] [--obs_delay_ms a[,b,...]]
+         [--force_n a[,b,...] [--force_dirs 8] [--force_at_s 2.0] [--force_for_s S] [--force_point x,y,z]
+          [--force_cmd vx,vy,yaw]]
          [--trace_falls M [--trace_s 2.0]] [--gait] [--joints] [--contacts]
 
 --action_delay_ms: a constant actuation latency for all envs (the env is built with the action
@@ -35,6 +37,14 @@ level), --obs_bias in multiples of the same amplitudes as a constant random offs
 --obs_delay_ms as a sensing latency in ms, rounded to control steps. A list that is not given is the neutral one
 (1 / 0 / 0). The env is built with domain_rand.sensor_model = True and the sensor history the largest latency needs;
 the rest of the config stays as trained. Not with --push_vel, --cmd_vx, --action_delay_ms or --motor_strength.
+
+--force_n: the force test (PolicyEvaluator.run_force_test): every env holds --force_cmd (default 0.5,0,0) and,
+from --force_at_s seconds into its episode on, takes a sustained external force of one of the given magnitudes (N;
+0 gives the control row) from one of --force_dirs directions in the robot's heading frame on its base, at
+--force_point (m, base link frame), for --force_for_s seconds (default: to the end of the episode); one run fills
+the forces x directions table with survival, settle time, peak tilt, the achieved velocity, the deflection and the
+compliance (m/s per N) per bin. The config's random pushes are switched off for this mode. Not with --push_vel,
+--cmd_vx, the sensor test, --action_delay_ms or --motor_strength.
 
 --trace_falls M: the flight recorder (PolicyEvaluator.traces), valid in every mode: the last --trace_s seconds
 of every env's episode are kept in a ring buffer on the device (depth = round(trace_s / dt) steps, clipped to
@@ -71,7 +81,8 @@ or bin with data is printed before the JSON ("contacts <where>: falls 37: base 6
 
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
-eval_<policy>_command.json; the sensor test: eval_<policy>_sensors.json)."""
+eval_<policy>_command.json; the sensor test: eval_<policy>_sensors.json; the force test:
+eval_<policy>_force.json)."""
 import argparse
 import json
 import os
@@ -93,7 +104,8 @@ from legged_gym_custom_amd.utils.evaluator import PolicyEvaluator  # noqa: E402
 def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, action_delay_ms=None, motor_strength=None,
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
              cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False, contacts=False, obs_noise=None,
-             obs_bias=None, obs_delay_ms=None):
+             obs_bias=None, obs_delay_ms=None, force_n=None, force_dirs=8, force_at_s=2.0, force_for_s=None,
+             force_point=None, force_cmd=None):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -124,6 +136,13 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         # the config's own capacity by the env's rule (a range counts only with its randomisation on)
         own = prm.sensor_model(env_cfg, env_cfg.control.decimation * env_cfg.sim.dt)["max_delay_s"]
         dr.max_obs_delay_s = max([own] + obs_delay_s)  # the capacity the largest latency needs
+    if force_n:
+        if push_vel or cmd_vx or sensors or delays_s or motor_strength is not None:
+            raise ValueError("--force_n is a mode of its own: not with --push_vel / --cmd_vx / --obs_noise / --obs_bias / "
+                             "--obs_delay_ms / --action_delay_ms / --motor_strength")
+        env_cfg.commands.scheduled_commands = True   # the schedule and the force buffers exist
+        env_cfg.domain_rand.scheduled_forces = True  # before any capture
+        env_cfg.domain_rand.push_robots = False      # the force is the only disturbance
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
 
     train_cfg.runner.resume = True
@@ -152,6 +171,12 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         report = dict(**head, **ev.run_sensor_test(obs_noise or (1.0,), obs_bias or (0.0,), obs_delay_s, num_steps=eval_steps,
                                                    graph=graph, trace_depth=depth, gait=gait, joints=joints, contacts=contacts))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_sensors.json")
+    elif force_n:
+        report = dict(**head, **ev.run_force_test(force_n, directions=force_dirs, at_s=force_at_s, for_s=force_for_s,
+                                                  point=force_point or (0.0, 0.0, 0.0), command=force_cmd or (0.5, 0.0, 0.0),
+                                                  num_steps=eval_steps, graph=graph, trace_depth=depth, gait=gait,
+                                                  joints=joints, contacts=contacts))
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_force.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
                                       trace_depth=depth, gait=gait, joints=joints, contacts=contacts)
@@ -198,6 +223,10 @@ def _each_place(report, line):
             for s, row in enumerate(rep["bins"]):
                 for d, cell in enumerate(row):
                     line(f"{tag}push {rep['speeds'][s]:g} m/s from {rep['directions_deg'][d]:g} deg", cell)
+        elif "forces_n" in rep:  # the force test
+            for f, row in enumerate(rep["bins"]):
+                for d, cell in enumerate(row):
+                    line(f"{tag}force {rep['forces_n'][f]:g} N from {rep['directions_deg'][d]:g} deg", cell)
         elif "delay_steps" in rep:  # the sensor test
             for i, a in enumerate(rep["bins"]):
                 for j, b in enumerate(a):
@@ -271,6 +300,12 @@ def main(argv=None):
     p.add_argument("--obs_noise", type=floats, default=None)
     p.add_argument("--obs_bias", type=floats, default=None)
     p.add_argument("--obs_delay_ms", type=floats, default=None)
+    p.add_argument("--force_n", type=floats, default=None)
+    p.add_argument("--force_dirs", type=int, default=8)
+    p.add_argument("--force_at_s", type=float, default=2.0)
+    p.add_argument("--force_for_s", type=float, default=None)
+    p.add_argument("--force_point", type=floats, default=None)
+    p.add_argument("--force_cmd", type=floats, default=None)
     p.add_argument("--trace_falls", type=int, default=None)
     p.add_argument("--trace_s", type=float, default=2.0)
     p.add_argument("--gait", action="store_true")
@@ -284,7 +319,9 @@ def main(argv=None):
                          cmd_vx=own.cmd_vx, cmd_vy=own.cmd_vy, cmd_yaw=own.cmd_yaw, cmd_at_s=own.cmd_at_s,
                          cmd_start=own.cmd_start, trace_falls=own.trace_falls, trace_s=own.trace_s,
                          gait=own.gait, joints=own.joints, contacts=own.contacts, obs_noise=own.obs_noise,
-                         obs_bias=own.obs_bias, obs_delay_ms=own.obs_delay_ms)
+                         obs_bias=own.obs_bias, obs_delay_ms=own.obs_delay_ms, force_n=own.force_n,
+                         force_dirs=own.force_dirs, force_at_s=own.force_at_s, force_for_s=own.force_for_s,
+                         force_point=own.force_point, force_cmd=own.force_cmd)
     for ln in (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []) + \
             (contact_summary(report) if own.contacts else []):
         print(ln)

@@ -38,6 +38,7 @@ def play(args, num_steps=None, root=None):
     env_cfg.domain_rand.randomize_obs_noise_scale = False
     env_cfg.domain_rand.randomize_obs_bias = False
     env_cfg.domain_rand.randomize_obs_delay = False
+    env_cfg.domain_rand.randomize_external_force = False
     env_cfg.domain_rand.push_robots = False
     env_cfg.commands.zero_command = False
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)

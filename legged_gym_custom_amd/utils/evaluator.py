@@ -124,6 +124,22 @@ def command_cell_report(ccell, dt, command):
 
 
 # lgx_gait_record's body pairs (columns 6..11), in order
+def force_cell_report(ccell, dt, command, force_n, theta, steady):
+    """The force-test entries of one command cell row [9] (command_cell_report's columns; the
+    onset is the record's switch step) for the bin's force (force_n newtons at angle theta from
+    forward towards left) under the held command (vx, vy, yaw). steady: the force lasts to the end
+    of the episode, so the steady window holds forced samples only; otherwise achieved, deflection
+    and compliance are None. Means without data are None."""
+    r = command_cell_report(ccell, dt, command)
+    achieved = r["achieved"] if steady else None
+    deflection = [a - c for a, c in zip(achieved, command)] if achieved is not None else None
+    compliance = ((deflection[0] * math.cos(theta) + deflection[1] * math.sin(theta)) / force_n
+                  if deflection is not None and force_n > 0 else None)
+    return {"forced": r["switched"], "survivors": r["survivors"], "mean_peak_tilt_rad": r["mean_peak_tilt_rad"],
+            "mean_settle_s": r["mean_settle_s"], "achieved": achieved, "deflection": deflection,
+            "compliance_m_per_s_per_n": compliance}
+
+
 GAIT_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
 _FOOT_PLACES = {"FL": (0, 0), "FR": (0, 1), "RL": (1, 0), "RR": (1, 1),   # (front 0 / hind 1, left 0 / right 1)
                 "LF": (0, 0), "RF": (0, 1), "LH": (1, 0), "RH": (1, 1)}
@@ -414,6 +430,8 @@ class PolicyEvaluator:
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
         self._sensor_graph = self._sensor_graph_key = None  # run_sensor_test's own captured loop
+        self._force_graph = self._force_graph_key = None  # run_force_test's own captured loop
+        self.last_force_cells = self.last_force_bins = None
         self.last_sensor_bins = None
         self._fused = None
         self.last_cells = None
@@ -444,7 +462,7 @@ class PolicyEvaluator:
         """Re-pack the fused act kernel's weights (after the runner loaded or trained them)."""
         if self._fused is not None:
             self._fused.refresh_weights()
-            self._graph = self._push_graph = self._cmd_graph = self._sensor_graph = None
+            self._graph = self._push_graph = self._cmd_graph = self._sensor_graph = self._force_graph = None
 
     # ------------------------------------------------------------------ one iteration
     def act(self):
@@ -589,8 +607,8 @@ class PolicyEvaluator:
                 buf.copy_(old)
 
     def _drive(self, slot, key, num_steps, graph, read_cells, prepare=None, started=None, cleanup=None):
-        """The run of all four modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
-        "_cmd_graph", "_sensor_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
+        """The run of all five modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
+        "_cmd_graph", "_sensor_graph", "_force_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
         the trace depth and the gait, joints and contacts flags are added: the loop is captured when
         there is no graph or the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
         buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
@@ -652,6 +670,14 @@ class PolicyEvaluator:
         if not 0 < step < last:
             raise ValueError(f"{test}: at_s = {at_s} s is step {step}, outside 0 < step < max_episode_length = {last}")
         return step
+
+    def _cmd_eval(self, key, other):
+        """env.cmd_eval_buffers(*key), which the command test and the force test share: the env
+        allocates them anew when the key changes, so the captured loop of the other mode (slot
+        `other`), which records into the old ones, is dropped then."""
+        if getattr(self.env, "_cmd_eval_key", None) != key:
+            setattr(self, other, None)
+        return self.env.cmd_eval_buffers(*key)
 
     def _bins(self, count):
         """Each env's bin of `count`: randperm(num_envs, seeded with env.seed) % count."""
@@ -816,7 +842,7 @@ class PolicyEvaluator:
         def prepare():
             # before begin: its reset sees segment 0 (the first call allocates: refused once a loop is captured)
             env.set_command_schedule([0, step], values)
-            ev = env.cmd_eval_buffers(*key)
+            ev = self._cmd_eval(key, "_force_graph")
             env.cmd_cell_ids.copy_(bins.to(torch.int32))
             env.cmd_switch_step.fill_(step)
             self._record_buffers(nx, ny * nw, env.cmd_cell_ids)  # the bin is the cell key
@@ -835,6 +861,99 @@ class PolicyEvaluator:
                "bins": [[[both(cells[ix, iy * nw + iw], ccells[ix, iy * nw + iw], (vx[ix], vy[iy], yaw[iw]))
                           for iw in range(nw)] for iy in range(ny)] for ix in range(nx)], **rates}
         self._attach_records(total, [b for plane in out["bins"] for row in plane for b in row])
+        return out
+
+    # ------------------------------------------------------------------ external force
+    def run_force_test(self, forces, directions=8, at_s=2.0, for_s=None, point=(0.0, 0.0, 0.0), command=(0.5, 0.0, 0.0),
+                       steady_after_s=1.0, settle_tol=0.3, yaw_tol=0.3, num_steps=None, graph=True, trace_depth=None,
+                       gait=False, joints=False, contacts=False):
+        """How many newtons from which side does the policy hold its course against, and how far
+        does it get deflected: one run in which every env holds `command` = (vx, vy, yaw rate)
+        through the command schedule (one segment from step 0, so a reset env holds it again) and,
+        from episode step round(at_s / dt) on, takes the sustained external force of its bin on its
+        base (include/lgx.h ABI 16; force index f, direction index d): forces[f] * (cos t, sin t, 0)
+        N with t = 2 pi d / directions from the robot's forward axis towards its left, at `point`
+        (m, base link frame), for round(for_s / dt) steps (None: to the end of the episode). Envs
+        get bins by randperm(num_envs, seeded with env.seed) % (F * D). Force 0 gives the control
+        row.
+
+        The per-env record is the step-response record of the command test with the onset as its
+        switch step (env.cmd_eval_buffers: the bin is the cell key; no record kernel of its own),
+        and this mode's captured loop is a graph of its own. The env needs the command schedule and
+        the force buffers before any of its steps is captured (commands.scheduled_commands and
+        domain_rand.scheduled_forces = True, or call this before run()). Both schedules are cleared
+        in place when the run ends, so a following run() is the plain one.
+
+        trace_depth, gait, joints, contacts: as in run(), the records per bin.
+
+        Returns the report: "bins"[f][d] with the REPORT_KEYS entries and forced (finished envs
+        with samples after the onset), survivors (timed out among them), mean_peak_tilt_rad,
+        mean_settle_s (the survivors' mean time from the onset until the tracking error stays within
+        settle_tol; 0: never off), achieved [vx, vy, yaw] (the survivors' mean velocities over the
+        samples from steady_after_s after the onset on), deflection (achieved minus command) and
+        compliance_m_per_s_per_n (the deflection projected on the force direction, over the force;
+        None at force 0); achieved, deflection and compliance are None when for_s is given (the
+        steady window would mix forced and free samples). "total" likewise without deflection and
+        compliance; forces_n, directions_deg, onset_step, force_steps (None: to the end), point,
+        command, steady_after, the tolerances. None where there is no data, never NaN.
+        ValueError: no forces or directions, a negative or non-finite force, a non-finite point or
+        command, an onset outside 0 < step < max_episode_length, a for_s shorter than one step, a
+        negative or non-finite tolerance or steady_after_s."""
+        env = self.env
+        self._set_trace(trace_depth, gait, joints, contacts)
+        forces, point, command = ([float(v) for v in lst] for lst in (forces, point, command))
+        F, D = len(forces), int(directions)
+        if F < 1 or D < 1 or not all(math.isfinite(v) and v >= 0.0 for v in forces):
+            raise ValueError(f"force test: need at least one finite force >= 0 and one direction (got {forces}, {directions})")
+        if len(point) != 3 or len(command) != 3 or not all(math.isfinite(v) for v in point + command):
+            raise ValueError(f"force test: point and command need three finite entries each (got {point}, {command})")
+        for name, tol in (("settle_tol", settle_tol), ("yaw_tol", yaw_tol), ("steady_after_s", steady_after_s)):
+            if not (math.isfinite(float(tol)) and float(tol) >= 0.0):
+                raise ValueError(f"force test: {name} must be finite and >= 0 (got {tol})")
+        dt, step = float(env.dt), self._switch_step(at_s, "force test")
+        fsteps = None
+        if for_s is not None:
+            fsteps = int(round(float(for_s) / dt)) if math.isfinite(float(for_s)) else 0
+            if fsteps < 1:
+                raise ValueError(f"force test: for_s = {for_s} s is shorter than one control step")
+        steady = int(round(float(steady_after_s) / dt))
+        n = env.num_envs
+        bins = self._bins(F * D)
+        theta = 2.0 * math.pi * (bins % D).double() / D
+        mag = torch.tensor(forces, dtype=torch.float64)[bins // D]
+        fvec = torch.stack([mag * torch.cos(theta), mag * torch.sin(theta), torch.zeros_like(mag)], 1).float()
+        values = torch.tensor(command + [0.0], dtype=torch.float32).expand(n, 1, 4)
+        key = (F, D, float(settle_tol), float(yaw_tol), steady)
+
+        def prepare():
+            # before begin: its reset sees the command segment; the force starts after begin, whose
+            # reset ends with an env step of its own (the first calls allocate: refused once a loop is captured)
+            env.set_command_schedule([0], values)
+            env.set_force_schedule(0, fvec, steps=fsteps, point=point)
+            ev = self._cmd_eval(key, "_cmd_graph")
+            env.cmd_cell_ids.copy_(bins.to(torch.int32))
+            env.cmd_switch_step.fill_(step)
+            self._record_buffers(F, D, env.cmd_cell_ids)  # the bin is the cell key
+            return ev
+
+        def cleanup():
+            env.clear_command_schedule()
+            env.clear_force_schedule()
+
+        (cells, ccells), head, rates = self._drive(
+            "_force_graph", key, num_steps, graph, env.eval_command_cells, prepare,
+            lambda: env.set_force_schedule(step, fvec, steps=fsteps, point=point), cleanup)
+        self.last_force_cells, self.last_force_bins = ccells, bins
+        w = self.mass * self.gravity
+        both = lambda c, p, f, t: {**cell_report(c, dt, w), **force_cell_report(p, dt, command, f, t, fsteps is None)}  # noqa: E731
+        total = both(cells.reshape(-1, cells.shape[2]).sum(0), ccells.reshape(-1, ccells.shape[2]).sum(0), 0.0, 0.0)
+        del total["deflection"], total["compliance_m_per_s_per_n"]  # (means over different forces say nothing)
+        out = {**head, "forces_n": forces, "directions_deg": [360.0 * d / D for d in range(D)], "onset_step": step,
+               "onset_at_s": step * dt, "force_steps": fsteps, "point": point, "command": command,
+               "steady_after": steady, "settle_tol": float(settle_tol), "yaw_tol": float(yaw_tol), "total": total,
+               "bins": [[both(cells[f, d], ccells[f, d], forces[f], 2.0 * math.pi * d / D) for d in range(D)]
+                        for f in range(F)], **rates}
+        self._attach_records(total, [b for row in out["bins"] for b in row])
         return out
 
     # ------------------------------------------------------------------ sensor model

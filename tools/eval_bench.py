@@ -3,6 +3,7 @@ networks (the timing does not depend on the weights), graph replay and the eager
 
   python tools/eval_bench.py [--task go2] [--num_envs 4096] [--steps N] [--repeats 3] [--out FILE]
   python tools/eval_bench.py --push_vel 0,0.5,1.0,1.5 [--push_dirs 8] ...   # + the push test (run_push_test)
+  python tools/eval_bench.py --force_n 0,20,40,80 [--force_dirs 8] ...   # + the force test (run_force_test)
   python tools/eval_bench.py --trace_depth 100 ...   # + the plain run with the flight recorder on, and traces()
   python tools/eval_bench.py --gait ...   # + the plain run with the gait record on (run(gait=True))
   python tools/eval_bench.py --joints ...   # + the plain run with the joint-load record on (run(joints=True))
@@ -60,6 +61,10 @@ def main():
                         "scheduled_commands; not with --push_vel)")
     p.add_argument("--cmd_vy", type=lambda s: [float(v) for v in s.split(",")], default=[0.0])
     p.add_argument("--cmd_yaw", type=lambda s: [float(v) for v in s.split(",")], default=[0.0])
+    p.add_argument("--force_n", type=lambda s: [float(v) for v in s.split(",")], default=None,
+                   help="also time run_force_test with these forces (the env is built with scheduled_commands and "
+                        "scheduled_forces; not with --push_vel or --cmd_vx)")
+    p.add_argument("--force_dirs", type=int, default=8)
     p.add_argument("--trace_depth", type=int, default=None,
                    help="also time run(trace_depth=K), the flight recorder, and traces('falls', 16) after it")
     p.add_argument("--gait", action="store_true", help="also time run(gait=True), the gait record")
@@ -70,7 +75,7 @@ def main():
     p.add_argument("--merge")
     p.add_argument("--out")
     a = p.parse_args()
-    assert not (a.push_vel and a.cmd_vx), "--push_vel or --cmd_vx, one at a time"
+    assert sum(bool(v) for v in (a.push_vel, a.cmd_vx, a.force_n)) <= 1, "--push_vel, --cmd_vx or --force_n, one at a time"
     if a.stats:
         return merge_stats(a.stats, a.merge)
     import torch
@@ -85,6 +90,8 @@ def main():
         cfg.domain_rand.scheduled_pushes = True  # buffers bound with no env scheduled: the plain run's step is unchanged
     if a.cmd_vx:
         cfg.commands.scheduled_commands = True  # likewise: bound, every entry unused
+    if a.force_n:
+        cfg.commands.scheduled_commands = cfg.domain_rand.scheduled_forces = True  # likewise: bound, nothing scheduled
     args = get_args([f"--task={a.task}", "--headless", f"--num_envs={a.num_envs}", "--seed=1",
                      f"--sim_device={a.device}", f"--rl_device={a.device}"])
     env, _ = task_registry.make_env(a.task, args, env_cfg=cfg)
@@ -111,6 +118,8 @@ def main():
     if a.cmd_vx:
         add("cmd", lambda steps, graph: ev.run_command_test(a.cmd_vx, vy=a.cmd_vy, yaw=a.cmd_yaw, num_steps=steps,
                                                             graph=graph))
+    if a.force_n:
+        add("force", lambda steps, graph: ev.run_force_test(a.force_n, directions=a.force_dirs, num_steps=steps, graph=graph))
     records = [flag for flag in ("gait", "joints", "contacts") if getattr(a, flag)]  # flag = mode prefix = report key
     for flag in records:
         add(flag, lambda steps, graph, flag=flag: ev.run(steps, graph, **{flag: True}))
@@ -139,7 +148,7 @@ def main():
                      # count / status / reset flags) in, one 304-byte row and the count out
                      "record_bytes_in_per_step": n * (8 + 69 * 4 + env.num_bodies * 12 + 4 + 1 + 1),
                      "record_bytes_out_per_step": n * (304 + 4)}
-    pr, cr = last.get("push"), last.get("cmd")
+    pr, cr, fr = last.get("push"), last.get("cmd"), last.get("force")
     r = ev.run(a.steps) if len(runs) > 1 else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
@@ -172,6 +181,13 @@ def main():
              "survivors": sum(c["survivors"] for r_ in row for c in r_),
              "switched": sum(c["switched"] for r_ in row for c in r_),
              "gain": [[c["gain"] for c in r_] for r_ in row]} for v, row in zip(cr["vx"], cr["bins"])]
+    if fr:
+        doc["force_test"] = {k: fr[k] for k in ("forces_n", "directions_deg", "onset_step", "force_steps", "point", "command",
+                                                "steady_after", "settle_tol", "yaw_tol", "total")}
+        doc["force_test"]["per_force"] = [
+            {"force_n": v, "episodes": sum(c["episodes"] for c in row), "survivors": sum(c["survivors"] for c in row),
+             "forced": sum(c["forced"] for c in row),
+             "compliance_m_per_s_per_n": [c["compliance_m_per_s_per_n"] for c in row]} for v, row in zip(fr["forces_n"], fr["bins"])]
     print(json.dumps(doc))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
