@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define LGX_ABI_VERSION 16
+#define LGX_ABI_VERSION 17
 
 #define LGX_MAX_DOF 12
 #define LGX_MAX_LINKS 16          /* dynamic links: base + 12 leg links (+spare) */
@@ -49,6 +49,7 @@ extern "C" {
 #define LGX_EVAL_CELL_COLS 12     /* per-cell output columns (lgx_eval_buffers.cells) */
 #define LGX_MAX_ACTION_HISTORY 4  /* control steps of actuation latency (action_history rows) */
 #define LGX_MAX_SENSOR_HISTORY 4  /* control steps of sensing latency (sensor_history rows) */
+#define LGX_SCAN_STREAM 3         /* Philox stream of the height-scan model (0 step, 1 reset, 2 act noise) */
 #define LGX_EVAL_PUSH_REC 4       /* per-env push-recovery record columns (lgx_eval_buffers.push_rec) */
 #define LGX_EVAL_PUSH_COLS 5      /* per-cell push-recovery columns (lgx_eval_buffers.push_cells) */
 #define LGX_CMD_SEGMENTS 4        /* segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val) */
@@ -453,6 +454,43 @@ typedef struct lgx_buffers {
      time: writing them between steps needs no re-bind. */
   const int32_t* force_window; /* [N,3] start, steps, period (episode steps) */
   const float* force_vec;      /* [N,6] forward, left, up in N; application point x, y, z in m, base link frame */
+  /* Height-scan model (ABI v17; the reference feeds the policy the clean scan). All five optional;
+     all NULL = the step of ABI 16, bit for bit. The model acts on the Go2 task kind's scan[e][i]
+     only (S = params.num_scan points), where the step forms it. The critic's copy of the scan is
+     privileged and stays clean, and so do measured_heights, the height reward sums, priv, est, obs
+     and the rewards.
+     Raw value: raw[i] = clip(root_z - 0.3 - h_i, -1, 1). With scan_offset unbound, or (dx, dy) =
+     scan_offset[e][0..1] both exactly 0, h_i is the height the step staged for point i (the bits
+     of the unbound step). Otherwise h_i is a second terrain lookup at the base-frame point
+     (height_points[i][0] + dx, height_points[i][1] + dy), each sum one fp32 add, and from there
+     the arithmetic of the step's own height scan on the root pose that scan used (the pose before
+     an in-step reset): yaw-only quaternion, border, truncation, clamp, min of three samples. On a
+     plane, or with no height_samples, the height is 0 as in the unbound step.
+     Latency: K = params.sensor_history_len and c = sensor_count[e] as the proprio pass found it
+     (0 for an env this step reset), d = min(clamp(scan_delay[e], 0, K), c). With d > 0 point i
+     uses scan_history[e][(c - d) % K][i], the raw value of d steps ago in the same episode; then
+     raw[i] is written to row c % K (one lane reads and then overwrites its own column, so d = K
+     needs no (K+1)-th row). The count is the proprio ring's: the step increments it once,
+     whichever of the two rings is bound, and every reset empties both rings by setting it to 0.
+     Noise: with amp = scan_noise[e] != 0, v = v + (2u - 1) * amp (the product rounded, then the
+     sum). u is slot i of a Philox stream of its own, LGX_SCAN_STREAM, with the env step's counter
+     layout (global env id, step, block | stream << 16; block = slot >> 2, word = slot & 3). No
+     draw of the other streams moves.
+     Vertical offset: dz = scan_offset[e][2] != 0 is added as a rounding of its own.
+     Dropout: with p = scan_dropout[e][0] > 0 point i is lost iff u' < p, u' slot
+     LGX_MAX_HEIGHT_POINTS + i of the same stream; a lost point reads scan_dropout[e][1] exactly
+     (1.0: "no return, far").
+     Order: delayed raw, noise, dz, dropout, then clip(., -1, 1). The clip is the identity on an
+     untouched value, so an env whose rows are all neutral keeps the bits of the unbound step.
+     lgx_bind refuses any of the five when num_scan = 0 or the task kind is not Go2, scan_delay
+     without scan_history and sensor_count or with K = 0, and scan_history without sensor_count or
+     with K = 0 (sensor_count alone needs one of the two rings). The step reads the four inputs at
+     kernel time: writing them between steps needs no re-bind. */
+  const float* scan_noise;     /* [N]     amplitude in m of uniform noise per point and step            */
+  const float* scan_dropout;   /* [N,2]   probability that a point is lost in a step; the value it reads */
+  const float* scan_offset;    /* [N,3]   map misregistration: dx, dy (m, robot yaw frame), dz (m)      */
+  const int32_t* scan_delay;   /* [N]     latency of env e's scan in control steps                      */
+  float* scan_history;         /* [N,K,S] state: the last K raw scan rows of the current episode        */
 } lgx_buffers;
 
 typedef struct lgx_env lgx_env;

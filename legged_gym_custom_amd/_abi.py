@@ -7,7 +7,7 @@ loaded library (`_native.lib()`; the oracle through `check_layout()`) reports it
 """
 import ctypes as C
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 MAX_DOF = 12
 MAX_LINKS = 16
 MAX_BODIES = 24
@@ -23,6 +23,7 @@ EVAL_METRICS = 8     # per-env record columns (lgx_eval_buffers.acc)
 EVAL_CELL_COLS = 12  # per-cell output columns (lgx_eval_buffers.cells)
 MAX_ACTION_HISTORY = 4  # control steps of actuation latency (rows of lgx_buffers.action_history)
 MAX_SENSOR_HISTORY = 4  # control steps of sensing latency (rows of lgx_buffers.sensor_history)
+SCAN_STREAM = 3         # Philox stream of the height-scan model
 EVAL_PUSH_REC = 4    # per-env push-recovery record columns (lgx_eval_buffers.push_rec)
 EVAL_PUSH_COLS = 5   # per-cell push-recovery columns (lgx_eval_buffers.push_cells)
 CMD_SEGMENTS = 4     # segments of an env's command schedule (lgx_buffers.cmd_step / cmd_val)
@@ -155,6 +156,7 @@ class Buffers(C.Structure):
         "action_delay", "action_history", "motor_strength", "push_step", "push_dvel", "cmd_step", "cmd_val",
         "obs_noise_scale", "obs_bias", "obs_delay", "sensor_history", "sensor_count",
         "force_window", "force_vec",
+        "scan_noise", "scan_dropout", "scan_offset", "scan_delay", "scan_history",
     ]]
 
 
@@ -213,7 +215,7 @@ CONSTANTS = {
     "LGX_MAX_HEIGHT_POINTS": MAX_HEIGHT_POINTS, "LGX_MAX_REWARDS": MAX_REWARDS,
     "LGX_MAX_CANDIDATES": MAX_CANDIDATES, "LGX_MAX_CONTACTS": MAX_CONTACTS, "LGX_MAX_PENALISED": MAX_PENALISED,
     "LGX_MAX_TERMINATION": MAX_TERMINATION, "LGX_EVAL_METRICS": EVAL_METRICS, "LGX_EVAL_CELL_COLS": EVAL_CELL_COLS,
-    "LGX_MAX_ACTION_HISTORY": MAX_ACTION_HISTORY, "LGX_MAX_SENSOR_HISTORY": MAX_SENSOR_HISTORY,
+    "LGX_MAX_ACTION_HISTORY": MAX_ACTION_HISTORY, "LGX_MAX_SENSOR_HISTORY": MAX_SENSOR_HISTORY, "LGX_SCAN_STREAM": SCAN_STREAM,
     "LGX_EVAL_PUSH_REC": EVAL_PUSH_REC, "LGX_EVAL_PUSH_COLS": EVAL_PUSH_COLS,
     "LGX_CMD_SEGMENTS": CMD_SEGMENTS, "LGX_EVAL_CMD_REC": EVAL_CMD_REC, "LGX_EVAL_CMD_COLS": EVAL_CMD_COLS,
     "LGX_TRACE_COLS": TRACE_COLS,

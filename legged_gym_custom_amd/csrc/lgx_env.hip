@@ -1511,24 +1511,11 @@ LGX_DEV void get_heights(const lgx_task_params* Pm, const lgx_buffers& B, Sh& s,
     for (int i = lane; i < NP; i += WL) stg_heights(A, Pm)[i] = 0.0f;
     return;
   }
-  float qz = root[5], qw = root[6];
-  float n = sqrtf(qz * qz + qw * qw);
-  n = n < 1e-9f ? 1e-9f : n;
-  float qy[4] = {0.f, 0.f, qz / n, qw / n};
-  for (int i = lane; i < NP; i += WL) {
-    float p[3] = {Pm->height_points[i][0], Pm->height_points[i][1], 0.f}, w[3];
-    quat_apply(qy, p, w);
-    float px = (w[0] + root[0]) + Pm->border_size, py = (w[1] + root[1]) + Pm->border_size;
-    long ix = (long)(px / Pm->horizontal_scale), iy = (long)(py / Pm->horizontal_scale);
-    ix = ix < 0 ? 0 : (ix > Pm->hf_rows - 2 ? Pm->hf_rows - 2 : ix);
-    iy = iy < 0 ? 0 : (iy > Pm->hf_cols - 2 ? Pm->hf_cols - 2 : iy);
-    int16_t h1 = B.height_samples[ix * Pm->hf_cols + iy];
-    int16_t h2 = B.height_samples[(ix + 1) * Pm->hf_cols + iy];
-    int16_t h3 = B.height_samples[ix * Pm->hf_cols + iy + 1];
-    int16_t h = h1 < h2 ? h1 : h2;
-    h = h < h3 ? h : h3;
-    stg_heights(A, Pm)[i] = (float)h * Pm->vertical_scale;
-  }
+  float qy[4];
+  scan_yaw_quat(root[5], root[6], qy);
+  for (int i = lane; i < NP; i += WL)
+    stg_heights(A, Pm)[i] = scan_point_height(Pm, B.height_samples, qy, root, Pm->height_points[i][0],
+                                              Pm->height_points[i][1]);
 }
 
 // ============================================================== kernels
@@ -1876,6 +1863,16 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
   }
   __syncthreads();
   PH(14);
+  // scan model (include/lgx.h, ABI 17), SENSOR instances: the second lookup of an env with a map
+  // offset uses the pose the height scan above used, which a reset replaces. (Like get_heights it
+  // asks the mesh type at run time: lgx_post_physics runs a terrain on a TERRAIN = false instance.)
+  float scan_pose[4] = {0.f, 0.f, 0.f, 1.f};
+  if constexpr (SENSOR) {
+    if (B.scan_offset) {
+      scan_pose[0] = s.root[0]; scan_pose[1] = s.root[1];
+      scan_pose[2] = s.root[5]; scan_pose[3] = s.root[6];
+    }
+  }
   // reset_idx (go2.py:207-263)
   if (reset) reset_env<WL>(Pm, B, s, AR, e, lane, true, false, true);
 
@@ -1925,6 +1922,7 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
   // row. No LDS beyond the staged row. Count and latency are per env: every lane of the env loads
   // the same word (a vector load; at two envs per wave uniform over a half-wave only). An env this
   // step reset starts at count 0, so its latency clamps to 0 and the count needs no zeroing here.
+  int scan_c = 0;  // the scan model's copy of the count (ABI 17; the rings share it)
   if constexpr (SENSOR) {
     // rows of this episode in the ring (0 for an env this step reset) and the env's clamped latency
     int sens_c = 0, sens_d = 0;
@@ -1947,6 +1945,7 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
       stg_cur(AR, Pm)[i] = v;
     }
     if (B.sensor_count && lane == 0) B.sensor_count[e] = sens_c + 1;
+    scan_c = sens_c;
   }
   // stage the old history (obs[0:H*P]) in LDS; a reset env's history was zeroed (go2.py:238)
   float* hist_g = B.obs_history + (size_t)e * H * Pp;
@@ -2016,10 +2015,53 @@ __global__ __launch_bounds__(64, ACTNET ? LGX_SEA_WAVES : (EPW == 2 ? 2 : 4)) vo
       B.est[(size_t)e * Pm->num_est + lane] = v;
       if (cr) cr[NO + Pm->num_priv + lane] = v;
     }
-    for (int i = lane; i < Pm->num_scan; i += WL) {
-      float v = clipf(s.root[2] - 0.3f - stg_heights(AR, Pm)[i], -1.0f, 1.0f);
-      B.scan[(size_t)e * Pm->num_scan + i] = v;
-      if (cr) cr[NO + Pm->num_priv + 3 + i] = clipf(v, -co, co);
+    if constexpr (!SENSOR) {
+      for (int i = lane; i < Pm->num_scan; i += WL) {
+        float v = clipf(s.root[2] - 0.3f - stg_heights(AR, Pm)[i], -1.0f, 1.0f);
+        B.scan[(size_t)e * Pm->num_scan + i] = v;
+        if (cr) cr[NO + Pm->num_priv + 3 + i] = clipf(v, -co, co);
+      }
+    } else {
+      // Height-scan model (include/lgx.h, ABI 17): per point the raw value (from a second terrain
+      // lookup for an env whose map is shifted in xy), the latency through the env's ring in
+      // global memory, then scan_point_model. The critic's copy stays the clean value. Lane i has
+      // points i, i + WL, ...: ring traffic is consecutive lanes on consecutive words of a row, and
+      // each lane reads and then overwrites its own column. No LDS beyond the staged heights. The
+      // env's four rows are the same word for every lane of the env (vector loads). A lane
+      // recomputes the Philox block of its point (the four lanes of a block would otherwise
+      // exchange it across a divergent branch); an env without noise and dropout draws nothing.
+      const int S = Pm->num_scan;
+      const float amp = B.scan_noise ? B.scan_noise[e] : 0.f;
+      const float drop_p = B.scan_dropout ? B.scan_dropout[(size_t)e * 2] : 0.f;
+      const float fill = B.scan_dropout ? B.scan_dropout[(size_t)e * 2 + 1] : 0.f;
+      float dx = 0.f, dy = 0.f, dz = 0.f;
+      if (B.scan_offset) {
+        dx = B.scan_offset[(size_t)e * 3];
+        dy = B.scan_offset[(size_t)e * 3 + 1];
+        dz = B.scan_offset[(size_t)e * 3 + 2];
+      }
+      const bool second = (dx != 0.f || dy != 0.f) && Pm->mesh_type != LGX_MESH_PLANE && B.height_samples != nullptr;
+      float qy[4] = {0.f, 0.f, 0.f, 1.f};
+      if (second) scan_yaw_quat(scan_pose[2], scan_pose[3], qy);
+      const int SK = Pm->sensor_history_len;
+      const int scan_d = B.scan_delay ? sensor_delay_clamp(B.scan_delay[e], SK, scan_c) : 0;
+      for (int i = lane; i < S; i += WL) {
+        const float clean = scan_raw(s.root[2], stg_heights(AR, Pm)[i]);
+        float raw = clean;
+        if (second)
+          raw = scan_raw(s.root[2], scan_point_height(Pm, B.height_samples, qy, scan_pose, Pm->height_points[i][0] + dx,
+                                                      Pm->height_points[i][1] + dy));
+        float v = raw;
+        if (B.scan_history) {
+          float* ring = B.scan_history + (size_t)e * SK * S;
+          if (scan_d > 0) v = ring[(size_t)sensor_ring_read_row(scan_c, scan_d, SK) * S + i];
+          ring[(size_t)sensor_ring_write_row(scan_c, SK) * S + i] = raw;
+        }
+        const float u = amp != 0.f ? scan_uniform(seed, gid, step, i) : 0.f;
+        const float ud = drop_p > 0.f ? scan_uniform(seed, gid, step, LGX_MAX_HEIGHT_POINTS + i) : 0.f;
+        B.scan[(size_t)e * S + i] = scan_point_model(v, amp, u, dz, drop_p, ud, fill);
+        if (cr) cr[NO + Pm->num_priv + 3 + i] = clipf(clean, -co, co);
+      }
     }
   }
   // history update go2.py:570-574 (the long-history path wrote it above)
@@ -2242,7 +2284,16 @@ int lgx_bind(lgx_env* env, const lgx_buffers* b) {
   if (b->obs_delay && (!b->sensor_history || !b->sensor_count || env->params.sensor_history_len <= 0))
     return fail(env, "lgx_bind: obs_delay needs sensor_history, sensor_count and params.sensor_history_len > 0");
   if (b->sensor_history && !b->sensor_count) return fail(env, "lgx_bind: sensor_history needs sensor_count");
-  if (b->sensor_count && !b->sensor_history) return fail(env, "lgx_bind: sensor_count needs sensor_history");
+  if (b->sensor_count && !b->sensor_history && !b->scan_history)
+    return fail(env, "lgx_bind: sensor_count needs sensor_history or scan_history");
+  if ((b->scan_noise || b->scan_dropout || b->scan_offset || b->scan_delay || b->scan_history) &&
+      (env->params.task_kind != LGX_TASK_GO2 || env->params.num_scan <= 0))
+    return fail(env, "lgx_bind: the scan model needs the Go2 task kind and params.num_scan > 0");
+  if (b->scan_delay && (!b->scan_history || !b->sensor_count || env->params.sensor_history_len <= 0))
+    return fail(env, "lgx_bind: scan_delay needs scan_history, sensor_count and params.sensor_history_len > 0");
+  if (b->scan_history && !b->sensor_count) return fail(env, "lgx_bind: scan_history needs sensor_count");
+  if (b->scan_history && env->params.sensor_history_len <= 0)
+    return fail(env, "lgx_bind: scan_history with params.sensor_history_len = 0");
   if (b->sensor_history && env->params.sensor_history_len <= 0)
     return fail(env, "lgx_bind: sensor_history with params.sensor_history_len = 0");
   if (b->force_window && !b->force_vec) return fail(env, "lgx_bind: force_window without force_vec");
@@ -2299,7 +2350,9 @@ static int launch_step(lgx_env* env, uint64_t seed, uint64_t step, const uint64_
   // the sensor model's code lives in instances of its own (SENSOR), chosen from the bound pointers:
   // with none of them bound the step runs the code it ran before ABI 15
   const lgx_buffers& hb = env->buffers;
-  const bool sensor = hb.obs_noise_scale || hb.obs_bias || hb.sensor_history;
+  // (the scan model of ABI 17 lives in the same instances)
+  const bool sensor = hb.obs_noise_scale || hb.obs_bias || hb.sensor_history || hb.scan_noise || hb.scan_dropout ||
+                      hb.scan_offset || hb.scan_delay || hb.scan_history;
   // and so does the external force's (FORCE; it acts in the physics: the other instances have none)
   const bool force = hb.force_window != nullptr;
 #define LGX_STEP_KERNEL(SENSOR, FORCE)                                                                       \

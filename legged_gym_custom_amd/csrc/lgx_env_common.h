@@ -515,14 +515,12 @@ LGX_HD void joint_body_sample(float* b, float P, bool sat, bool out) {
   b[3] += out ? 1.0f : 0.f;
 }
 
-// Contact record (lgx_contact_buffers, include/lgx.h ABI 14). The terrain height under (x, y): the
-// index arithmetic of the step's height scan (get_heights), every index clamped before use; ix, iy:
-// the clamped cell, for contact_relief. hs == nullptr (a plane): 0.
-LGX_HD float contact_terrain_height(const lgx_task_params* Pm, const int16_t* hs, float x, float y, long& ix,
-                                    long& iy) {
-  ix = iy = 0;
-  if (hs == nullptr) return 0.f;
-  const float px = x + Pm->border_size, py = y + Pm->border_size;
+// The terrain height in the cell of the point (px, py), world coordinates plus the border,
+// LeggedRobot._get_heights legged_robot.py:1015-1032: truncation, every index clamped before use, the
+// min of three samples, one float multiply. ix, iy: the clamped cell. hs: height_samples, not NULL.
+// The step's height scan, the contact record and the scan model's second lookup (include/lgx.h,
+// ABI 17) all go through this.
+LGX_HD float terrain_cell_height(const lgx_task_params* Pm, const int16_t* hs, float px, float py, long& ix, long& iy) {
   ix = (long)(px / Pm->horizontal_scale);
   iy = (long)(py / Pm->horizontal_scale);
   ix = ix < 0 ? 0 : (ix > Pm->hf_rows - 2 ? Pm->hf_rows - 2 : ix);
@@ -533,6 +531,33 @@ LGX_HD float contact_terrain_height(const lgx_task_params* Pm, const int16_t* hs
   int16_t h = h1 < h2 ? h1 : h2;
   h = h < h3 ? h : h3;
   return (float)h * Pm->vertical_scale;
+}
+// The yaw-only quaternion of the height scan from the root quaternion's z and w.
+LGX_HD void scan_yaw_quat(float qz, float qw, float* qy) {
+  float n = sqrtf(qz * qz + qw * qw);
+  n = n < 1e-9f ? 1e-9f : n;
+  qy[0] = 0.f; qy[1] = 0.f; qy[2] = qz / n; qy[3] = qw / n;
+}
+// One point of the height scan: the terrain height under the base-frame point (bx, by) of a robot
+// whose world position is pos[0..1], with the yaw-only quaternion qy.
+LGX_HD float scan_point_height(const lgx_task_params* Pm, const int16_t* hs, const float* qy, const float* pos,
+                               float bx, float by) {
+  float p[3] = {bx, by, 0.f}, w[3];
+  quat_apply(qy, p, w);
+  float px = (w[0] + pos[0]) + Pm->border_size, py = (w[1] + pos[1]) + Pm->border_size;
+  long ix, iy;
+  return terrain_cell_height(Pm, hs, px, py, ix, iy);
+}
+
+// Contact record (lgx_contact_buffers, include/lgx.h ABI 14). The terrain height under (x, y): the
+// arithmetic of the step's height scan (terrain_cell_height); ix, iy: the clamped cell, for
+// contact_relief. hs == nullptr (a plane): 0.
+LGX_HD float contact_terrain_height(const lgx_task_params* Pm, const int16_t* hs, float x, float y, long& ix,
+                                    long& iy) {
+  ix = iy = 0;
+  if (hs == nullptr) return 0.f;
+  const float px = x + Pm->border_size, py = y + Pm->border_size;
+  return terrain_cell_height(Pm, hs, px, py, ix, iy);
 }
 // The terrain relief around the cell (ix, iy) of contact_terrain_height: max - min of the nine
 // samples around the cell moved into [1, rows - 2] x [1, cols - 2] (hf_rows, hf_cols >= 3: checked
@@ -663,6 +688,38 @@ LGX_HD float sensor_noise_bias(float v, bool add_noise, float u, float nv, const
     if (b != 0.0f) v = v + b;
   }
   return v;
+}
+
+// Height-scan model (lgx_buffers.scan_noise .. scan_history, include/lgx.h, ABI 17). The rule of one
+// point; the HIP kernel and the host backend both call these.
+// The four uniforms of block `block` of the model's own Philox stream (the env step's counter layout).
+LGX_HD void scan_uniform_block(uint64_t seed, uint32_t gid, uint64_t step, int block, float* u) {
+  uint32_t o[4];
+  philox4x32_10(gid, (uint32_t)step, (uint32_t)block | ((uint32_t)LGX_SCAN_STREAM << 16), (uint32_t)(step >> 32),
+                (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  u[0] = u01(o[0]); u[1] = u01(o[1]); u[2] = u01(o[2]); u[3] = u01(o[3]);
+}
+// Uniform `slot` of that stream: the noise of point i is slot i, its dropout draw slot
+// LGX_MAX_HEIGHT_POINTS + i.
+LGX_HD float scan_uniform(uint64_t seed, uint32_t gid, uint64_t step, int slot) {
+  float u[4];
+  scan_uniform_block(seed, gid, step, slot >> 2, u);
+  const int w = slot & 3;
+  return w == 0 ? u[0] : (w == 1 ? u[1] : (w == 2 ? u[2] : u[3]));
+}
+// The raw value of a point from the height under it.
+LGX_HD float scan_raw(float root_z, float h) { return clipf(root_z - 0.3f - h, -1.0f, 1.0f); }
+// Is the point lost in this step: u its dropout uniform, p the env's probability.
+LGX_HD bool scan_point_lost(float u, float p) { return p > 0.0f && u < p; }
+// The model of one point on v, its (delayed) raw value: noise of amplitude amp with uniform u, the
+// vertical offset dz, dropout (probability p, uniform ud, fill value), in this order, each sum a
+// rounding of its own, then the clip. amp = 0, dz = 0 and p = 0 return v with its bits: the clip
+// is the identity on a raw value.
+LGX_HD float scan_point_model(float v, float amp, float u, float dz, float p, float ud, float fill) {
+  if (amp != 0.0f) v = v + obs_noise_term(u, amp);
+  if (dz != 0.0f) v = v + dz;
+  if (scan_point_lost(ud, p)) v = fill;
+  return clipf(v, -1.0f, 1.0f);
 }
 
 // One uniform of the env step's Philox table (fill_uniforms: slot = 4 * block + word).

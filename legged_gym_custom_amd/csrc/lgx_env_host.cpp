@@ -631,22 +631,11 @@ static void get_heights(const lgx_task_params* P, const lgx_buffers* B, Env& s) 
     return;
   }
   const float* root = s.root;
-  const float qz = root[5], qw = root[6];
-  float n = sqrtf(qz * qz + qw * qw);
-  n = n < 1e-9f ? 1e-9f : n;
-  const float qy[4] = {0.f, 0.f, qz / n, qw / n};
-  for (int i = 0; i < NP; ++i) {
-    const float p[3] = {P->height_points[i][0], P->height_points[i][1], 0.f};
-    float w[3];
-    quat_apply(qy, p, w);
-    const float px = (w[0] + root[0]) + P->border_size, py = (w[1] + root[1]) + P->border_size;
-    long ix = (long)(px / P->horizontal_scale), iy = (long)(py / P->horizontal_scale);
-    ix = ix < 0 ? 0 : (ix > P->hf_rows - 2 ? P->hf_rows - 2 : ix);
-    iy = iy < 0 ? 0 : (iy > P->hf_cols - 2 ? P->hf_cols - 2 : iy);
-    const int16_t* hsm = B->height_samples;
-    int16_t h = std::min(std::min(hsm[ix * P->hf_cols + iy], hsm[(ix + 1) * P->hf_cols + iy]), hsm[ix * P->hf_cols + iy + 1]);
-    s.heights[i] = (float)h * P->vertical_scale;
-  }
+  float qy[4];
+  scan_yaw_quat(root[5], root[6], qy);
+  for (int i = 0; i < NP; ++i)
+    s.heights[i] = scan_point_height(P, B->height_samples, qy, root, P->height_points[i][0],
+                                     P->height_points[i][1]);
 }
 
 // sums over joints / height points shared by the reward terms (lgx_env.hip joint_sums)
@@ -886,6 +875,8 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
     *B->blowup_count += 1u;
   }
   for (int k = 0; k < KS; ++k) B->episode_sums[(size_t)e * KS + k] += s.rterm[k];
+  // scan model (include/lgx.h, ABI 17): the second lookup uses the pose the height scan used
+  const float scan_pose[4] = {s.root[0], s.root[1], s.root[5], s.root[6]};
   if (reset) reset_env(P, B, s, e, false, stats);  // reset_idx go2.py:207-263
 
   // compute_observations go2.py:467-574 / legged_robot.py:240-273
@@ -972,10 +963,34 @@ static void env_step(Env& s, const lgx_model* M, const lgx_task_params* P, const
       B->est[(size_t)e * P->num_est + i] = v;
       if (cr) cr[NO + P->num_priv + i] = v;
     }
-    for (int i = 0; i < P->num_scan; ++i) {
-      const float v = clipf(s.root[2] - 0.3f - s.heights[i], -1.0f, 1.0f);
-      B->scan[(size_t)e * P->num_scan + i] = v;
-      if (cr) cr[NO + P->num_priv + 3 + i] = clipf(v, -co, co);
+    // height-scan model (include/lgx.h, ABI 17): the kernel's rule; all unbound = the clean scan
+    const int S = P->num_scan, SK = P->sensor_history_len;
+    const uint32_t gid = (uint32_t)(P->env_id_offset + e);
+    const float amp = B->scan_noise ? B->scan_noise[e] : 0.f;
+    const float drop_p = B->scan_dropout ? B->scan_dropout[(size_t)e * 2] : 0.f;
+    const float fill = B->scan_dropout ? B->scan_dropout[(size_t)e * 2 + 1] : 0.f;
+    const float* off = B->scan_offset ? B->scan_offset + (size_t)e * 3 : nullptr;
+    const float dx = off ? off[0] : 0.f, dy = off ? off[1] : 0.f, dz = off ? off[2] : 0.f;
+    const bool second = (dx != 0.f || dy != 0.f) && P->mesh_type != LGX_MESH_PLANE && B->height_samples != nullptr;
+    float qy[4] = {0.f, 0.f, 0.f, 1.f};
+    if (second) scan_yaw_quat(scan_pose[2], scan_pose[3], qy);
+    const int scan_d = B->scan_delay ? sensor_delay_clamp(B->scan_delay[e], SK, sens_c) : 0;
+    for (int i = 0; i < S; ++i) {
+      const float clean = scan_raw(s.root[2], s.heights[i]);
+      float raw = clean;
+      if (second)
+        raw = scan_raw(s.root[2], scan_point_height(P, B->height_samples, qy, scan_pose,
+                                                    P->height_points[i][0] + dx, P->height_points[i][1] + dy));
+      float v = raw;
+      if (B->scan_history) {
+        float* ring = B->scan_history + (size_t)e * SK * S;
+        if (scan_d > 0) v = ring[(size_t)sensor_ring_read_row(sens_c, scan_d, SK) * S + i];
+        ring[(size_t)sensor_ring_write_row(sens_c, SK) * S + i] = raw;
+      }
+      const float u = amp != 0.f ? scan_uniform(seed, gid, step, i) : 0.f;
+      const float ud = drop_p > 0.f ? scan_uniform(seed, gid, step, LGX_MAX_HEIGHT_POINTS + i) : 0.f;
+      B->scan[(size_t)e * S + i] = scan_point_model(v, amp, u, dz, drop_p, ud, fill);
+      if (cr) cr[NO + P->num_priv + 3 + i] = clipf(clean, -co, co);
     }
   }
   for (int i = 0; i < H * Pp; ++i)  // history update go2.py:570-574

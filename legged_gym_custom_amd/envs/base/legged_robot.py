@@ -257,6 +257,28 @@ class LeggedRobot(BaseTask):
         return self._reduced_cells("lgx_eval_reduce", self._sensor_eval, self._sensor_eval_overflow, "a cell id",
                                    self._sensor_eval_cells)[0]
 
+    def scan_eval_buffers(self, rows, cols):
+        """sensor_eval_buffers for the scan test (PolicyEvaluator.run_scan_test): scan_cell_ids [N]
+        int32, scan_eval_acc [N, 8], scan_eval_status [N] and, after eval_scan_cells, cells
+        [rows, cols, 12]; allocated once per (rows, cols)."""
+        key = (int(rows), int(cols))
+        if getattr(self, "_scan_eval_key", None) != key:
+            z, n = self._zeros, self.num_envs
+            self.scan_eval_acc, self.scan_eval_status = z(n, _abi.EVAL_METRICS), z(n, dtype=torch.uint8)
+            self.scan_cell_ids = z(n, dtype=torch.int32)
+            self._scan_eval_cells = z(*key, _abi.EVAL_CELL_COLS, dtype=torch.float64)
+            self._scan_eval_overflow = z(1, dtype=torch.int32)
+            self._scan_eval = self._native.eval_buffers(self.scan_eval_acc, self.scan_eval_status, self._scan_eval_cells,
+                                                        self._scan_eval_overflow, cell_ids=self.scan_cell_ids)
+            self._scan_eval_key = key
+        return self._scan_eval
+
+    def eval_scan_cells(self):
+        """lgx_eval_reduce on the scan test's buffers, then the cells [rows, cols, 12] float64 on the
+        host. Synchronises. A cell id outside the grid is an error."""
+        return self._reduced_cells("lgx_eval_reduce", self._scan_eval, self._scan_eval_overflow, "a cell id",
+                                   self._scan_eval_cells)[0]
+
     def eval_cells(self):
         """lgx_eval_reduce, then the cells [rows, cols, 12] float64 on the host: n_envs, n_timeout,
         n_fall, n_blowup and the sums of the 8 record columns over each cell's finished envs.
@@ -671,6 +693,7 @@ class LeggedRobot(BaseTask):
         if prm.scheduled_commands(self.cfg):
             self._alloc_command_schedule()
         self._init_external_force()  # after every existing setup draw: those keep their values
+        self._init_scan_model()      # and so do these, after the force's
         self.default_dof_pos = torch.tensor([self.cfg.init_state.default_joint_angles[nm] for nm in self.dof_names],
                                             device=dev).unsqueeze(0)
         self._dof_state3[..., 0] = self.default_dof_pos
@@ -755,6 +778,8 @@ class LeggedRobot(BaseTask):
             "obs_noise_scale": self.obs_noise_scales, "obs_bias": self.obs_biases, "obs_delay": self.obs_delay_steps,
             "sensor_history": self.sensor_history, "sensor_count": self.sensor_count,
             "force_window": self.force_window, "force_vec": self.force_vec,
+            "scan_noise": self.scan_noise_amps, "scan_dropout": self.scan_dropouts, "scan_offset": self.scan_offsets,
+            "scan_delay": self.scan_delay_steps, "scan_history": self.scan_history,
             **self._sea_buffers,
         })
 
@@ -848,7 +873,7 @@ class LeggedRobot(BaseTask):
             self.obs_noise_scales = torch.ones(n, device=dev)
         if sm["on"] or sm["bias_on"]:
             self.obs_biases = torch.zeros(n, p, device=dev)
-        if K > 0:
+        if K > 0:  # (K covers the scan model's latency too: the proprio ring then exists beside the scan's)
             self.obs_delay_steps = torch.zeros(n, dtype=torch.int32, device=dev)
             self.sensor_history = torch.zeros(n, K, p, device=dev)
             self.sensor_count = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -864,12 +889,12 @@ class LeggedRobot(BaseTask):
             lo, hi = sm["delay_range_s"]
             self.set_obs_delay(((hi - lo) * torch.rand(total, device=dev) + lo)[sl])
 
-    def _sensor_alloc(self, name, what, make):
+    def _sensor_alloc(self, name, what, make, key="sensor_model"):
         """The first call of a sensor setter on an env built without its buffer: allocate, re-bind."""
         if self._captured:
             raise RuntimeError(f"{what}: this env has no {name} buffer and its step has been captured in a graph, "
                                "which would go on replaying the old binding; build the env with "
-                               f"domain_rand.sensor_model or call {what} before the capture")
+                               f"domain_rand.{key} or call {what} before the capture")
         setattr(self, name, make())
         self._bind()
 
@@ -947,6 +972,119 @@ class LeggedRobot(BaseTask):
                 raise ValueError(f"obs bias {name} must be finite")
             out[:, sl] = v * prm.sensor_obs_scale(self.cfg, name)
         return out
+
+    # ------------------------------------------------------------------ height-scan model
+    def _init_scan_model(self):
+        """Per-env height-scan model (include/lgx.h ABI 17; domain_rand keys of params.scan_model):
+        noise, dropout, map offset and latency on the Go2 task kind's scan_obs_buf. scan_noise_amps
+        [N], scan_dropouts [N, 2] (probability, value) and scan_offsets [N, 3] exist, and are bound,
+        when their randomisation or domain_rand.scan_model is on (or after their setter's first
+        call); scan_delay_steps [N] and scan_history [N, K, S] when max_scan_delay_s gives a
+        capacity. Otherwise the attributes are None and the step is that of ABI 16. Draws only for
+        an enabled feature, after every other setup draw, for all global envs and sliced by rank,
+        fixed per env: an amplitude U(lo, hi) m, a probability U(lo, hi), a shift of length
+        U(lo, hi) m in a direction uniform on the circle with dz U(lo, hi) m, a latency
+        round(U(lo, hi) / dt)."""
+        n, dev = self.num_envs, self.device
+        total, sl = self.num_envs_total, slice(self.env_id_offset, self.env_id_offset + self.num_envs)
+        sc = prm.scan_model(self.cfg, self.dt)
+        S = int(self.num_scan_obs) if self.TASK_KIND == _abi.TASK_GO2 else 0
+        self.scan_noise_amps = self.scan_dropouts = self.scan_offsets = self.scan_delay_steps = self.scan_history = None
+        self._scan_points = S
+        self._scan_dropout_value = sc["dropout_value"]
+        self._scan_delay_cap = sc["delay_steps"] if S > 0 else 0
+        if sc["any"] and S <= 0:
+            raise ValueError("domain_rand: the scan model needs a task with a height scan (Go2 task kind, num_scan_obs > 0)")
+        if S <= 0:
+            return
+        if sc["on"] or sc["noise_on"]:
+            self.scan_noise_amps = torch.zeros(n, device=dev)
+        if sc["on"] or sc["dropout_on"]:
+            self.scan_dropouts = self._neutral_scan_dropout()
+        if sc["on"] or sc["offset_on"]:
+            self.scan_offsets = torch.zeros(n, 3, device=dev)
+        if sc["delay_steps"] > 0:
+            self.scan_delay_steps = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.scan_history = torch.zeros(n, self._sensor_history_len, S, device=dev)
+        u = lambda r, *shape: (r[1] - r[0]) * torch.rand(total, *shape, device=dev) + r[0]  # noqa: E731
+        if sc["noise_on"]:
+            self.set_scan_noise(u(sc["noise_range"])[sl])
+        if sc["dropout_on"]:
+            self.set_scan_dropout(u(sc["dropout_range"])[sl], sc["dropout_value"])
+        if sc["offset_on"]:
+            r, th = u(sc["offset_xy_range"]), 2.0 * math.pi * torch.rand(total, device=dev)
+            dz = u(sc["offset_z_range"])
+            self.set_scan_offset((r * torch.cos(th))[sl], (r * torch.sin(th))[sl], dz[sl])
+        if sc["delay_on"] and sc["delay_steps"] > 0:
+            self.set_scan_delay(u(sc["delay_range_s"])[sl])
+
+    def _neutral_scan_dropout(self):
+        d = torch.zeros(self.num_envs, 2, device=self.device)
+        d[:, 1] = self._scan_dropout_value
+        return d
+
+    def _scan_per_env(self, what, value, lo=None, hi=None):
+        """A number or a tensor [num_envs] -> float32 [num_envs] on the device; ValueError otherwise."""
+        if self._scan_points <= 0:
+            raise ValueError(f"{what}: this task has no height scan (Go2 task kind, num_scan_obs > 0)")
+        v = torch.as_tensor(value, dtype=torch.float32, device=self.device)
+        if v.dim() not in (0, 1) or (v.dim() == 1 and v.shape[0] != self.num_envs):
+            raise ValueError(f"{what}: a number or a tensor [{self.num_envs}], got shape {list(v.shape)}")
+        if not bool(torch.isfinite(v).all()) or (lo is not None and float(v.min()) < lo) or \
+                (hi is not None and float(v.max()) > hi):
+            raise ValueError(f"{what}: finite values" + (f" in [{lo:g}, {hi if hi is not None else math.inf:g}]"
+                                                          if lo is not None else ""))
+        return v.expand(self.num_envs)
+
+    def set_scan_noise(self, m):
+        """Scan noise of every env: a number or a tensor [num_envs], the amplitude in m of uniform
+        noise per scan point and step (0: none). Written in place once the buffer exists; the first
+        call on an env built without it allocates and re-binds: RuntimeError once a step of this
+        env has been captured. ValueError when negative or not finite."""
+        v = self._scan_per_env("set_scan_noise", m, 0.0)
+        if self.scan_noise_amps is None:
+            self._sensor_alloc("scan_noise_amps", "set_scan_noise", lambda: torch.zeros(self.num_envs, device=self.device),
+                               key="scan_model")
+        self.scan_noise_amps.copy_(v)
+
+    def set_scan_dropout(self, p, value=1.0):
+        """Scan dropout of every env: p, a number or a tensor [num_envs], the probability that a
+        scan point is lost in a step, and the value a lost point reads (a number or [num_envs],
+        |value| <= 1; 1.0: no return, far). In place / first call as set_scan_noise."""
+        pv = self._scan_per_env("set_scan_dropout", p, 0.0, 1.0)
+        fv = self._scan_per_env("set_scan_dropout value", value, -1.0, 1.0)
+        if self.scan_dropouts is None:
+            self._sensor_alloc("scan_dropouts", "set_scan_dropout", self._neutral_scan_dropout, key="scan_model")
+        self.scan_dropouts[:, 0].copy_(pv)
+        self.scan_dropouts[:, 1].copy_(fv)
+
+    def set_scan_offset(self, dx, dy, dz=0.0):
+        """Map misregistration of every env: the scan is taken at the scan points shifted by (dx, dy)
+        m in the robot's yaw frame, and dz m is added to every point. Each a number or a tensor
+        [num_envs]. In place / first call as set_scan_noise."""
+        vs = [self._scan_per_env("set_scan_offset", v) for v in (dx, dy, dz)]
+        if self.scan_offsets is None:
+            self._sensor_alloc("scan_offsets", "set_scan_offset", lambda: torch.zeros(self.num_envs, 3, device=self.device),
+                               key="scan_model")
+        for j, v in enumerate(vs):
+            self.scan_offsets[:, j].copy_(v)
+
+    def set_scan_delay(self, seconds):
+        """Latency of every env's scan: a number of seconds or a tensor [num_envs], rounded to control
+        steps. Written in place. ValueError when negative, or beyond the capacity the env was built
+        with (domain_rand.max_scan_delay_s)."""
+        if self.scan_delay_steps is None:
+            raise ValueError("this env was built without scan latency support: set "
+                             "domain_rand.max_scan_delay_s (or randomize_scan_delay) in its config")
+        s = torch.as_tensor(seconds, dtype=torch.float64, device=self.device)
+        if s.dim() not in (0, 1) or (s.dim() == 1 and s.shape[0] != self.num_envs):
+            raise ValueError(f"scan delay: a number or a tensor [{self.num_envs}], got shape {list(s.shape)}")
+        st = torch.round(s / float(self.dt))
+        lo, hi = float(st.min()), float(st.max())
+        if not (lo >= 0.0 and hi <= self._scan_delay_cap):  # also refuses NaN
+            raise ValueError(f"scan delay of {lo:g}..{hi:g} control steps is outside 0..{self._scan_delay_cap} "
+                             "(capacity: domain_rand.max_scan_delay_s)")
+        self.scan_delay_steps.copy_(st.to(torch.int32).expand(self.num_envs))
 
     # ------------------------------------------------------------------ scheduled pushes
     def _alloc_push_schedule(self):

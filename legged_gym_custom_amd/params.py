@@ -111,7 +111,8 @@ def sensor_model(cfg, dt):
       bias_on / bias_level_range   randomize_obs_bias, obs_bias_level_range (multiples of sensor_amplitudes)
       delay_on / delay_range_s / max_delay_s   randomize_obs_delay, obs_delay_range_s, max_obs_delay_s
                                                (default: the range's upper end)
-      history_len    K = round(max_obs_delay_s / dt) control steps (lgx_task_params.sensor_history_len)
+      history_len    K = round(max(max_obs_delay_s, max_scan_delay_s) / dt) control steps
+                     (lgx_task_params.sensor_history_len; the scan model's ring shares it)
     A ValueError when K exceeds LGX_MAX_SENSOR_HISTORY or a range is not 0 <= lo <= hi."""
     dr = cfg.domain_rand
     delay_on = bool(getattr(dr, "randomize_obs_delay", False))
@@ -119,12 +120,13 @@ def sensor_model(cfg, dt):
     max_s = float(getattr(dr, "max_obs_delay_s", hi if delay_on else 0.0))
     if not (0.0 <= lo <= hi) or not max_s >= 0.0:
         raise ValueError(f"domain_rand.obs_delay_range_s {[lo, hi]} / max_obs_delay_s {max_s}: need 0 <= lo <= hi")
-    K = int(round(max_s / dt))
-    if delay_on and int(round(hi / dt)) > K:
+    if delay_on and int(round(hi / dt)) > int(round(max_s / dt)):
         raise ValueError(f"domain_rand.obs_delay_range_s upper end {hi} s exceeds max_obs_delay_s {max_s} s")
+    # the scan model's ring (ABI 17) has the same K rows: the capacity is the larger of the two
+    K = int(round(max(max_s, scan_delay_capacity(cfg, dt)[0]) / dt))
     if K > _abi.MAX_SENSOR_HISTORY:
-        raise ValueError(f"domain_rand.max_obs_delay_s = {max_s} s is {K} control steps of sensor history; "
-                         f"at most {_abi.MAX_SENSOR_HISTORY} (LGX_MAX_SENSOR_HISTORY)")
+        raise ValueError(f"domain_rand.max_obs_delay_s / max_scan_delay_s = {max(max_s, scan_delay_capacity(cfg, dt)[0])} s "
+                         f"is {K} control steps of sensor history; at most {_abi.MAX_SENSOR_HISTORY} (LGX_MAX_SENSOR_HISTORY)")
     scale_on = bool(getattr(dr, "randomize_obs_noise_scale", False))
     slo, shi = (float(v) for v in getattr(dr, "obs_noise_scale_range", [1.0, 1.0]))
     if scale_on and not (0.0 <= slo <= shi):
@@ -136,6 +138,65 @@ def sensor_model(cfg, dt):
     return dict(on=bool(getattr(dr, "sensor_model", False)), scale_on=scale_on, scale_range=[slo, shi],
                 bias_on=bias_on, bias_level_range=[blo, bhi], delay_on=delay_on, delay_range_s=[lo, hi],
                 max_delay_s=max_s, history_len=K)
+
+
+def scan_delay_capacity(cfg, dt):
+    """(max_scan_delay_s, delay_on, [lo, hi]) of cfg.domain_rand: the scan model's latency keys
+    randomize_scan_delay, scan_delay_range_s, max_scan_delay_s (default: the range's upper end when
+    the randomisation is on). ValueError when the range is not 0 <= lo <= hi or exceeds the capacity."""
+    dr = cfg.domain_rand
+    delay_on = bool(getattr(dr, "randomize_scan_delay", False))
+    lo, hi = (float(v) for v in getattr(dr, "scan_delay_range_s", [0.0, 0.0]))
+    max_s = float(getattr(dr, "max_scan_delay_s", hi if delay_on else 0.0))
+    if not (0.0 <= lo <= hi) or not max_s >= 0.0:
+        raise ValueError(f"domain_rand.scan_delay_range_s {[lo, hi]} / max_scan_delay_s {max_s}: need 0 <= lo <= hi")
+    if delay_on and int(round(hi / dt)) > int(round(max_s / dt)):
+        raise ValueError(f"domain_rand.scan_delay_range_s upper end {hi} s exceeds max_scan_delay_s {max_s} s")
+    return max_s, delay_on, [lo, hi]
+
+
+def scan_model(cfg, dt):
+    """The height-scan model's keys of cfg.domain_rand (include/lgx.h ABI 17; all optional, read with
+    getattr: the shipped config classes do not carry them) -> dict:
+      on             scan_model: allocate and bind the buffers up front, with neutral values
+      noise_on / noise_range       randomize_scan_noise, scan_noise_range (m)
+      dropout_on / dropout_range / dropout_value
+                                   randomize_scan_dropout, scan_dropout_range (probability),
+                                   scan_dropout_value (what a lost point reads, default 1.0)
+      offset_on / offset_xy_range / offset_z_range
+                                   randomize_scan_offset, scan_offset_xy_range (m, the length of a
+                                   shift in a random direction), scan_offset_z_range (m, lo <= hi)
+      delay_on / delay_range_s / max_delay_s
+                                   randomize_scan_delay, scan_delay_range_s, max_scan_delay_s
+      delay_steps    round(max_scan_delay_s / dt): > 0 = the scan ring exists (its K rows are
+                     sensor_model's history_len, the larger of the two capacities)
+      any            one of the above asks for a buffer
+    A ValueError for a bad range: 0 <= lo <= hi (dropout: hi <= 1; z: lo <= hi), |dropout value| <= 1."""
+    dr = cfg.domain_rand
+    max_s, delay_on, delay_range = scan_delay_capacity(cfg, dt)
+
+    def rng(key, default, lo_min=0.0, hi_max=math.inf):
+        lo, hi = (float(v) for v in getattr(dr, key, default))
+        if not (lo_min <= lo <= hi <= hi_max):
+            raise ValueError(f"domain_rand.{key} {[lo, hi]}: need {lo_min:g} <= lo <= hi <= {hi_max:g}")
+        return [lo, hi]
+
+    noise_range = rng("scan_noise_range", [0.0, 0.0])
+    dropout_range = rng("scan_dropout_range", [0.0, 0.0], hi_max=1.0)
+    xy_range = rng("scan_offset_xy_range", [0.0, 0.0])
+    z_range = rng("scan_offset_z_range", [0.0, 0.0], lo_min=-math.inf)
+    value = float(getattr(dr, "scan_dropout_value", 1.0))
+    if not abs(value) <= 1.0:
+        raise ValueError(f"domain_rand.scan_dropout_value {value}: a scan value, |value| <= 1")
+    out = dict(on=bool(getattr(dr, "scan_model", False)),
+               noise_on=bool(getattr(dr, "randomize_scan_noise", False)), noise_range=noise_range,
+               dropout_on=bool(getattr(dr, "randomize_scan_dropout", False)), dropout_range=dropout_range,
+               dropout_value=value,
+               offset_on=bool(getattr(dr, "randomize_scan_offset", False)), offset_xy_range=xy_range,
+               offset_z_range=z_range, delay_on=delay_on, delay_range_s=delay_range, max_delay_s=max_s,
+               delay_steps=int(round(max_s / dt)))
+    out["any"] = out["on"] or out["noise_on"] or out["dropout_on"] or out["offset_on"] or out["delay_steps"] > 0
+    return out
 
 
 def noise_vector(cfg, go2):

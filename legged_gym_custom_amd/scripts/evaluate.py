@@ -10,6 +10,7 @@ stays as trained: observation noise, pushes, friction / mass / gain randomisatio
          [--push_vel v[,v,...] [--push_dirs 8] [--push_at_s 2.0]]
          [--cmd_vx a[,b,...] [--cmd_vy ...] [--cmd_yaw ...] [--cmd_at_s 2.0] [--cmd_start vx,vy,yaw]]
          [--obs_noise a[,b,...]] [--obs_bias a[,b,...]] [--obs_delay_ms a[,b,...]]
+         [--scan_noise_m a[,b,...]] [--scan_dropout a[,b,...]] [--scan_offset_m=a[,b,...]] [--scan_delay_ms a[,b,...]]
          [--force_n a[,b,...] [--force_dirs 8] [--force_at_s 2.0] [--force_for_s S] [--force_point x,y,z]
           [--force_cmd vx,vy,yaw]]
          [--trace_falls M [--trace_s 2.0]] [--gait] [--joints] [--contacts]
@@ -37,6 +38,16 @@ level), --obs_bias in multiples of the same amplitudes as a constant random offs
 --obs_delay_ms as a sensing latency in ms, rounded to control steps. A list that is not given is the neutral one
 (1 / 0 / 0). The env is built with domain_rand.sensor_model = True and the sensor history the largest latency needs;
 the rest of the config stays as trained. Not with --push_vel, --cmd_vx, --action_delay_ms or --motor_strength.
+
+--scan_noise_m / --scan_dropout / --scan_offset_m / --scan_delay_ms: the scan test (PolicyEvaluator.run_scan_test);
+any of the four selects it. Every env gets one cell of the noise x dropout x offset x latency grid through the step
+kernel's height-scan model: --scan_noise_m as the amplitude in m of uniform noise per scan point and step,
+--scan_dropout as the probability that a point is lost in a step (it then reads --scan_dropout_value, default 1.0:
+no return, far), --scan_offset_m as a shift of the whole map along the robot's heading in m (write the list with
+"=" when it begins with a minus sign), --scan_delay_ms as the scan's latency in ms, rounded to control steps. A
+list that is not given is the neutral one (0). The env is built with domain_rand.scan_model = True and the scan
+history the largest latency needs; the rest of the config stays as trained. One line per bin with its survival
+rate is printed before the JSON. Tasks with a height scan only (Go2 task kind). Not with the other tests.
 
 --force_n: the force test (PolicyEvaluator.run_force_test): every env holds --force_cmd (default 0.5,0,0) and,
 from --force_at_s seconds into its episode on, takes a sustained external force of one of the given magnitudes (N;
@@ -82,7 +93,7 @@ or bin with data is printed before the JSON ("contacts <where>: falls 37: base 6
 One JSON document is printed and written next to the checkpoint (eval_<policy>.json; a sweep:
 eval_<policy>_latency.json; the push test: eval_<policy>_push.json; the command test:
 eval_<policy>_command.json; the sensor test: eval_<policy>_sensors.json; the force test:
-eval_<policy>_force.json)."""
+eval_<policy>_force.json; the scan test: eval_<policy>_scan.json)."""
 import argparse
 import json
 import os
@@ -105,7 +116,8 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
              push_vel=None, push_dirs=8, push_at_s=2.0, cmd_vx=None, cmd_vy=None, cmd_yaw=None, cmd_at_s=2.0,
              cmd_start=None, trace_falls=None, trace_s=2.0, gait=False, joints=False, contacts=False, obs_noise=None,
              obs_bias=None, obs_delay_ms=None, force_n=None, force_dirs=8, force_at_s=2.0, force_for_s=None,
-             force_point=None, force_cmd=None):
+             force_point=None, force_cmd=None, scan_noise_m=None, scan_dropout=None, scan_offset_m=None, scan_delay_ms=None,
+             scan_dropout_value=1.0):
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.terrain.curriculum = False
     env_cfg.commands.curriculum = False
@@ -143,6 +155,17 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
         env_cfg.commands.scheduled_commands = True   # the schedule and the force buffers exist
         env_cfg.domain_rand.scheduled_forces = True  # before any capture
         env_cfg.domain_rand.push_robots = False      # the force is the only disturbance
+    scan = any(v is not None for v in (scan_noise_m, scan_dropout, scan_offset_m, scan_delay_ms))
+    if scan:
+        if push_vel or cmd_vx or sensors or force_n or delays_s or motor_strength is not None:
+            raise ValueError("--scan_noise_m / --scan_dropout / --scan_offset_m / --scan_delay_ms are a mode of their own: "
+                             "not with --push_vel / --cmd_vx / --obs_* / --force_n / --action_delay_ms / --motor_strength")
+        scan_delay_s = [float(ms) / 1000.0 for ms in (scan_delay_ms or [0.0])]
+        dr = env_cfg.domain_rand
+        dr.scan_model = True  # the buffers exist before any capture
+        from legged_gym_custom_amd import params as prm
+        own = prm.scan_delay_capacity(env_cfg, env_cfg.control.decimation * env_cfg.sim.dt)[0]
+        dr.max_scan_delay_s = max([own] + scan_delay_s)  # the capacity the largest latency needs
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
 
     train_cfg.runner.resume = True
@@ -177,6 +200,12 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
                                                   num_steps=eval_steps, graph=graph, trace_depth=depth, gait=gait,
                                                   joints=joints, contacts=contacts))
         out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_force.json")
+    elif scan:
+        report = dict(**head, **ev.run_scan_test(scan_noise_m or (0.0,), scan_dropout or (0.0,), scan_offset_m or (0.0,),
+                                                 scan_delay_s, num_steps=eval_steps, graph=graph, trace_depth=depth,
+                                                 gait=gait, joints=joints, contacts=contacts,
+                                                 dropout_value=scan_dropout_value))
+        out = os.path.join(os.path.dirname(checkpoint), f"eval_{policy}_scan.json")
     elif len(delays_s) > 1:
         sweep = ev.sweep_action_delay(delays_s, num_steps=eval_steps, graph=graph, motor_strength=motor_strength,
                                       trace_depth=depth, gait=gait, joints=joints, contacts=contacts)
@@ -195,6 +224,19 @@ def evaluate(args, policy="student", eval_steps=None, root=None, graph=True, act
     with open(out, "w") as f:
         json.dump(report, f, indent=1)
     return report, out
+
+
+def scan_summary(report):
+    """The survival table of a scan test: one line per bin, then the total."""
+    fmt = lambda v, spec: "-" if v is None else format(v, spec)  # noqa: E731
+    lines = []
+
+    def line(where, entry, always=False):
+        lines.append(f"{where}: survival {fmt(entry['survival_rate'], '.3f')}, fall rate {fmt(entry['fall_rate'], '.3f')}, "
+                     f"{entry['episodes']} episodes")
+
+    _each_place(report, line)
+    return lines
 
 
 def gait_summary(report):
@@ -227,6 +269,13 @@ def _each_place(report, line):
             for f, row in enumerate(rep["bins"]):
                 for d, cell in enumerate(row):
                     line(f"{tag}force {rep['forces_n'][f]:g} N from {rep['directions_deg'][d]:g} deg", cell)
+        elif "offset_x_m" in rep:  # the scan test
+            for i, a in enumerate(rep["bins"]):
+                for j, b in enumerate(a):
+                    for k, c in enumerate(b):
+                        for m, cell in enumerate(c):
+                            line(f"{tag}scan noise {rep['noise_m'][i]:g} m dropout {rep['dropout'][j]:g} offset "
+                                 f"{rep['offset_x_m'][k]:g} m delay {1000.0 * rep['delay_s'][m]:g} ms", cell)
         elif "delay_steps" in rep:  # the sensor test
             for i, a in enumerate(rep["bins"]):
                 for j, b in enumerate(a):
@@ -300,6 +349,11 @@ def main(argv=None):
     p.add_argument("--obs_noise", type=floats, default=None)
     p.add_argument("--obs_bias", type=floats, default=None)
     p.add_argument("--obs_delay_ms", type=floats, default=None)
+    p.add_argument("--scan_noise_m", type=floats, default=None)
+    p.add_argument("--scan_dropout", type=floats, default=None)
+    p.add_argument("--scan_dropout_value", type=float, default=1.0)
+    p.add_argument("--scan_offset_m", type=floats, default=None)
+    p.add_argument("--scan_delay_ms", type=floats, default=None)
     p.add_argument("--force_n", type=floats, default=None)
     p.add_argument("--force_dirs", type=int, default=8)
     p.add_argument("--force_at_s", type=float, default=2.0)
@@ -321,8 +375,10 @@ def main(argv=None):
                          gait=own.gait, joints=own.joints, contacts=own.contacts, obs_noise=own.obs_noise,
                          obs_bias=own.obs_bias, obs_delay_ms=own.obs_delay_ms, force_n=own.force_n,
                          force_dirs=own.force_dirs, force_at_s=own.force_at_s, force_for_s=own.force_for_s,
-                         force_point=own.force_point, force_cmd=own.force_cmd)
-    for ln in (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []) + \
+                         force_point=own.force_point, force_cmd=own.force_cmd, scan_noise_m=own.scan_noise_m,
+                         scan_dropout=own.scan_dropout, scan_offset_m=own.scan_offset_m, scan_delay_ms=own.scan_delay_ms,
+                         scan_dropout_value=own.scan_dropout_value)
+    for ln in (scan_summary(report) if "offset_x_m" in report else []) + (gait_summary(report) if own.gait else []) + (joint_summary(report) if own.joints else []) + \
             (contact_summary(report) if own.contacts else []):
         print(ln)
     print(json.dumps(report))

@@ -38,6 +38,10 @@ def play(args, num_steps=None, root=None):
     env_cfg.domain_rand.randomize_obs_noise_scale = False
     env_cfg.domain_rand.randomize_obs_bias = False
     env_cfg.domain_rand.randomize_obs_delay = False
+    env_cfg.domain_rand.randomize_scan_noise = False
+    env_cfg.domain_rand.randomize_scan_dropout = False
+    env_cfg.domain_rand.randomize_scan_offset = False
+    env_cfg.domain_rand.randomize_scan_delay = False
     env_cfg.domain_rand.randomize_external_force = False
     env_cfg.domain_rand.push_robots = False
     env_cfg.commands.zero_command = False

@@ -34,6 +34,11 @@ offset and the sensing latency of its bin of a noise x bias x latency grid throu
 kernel's sensor model (lgx_buffers.obs_noise_scale / obs_bias / obs_delay, ABI 15); the plain
 record is reduced per bin: one run gives the whole table.
 
+Height-scan model (run_scan_test): every env gets the scan noise, dropout, map shift and scan
+latency of its bin of a four-way grid through the step kernel's height-scan model
+(lgx_buffers.scan_noise / scan_dropout / scan_offset / scan_delay, ABI 17); the plain record is
+reduced per bin.
+
 Flight recorder (trace_depth= of the three runs, then traces()): a ring buffer on the device for every
 env holds the last trace_depth control steps of the env's recorded episode (lgx_trace_record after
 each step, include/lgx.h ABI 11: state, commands, joints, torques, actions, foot forces, reward and
@@ -430,6 +435,8 @@ class PolicyEvaluator:
         self._push_graph = self._push_graph_key = None  # run_push_test's own captured loop
         self._cmd_graph = self._cmd_graph_key = None    # run_command_test's own captured loop
         self._sensor_graph = self._sensor_graph_key = None  # run_sensor_test's own captured loop
+        self._scan_graph = self._scan_graph_key = None      # run_scan_test's own captured loop
+        self.last_scan_bins = None
         self._force_graph = self._force_graph_key = None  # run_force_test's own captured loop
         self.last_force_cells = self.last_force_bins = None
         self.last_sensor_bins = None
@@ -462,7 +469,7 @@ class PolicyEvaluator:
         """Re-pack the fused act kernel's weights (after the runner loaded or trained them)."""
         if self._fused is not None:
             self._fused.refresh_weights()
-            self._graph = self._push_graph = self._cmd_graph = self._sensor_graph = self._force_graph = None
+            self._graph = self._push_graph = self._cmd_graph = self._sensor_graph = self._force_graph = self._scan_graph = None
 
     # ------------------------------------------------------------------ one iteration
     def act(self):
@@ -608,7 +615,7 @@ class PolicyEvaluator:
 
     def _drive(self, slot, key, num_steps, graph, read_cells, prepare=None, started=None, cleanup=None):
         """The run of all five modes. slot / key: the mode's graph attribute ("_graph", "_push_graph",
-        "_cmd_graph", "_sensor_graph", "_force_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
+        "_cmd_graph", "_sensor_graph", "_force_graph", "_scan_graph"; its key lives in slot + "_key") and the mode's part of the graph key, to which
         the trace depth and the gait, joints and contacts flags are added: the loop is captured when
         there is no graph or the key changed. prepare(): the mode's setup before the capture and begin, returns the eval
         buffers to record into (None: the plain evaluation's); started(): after begin; cleanup():
@@ -1041,6 +1048,96 @@ class PolicyEvaluator:
                "bins": [[[cell_report(cells[i, j * nd + k], dt, w) for k in range(nd)] for j in range(nb)]
                         for i in range(nn)], **rates}
         self._attach_records(out["total"], [b for plane in out["bins"] for row in plane for b in row])
+        return out
+
+    # ------------------------------------------------------------------ height-scan model
+    def run_scan_test(self, noise_m=(0.0,), dropout=(0.0,), offset_x_m=(0.0,), delay_s=(0.0,), num_steps=None, graph=True,
+                      trace_depth=None, gait=False, joints=False, contacts=False, dropout_value=1.0):
+        """How much scan noise, how many lost points, how much map drift and how stale a map does
+        the policy survive: one run over a noise x dropout x offset x latency grid through the step
+        kernel's height-scan model (lgx_buffers.scan_noise / scan_dropout / scan_offset / scan_delay,
+        include/lgx.h ABI 17). Bin index ((in * |dropout| + ip) * |offset_x_m| + io) * |delay_s| +
+        id; envs get bins by randperm(num_envs, seeded with env.seed) % bins. Env e of a bin gets
+        the noise amplitude noise_m[in] (m), the dropout probability dropout[ip] (a lost point reads
+        dropout_value), the map shift offset_x_m[io] m along its heading (negative: the map lags
+        behind) and the scan latency round(delay_s[id] / dt) control steps.
+
+        The records go to eval buffers of their own (env.scan_eval_buffers: the bin is the cell
+        key), and this mode's captured loop is a graph of its own, captured once per grid shape and
+        flags: the buffers are written in place, so other level values of the same shape replay it.
+        The env needs the buffers before any of its steps is captured (domain_rand.scan_model =
+        True, or call this before run()) and, for a latency, the capacity
+        (domain_rand.max_scan_delay_s). The env's own per-env values are put back in place when the
+        run ends or fails. No evaluation kernel of its own: the plain record, reduced per bin.
+
+        trace_depth, gait, joints, contacts: as in run(), the records per bin.
+
+        Returns the report: "bins"[in][ip][io][id] with the REPORT_KEYS entries, "total", noise_m,
+        dropout, offset_x_m, delay_s, delay_steps. None where there is no data, never NaN.
+        ValueError: an empty list, a non-finite entry, a negative noise, dropout or latency, a
+        dropout above 1, a latency beyond the capacity, a task without a height scan."""
+        env = self.env
+        self._set_trace(trace_depth, gait, joints, contacts)
+        noise_m, dropout, offset_x_m, delay_s = ([float(v) for v in lst] for lst in (noise_m, dropout, offset_x_m, delay_s))
+        if min(len(noise_m), len(dropout), len(offset_x_m), len(delay_s)) < 1 or \
+                not all(math.isfinite(v) for v in noise_m + dropout + offset_x_m + delay_s) or \
+                not all(v >= 0.0 for v in noise_m + dropout + delay_s) or max(dropout) > 1.0:
+            raise ValueError("scan test: noise_m, dropout, offset_x_m and delay_s need at least one finite entry each, "
+                             f"noise_m and delay_s >= 0, dropout in [0, 1] (got {noise_m}, {dropout}, {offset_x_m}, {delay_s})")
+        if getattr(env, "_scan_points", 0) <= 0:
+            raise ValueError("scan test: this task has no height scan (Go2 task kind, num_scan_obs > 0)")
+        dt = float(env.dt)
+        dsteps = [int(round(d / dt)) for d in delay_s]
+        cap = int(env._scan_delay_cap) if env.scan_delay_steps is not None else 0
+        if max(dsteps) > cap:
+            raise ValueError(f"scan test: a latency of {max(dsteps)} control steps is beyond the env's capacity of {cap} "
+                             "(domain_rand.max_scan_delay_s)")
+        nn, np_, no, nd = len(noise_m), len(dropout), len(offset_x_m), len(delay_s)
+        bins = self._bins(nn * np_ * no * nd)
+        pick = lambda lst, idx: torch.tensor(lst, dtype=torch.float32)[idx]  # noqa: E731
+        amp = pick(noise_m, bins // (np_ * no * nd))
+        prob = pick(dropout, (bins // (no * nd)) % np_)
+        shift = pick(offset_x_m, (bins // nd) % no)
+        steps = torch.tensor(dsteps, dtype=torch.float64)[bins % nd]
+        saved = []  # (buffer, its values before this run; neutral ones for a buffer this run allocates)
+
+        def prepare():
+            had = [t is not None for t in (env.scan_noise_amps, env.scan_dropouts, env.scan_offsets)]
+            for t in (env.scan_noise_amps, env.scan_dropouts, env.scan_offsets, env.scan_delay_steps):
+                if t is not None:
+                    saved.append((t, t.clone()))
+            dev = env.device
+            env.set_scan_noise(amp.to(dev))  # (a first call allocates: refused once a loop is captured)
+            if not had[0]:
+                saved.append((env.scan_noise_amps, torch.zeros_like(env.scan_noise_amps)))
+            env.set_scan_dropout(prob.to(dev), dropout_value)
+            if not had[1]:
+                saved.append((env.scan_dropouts, env._neutral_scan_dropout()))
+            env.set_scan_offset(shift.to(dev), 0.0, 0.0)
+            if not had[2]:
+                saved.append((env.scan_offsets, torch.zeros_like(env.scan_offsets)))
+            if env.scan_delay_steps is not None:
+                env.set_scan_delay(steps.to(dev) * dt)
+            ev = env.scan_eval_buffers(nn * np_, no * nd)
+            env.scan_cell_ids.copy_(bins.to(torch.int32))
+            self._record_buffers(nn * np_, no * nd, env.scan_cell_ids)  # the bin is the cell key
+            return ev
+
+        def restore():
+            for buf, old in saved:
+                buf.copy_(old)
+
+        cells, head, rates = self._drive("_scan_graph", (nn, np_, no, nd), num_steps, graph, env.eval_scan_cells,
+                                         prepare, cleanup=restore)
+        self.last_scan_bins = bins
+        w = self.mass * self.gravity
+        flat = cells.reshape(-1, cells.shape[2])
+        out = {**head, "noise_m": noise_m, "dropout": dropout, "dropout_value": float(dropout_value),
+               "offset_x_m": offset_x_m, "delay_s": delay_s, "delay_steps": dsteps,
+               "total": cell_report(flat.sum(0), dt, w),
+               "bins": [[[[cell_report(flat[((i * np_ + j) * no + k) * nd + m], dt, w) for m in range(nd)]
+                          for k in range(no)] for j in range(np_)] for i in range(nn)], **rates}
+        self._attach_records(out["total"], [b for a in out["bins"] for p_ in a for row in p_ for b in row])
         return out
 
     # ------------------------------------------------------------------ flight recorder

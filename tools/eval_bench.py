@@ -4,6 +4,8 @@ networks (the timing does not depend on the weights), graph replay and the eager
   python tools/eval_bench.py [--task go2] [--num_envs 4096] [--steps N] [--repeats 3] [--out FILE]
   python tools/eval_bench.py --push_vel 0,0.5,1.0,1.5 [--push_dirs 8] ...   # + the push test (run_push_test)
   python tools/eval_bench.py --force_n 0,20,40,80 [--force_dirs 8] ...   # + the force test (run_force_test)
+  python tools/eval_bench.py --scan_offset_m=-0.1,0,0.1 [--scan_noise_m ..] [--scan_dropout ..] [--scan_delay_ms 0,40,80] ...
+                                                     # + the scan test (run_scan_test; --task go2 or go2_parkour)
   python tools/eval_bench.py --trace_depth 100 ...   # + the plain run with the flight recorder on, and traces()
   python tools/eval_bench.py --gait ...   # + the plain run with the gait record on (run(gait=True))
   python tools/eval_bench.py --joints ...   # + the plain run with the joint-load record on (run(joints=True))
@@ -65,6 +67,13 @@ def main():
                    help="also time run_force_test with these forces (the env is built with scheduled_commands and "
                         "scheduled_forces; not with --push_vel or --cmd_vx)")
     p.add_argument("--force_dirs", type=int, default=8)
+    floats = lambda s: [float(v) for v in s.split(",")]  # noqa: E731
+    p.add_argument("--scan_noise_m", type=floats, default=None,
+                   help="also time run_scan_test over this grid (any of the four --scan_* lists; the env is built with "
+                        "domain_rand.scan_model and the scan history the largest latency needs; not with the other tests)")
+    p.add_argument("--scan_dropout", type=floats, default=None)
+    p.add_argument("--scan_offset_m", type=floats, default=None)
+    p.add_argument("--scan_delay_ms", type=floats, default=None)
     p.add_argument("--trace_depth", type=int, default=None,
                    help="also time run(trace_depth=K), the flight recorder, and traces('falls', 16) after it")
     p.add_argument("--gait", action="store_true", help="also time run(gait=True), the gait record")
@@ -75,7 +84,9 @@ def main():
     p.add_argument("--merge")
     p.add_argument("--out")
     a = p.parse_args()
-    assert sum(bool(v) for v in (a.push_vel, a.cmd_vx, a.force_n)) <= 1, "--push_vel, --cmd_vx or --force_n, one at a time"
+    scan = any(v is not None for v in (a.scan_noise_m, a.scan_dropout, a.scan_offset_m, a.scan_delay_ms))
+    assert sum(bool(v) for v in (a.push_vel, a.cmd_vx, a.force_n, scan)) <= 1, \
+        "--push_vel, --cmd_vx, --force_n or --scan_*, one at a time"
     if a.stats:
         return merge_stats(a.stats, a.merge)
     import torch
@@ -92,6 +103,9 @@ def main():
         cfg.commands.scheduled_commands = True  # likewise: bound, every entry unused
     if a.force_n:
         cfg.commands.scheduled_commands = cfg.domain_rand.scheduled_forces = True  # likewise: bound, nothing scheduled
+    scan_delay_s = [ms / 1000.0 for ms in (a.scan_delay_ms or [0.0])]
+    if scan:  # bound with neutral values: the plain run then launches the SENSOR instance of the step kernel
+        cfg.domain_rand.scan_model, cfg.domain_rand.max_scan_delay_s = True, max(scan_delay_s)
     args = get_args([f"--task={a.task}", "--headless", f"--num_envs={a.num_envs}", "--seed=1",
                      f"--sim_device={a.device}", f"--rl_device={a.device}"])
     env, _ = task_registry.make_env(a.task, args, env_cfg=cfg)
@@ -120,6 +134,9 @@ def main():
                                                             graph=graph))
     if a.force_n:
         add("force", lambda steps, graph: ev.run_force_test(a.force_n, directions=a.force_dirs, num_steps=steps, graph=graph))
+    if scan:
+        add("scan", lambda steps, graph: ev.run_scan_test(a.scan_noise_m or (0.0,), a.scan_dropout or (0.0,),
+                                                          a.scan_offset_m or (0.0,), scan_delay_s, num_steps=steps, graph=graph))
     records = [flag for flag in ("gait", "joints", "contacts") if getattr(a, flag)]  # flag = mode prefix = report key
     for flag in records:
         add(flag, lambda steps, graph, flag=flag: ev.run(steps, graph, **{flag: True}))
@@ -148,7 +165,7 @@ def main():
                      # count / status / reset flags) in, one 304-byte row and the count out
                      "record_bytes_in_per_step": n * (8 + 69 * 4 + env.num_bodies * 12 + 4 + 1 + 1),
                      "record_bytes_out_per_step": n * (304 + 4)}
-    pr, cr, fr = last.get("push"), last.get("cmd"), last.get("force")
+    pr, cr, fr, sr = last.get("push"), last.get("cmd"), last.get("force"), last.get("scan")
     r = ev.run(a.steps) if len(runs) > 1 else r
     doc = {"task": a.task, "num_envs": a.num_envs, "num_steps": r["num_steps"], "fused_act": ev._fused is not None,
            "env_steps_per_s": {m: {"median": sorted(v)[len(v) // 2], "runs": [round(x) for x in v]}
@@ -188,6 +205,10 @@ def main():
             {"force_n": v, "episodes": sum(c["episodes"] for c in row), "survivors": sum(c["survivors"] for c in row),
              "forced": sum(c["forced"] for c in row),
              "compliance_m_per_s_per_n": [c["compliance_m_per_s_per_n"] for c in row]} for v, row in zip(fr["forces_n"], fr["bins"])]
+    if sr:
+        doc["scan_test"] = {k: sr[k] for k in ("noise_m", "dropout", "dropout_value", "offset_x_m", "delay_s", "delay_steps", "total")}
+        doc["scan_test"]["survival_rate"] = [[[[c["survival_rate"] for c in r_] for r_ in p_] for p_ in n_] for n_ in sr["bins"]]
+        doc["scan_test"]["episodes"] = [[[[c["episodes"] for c in r_] for r_ in p_] for p_ in n_] for n_ in sr["bins"]]
     print(json.dumps(doc))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
